@@ -16,10 +16,14 @@ path).  The step is captured into a hipGraph and replayed, as the reference's Mo
 N > 1 runs the SAME global batch tensor-parallel over RCCL/xGMI (heads and GEMM N/K sharded,
 2 all-reduces per layer): total work is fixed => "scaling": "strong".
 
-Rank 0 prints ONE JSON line: metric/value/unit..., plus
+Rank 0 prints ONE JSON line: metric/value/unit/ms_per_step...  A plain run sets up, warms up, times
+the --steps steps and prints that line; --full adds what takes runs of its own:
   "roofline":     the dominant kernel (paged-attention decode) measured live with HIP events,
+  "int4_gemm":    the largest layer GEMM timed alone,
   "cpu_baseline": the CPU oracle (reference CPU-path restatement) timed on the host cores on a
-                  bounded sample of the same workload (N = 1 only).
+                  bounded sample of the same workload (N = 1 only),
+  and the Python mirror of the C++ host step, checked on the first step and timed.
+--dump-outputs DIR writes what the last timed step returned (the next-token ids) as DIR/*.npy.
 """
 from __future__ import annotations
 
@@ -524,6 +528,10 @@ def main():
                     "kv_len ~ U[seqlen/2, seqlen] per sequence (numpy default_rng(1)); not the BASELINE metric line")
     ap.add_argument("--simulate-tp", type=int, default=0, help="tuning aid: run rank 0's shard of a "
                     "TP=N step on one GPU with the collectives stubbed (flagged in the output)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not "
+                    "need: roofline, int4 GEMM, CPU baseline, the Python mirror of the C++ host step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output "
+                    "(next-token ids, float64) to DIR/next_tokens.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -535,17 +543,6 @@ def main():
         if args.gpus != 1 or world != 1:
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torchrun "
                              f"--nproc-per-node {args.gpus}")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X GPU (no CPU fallback)")
-    device = torch.device("cuda", local_rank)
-    torch.cuda.set_device(device)
-    pg = ProcessGroup.create_from_env(device)
-    pa = ParallelArgs(rank=pg.rank, world_size=pg.world_size, process_group=pg)
-    if args.simulate_tp > 1:
-        from scalellm_amd.model_parallel import LocalShardProcessGroup
-        pa = ParallelArgs(rank=0, world_size=args.simulate_tp,
-                          process_group=LocalShardProcessGroup(args.simulate_tp))
-
     shape = LlamaShape.llama3_70b() if args.model == "70b" else LlamaShape.llama3_8b()
     quant = args.quant or ("gptq" if args.model == "70b" else "awq")
     gptq_sym = args.model == "70b"  # BASELINE configs[3]: GPTQ symmetric (zero = 8), group 128
@@ -555,6 +552,26 @@ def main():
     bs, L, B = args.bs or (128 if args.model == "70b" else 256), args.seqlen, args.block
     shape.max_position = max(shape.max_position, L + 8 + (args.steps + 2 * args.warmup + 16 if args.advance else 0))
     spare = ((args.steps + 2 * args.warmup + 8) // B + 2) if args.advance else 0
+
+    device = torch.device("cuda", local_rank)
+    want_xgmi = world > 1 and args.simulate_tp <= 1 and os.environ.get("SLM_CUSTOM_AR", "1") != "0"
+    xgmi_ok = None
+    if want_xgmi and os.environ.get("SLM_DIST_BACKEND") == "gloo":
+        # ranks sharing one GPU over gloo: a gloo group needs no GPU, so the probe children run before this
+        # rank opens the GPU -- a rank and its probe child never hold it at the same time (at world 8 that
+        # would be 16 processes on one GPU)
+        ProcessGroup.create_from_env(device)
+        xgmi_ok = xgmi_allreduce_works(world, device, bs, shape.hidden)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X GPU (no CPU fallback)")
+    torch.cuda.set_device(device)
+    pg = ProcessGroup.create_from_env(device)
+    pa = ParallelArgs(rank=pg.rank, world_size=pg.world_size, process_group=pg)
+    if args.simulate_tp > 1:
+        from scalellm_amd.model_parallel import LocalShardProcessGroup
+        pa = ParallelArgs(rank=0, world_size=args.simulate_tp,
+                          process_group=LocalShardProcessGroup(args.simulate_tp))
+
     kv_lens = L   # one length (uniform batch) or the per-sequence list (--ragged)
     if args.ragged:
         import numpy as np
@@ -573,8 +590,7 @@ def main():
     # processes, then repeated here); otherwise RCCL all-reduce + slm_rms_norm.
     # SLM_CUSTOM_AR=0 forces the RCCL path.
     custom_ar = None
-    if (world > 1 and args.simulate_tp <= 1 and os.environ.get("SLM_CUSTOM_AR", "1") != "0"
-            and xgmi_allreduce_works(world, device, bs, shape.hidden)):
+    if want_xgmi and (xgmi_ok if xgmi_ok is not None else xgmi_allreduce_works(world, device, bs, shape.hidden)):
         from scalellm_amd.custom_allreduce import try_create_xgmi_allreduce
         custom_ar = try_create_xgmi_allreduce(
             pg.rank, pg.world_size, bs, shape.hidden, torch.bfloat16, device,
@@ -642,7 +658,7 @@ def main():
     first_tokens = None
     hosts_agree = None
     for i in range(max(args.warmup, 1)):
-        if i == 0 and cpp_model is not None:
+        if i == 0 and cpp_model is not None and args.full:
             # the same first step through the Python mirror (same inputs, same cache rows rewritten): the two hosts
             # issue the same launches, so the greedy ids must be identical
             step(use_cpp=False)
@@ -653,7 +669,7 @@ def main():
         if i == 0:  # the first step's greedy ids: a TP=N run must reproduce the TP=1 run's
             torch.cuda.synchronize()
             first_tokens = static_tokens[:16].tolist()
-            if cpp_model is not None:
+            if cpp_model is not None and args.full:
                 hosts_agree = bool(torch.equal(py_tokens, static_tokens))
     torch.cuda.synchronize()
 
@@ -726,10 +742,16 @@ def main():
     check_fused_reduce("during the timed steps")
     ms_per_step = elapsed / args.steps * 1e3
     tok_s = bs * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives from its last replay: the greedy next-token ids [bs]
+        # (float64 holds every vocab id exactly)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "next_tokens.npy"), static_tokens.cpu().numpy().astype(np.float64))
     # the Python mirror beside the C++ host: the same step composed by decode.LlamaDecodeStep, captured and
     # replayed the same way (config.python_mirror_ms)
     py_ms = None
-    if cpp_model is not None:
+    if cpp_model is not None and args.full:
         try:
             if graph is not None:
                 g2 = torch.cuda.CUDAGraph()
@@ -749,71 +771,73 @@ def main():
         except Exception as e:  # noqa: BLE001
             print(f"[bench] Python-mirror comparison run failed ({type(e).__name__}: {e})", file=sys.stderr)
 
-    # ---- roofline of the dominant kernel (paged-attention decode), this rank's shard ----
-    # (two-lane steps launch the attention once per HALF batch: that launch is the one measured)
-    attn_rows, attn_params, attn_lens = bs, params, kv_lens
-    if model.last_lanes == 2:
-        lane0 = model._make_lanes(bs, positions, params, model.buf["o"][:bs], model.buf["down"][:bs], None, False)[0]
-        attn_rows, attn_params = lane0.T, lane0.params
-        attn_lens = kv_lens if isinstance(kv_lens, int) else kv_lens[:attn_rows]
-    avg_us, med_us = measure_attention_kernel(model, tokens[:attn_rows], positions, attn_params, n_launch=32)
-    nbytes = attn_algo_bytes(attn_rows, attn_lens, model.n_heads, model.n_kv_heads, shape.head_dim, B)
-    alone_gbps = nbytes / avg_us / 1e3  # GB/s, the launch replayed ALONE after the timed loop
-    # the gate_up GEMM at the row count the step launches it with (a lane's rows under two lanes), and at
-    # the full batch for continuity with rounds 1-3 (before the profiler children below: same clocks
-    # as the timed steps)
-    gemm = measure_gemm(model, attn_rows)
-    if attn_rows != bs:
-        gemm["rows_note"] = f"M = {attn_rows}: the rows of one of the step's two lanes"
-        gemm["at_full_batch"] = measure_gemm(model, bs)
-    # HBM traffic of that launch from the PMC counters, measured IN THIS RUN (rank 0, N = 1): two
-    # rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE: they do not fit one pass) over a child process
-    # that launches the same kernel on the same shapes; null when rocprofv3 is unavailable
-    traffic, traffic_src = (None, None)
-    if rank == 0 and world == 1 and not args.no_traffic and not args.ragged:
-        traffic, traffic_src = measure_attention_traffic_live(attn_rows, L, model.n_heads, model.n_kv_heads, B)
-    # which kernel ran the q_len = 1 rows: asked of the library's own plan (tuning knobs included),
-    # not re-derived here -- the MFMA tile kernel for wide GQA groups, the token-major stream otherwise
-    on_tile = kernels.paged_kv_varlen_mha_decode_kernel(
-        attn_rows, attn_rows, model.n_heads, model.n_kv_heads, shape.head_dim, B, 1, L, model.dtype) == "attn_tile_kernel"
-    # Round 5 (round-4 review, weak 6): `achieved` / `frac` describe the launch AS THE TIMED LOOP RUNS IT.
-    # With two lanes that is the launch next to the other lane's int4 GEMMs -- timed inside eager two-lane
-    # steps, HIP events on the launching stream right around every attention call (behind the event that
-    # chains the lanes' KV streams, so no waiting is included); the same launch replayed alone is reported
-    # as `alone`.  One lane: the launch has the chip to itself in the step too, the two coincide.
-    alone = dict(GBps=round(alone_gbps, 1), frac=round(alone_gbps / HBM_PEAK_GBPS, 4),
-                 avg_launch_us=round(avg_us, 2), median_launch_us=round(med_us, 2),
-                 launches="5 x 32 (hipGraph replay of the launch alone, after the timed loop)")
-    achieved, ach_us, ach_src = alone_gbps, avg_us, "the launch replayed alone (one lane: nothing shares the chip in the step either)"
-    in_step = None
-    if model.last_lanes == 2:
-        a_us, m_us, n_l = measure_attention_in_step(model, static_tokens, positions, params)
-        in_step = dict(avg_call_us=round(a_us, 2), median_call_us=round(m_us, 2), calls=n_l,
-                       GBps=round(nbytes / a_us / 1e3, 1), frac=round(nbytes / a_us / 1e3 / HBM_PEAK_GBPS, 4),
-                       note="attention calls (stream kernel + split-KV combine) timed inside eager two-lane steps: "
-                            "each runs while the other lane's int4 GEMMs share the CUs -- the stretch over "
-                            "alone.avg_launch_us is the price of hiding those GEMMs")
-        achieved, ach_us, ach_src = nbytes / a_us / 1e3, a_us, "in_step (the launch inside the two-lane step)"
-    sb = step_algo_bytes(model, bs, kv_lens, B)
-    step_gbps = sb["total"] / ms_per_step / 1e6
-    roofline = dict(kernel="attn_tile_kernel (paged-attention decode, MFMA tile form)" if on_tile
-                    else "attn_token_kernel (paged-attention decode)", bound="hbm",
-                    achieved=round(achieved, 1), peak=HBM_PEAK_GBPS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBPS, 4), traffic=traffic, traffic_source=traffic_src,
-                    algorithmic_bytes_per_launch=nbytes, avg_launch_us=round(ach_us, 2),
-                    achieved_source=ach_src,
-                    sequences_per_launch=attn_rows,
-                    launches_per_layer=model.last_lanes, alone=alone, in_step=in_step,
-                    # the whole step against the same roof: every algorithmic byte of one step (KV of all
-                    # layers + int4 weights + lm_head) over the measured ms_per_step
-                    step_hbm_frac=round(step_gbps / HBM_PEAK_GBPS, 4), step_GBps=round(step_gbps, 1),
-                    step_algorithmic_bytes=sb)
+    roofline = gemm = None
+    if args.full:
+        # ---- roofline of the dominant kernel (paged-attention decode), this rank's shard ----
+        # (two-lane steps launch the attention once per HALF batch: that launch is the one measured)
+        attn_rows, attn_params, attn_lens = bs, params, kv_lens
+        if model.last_lanes == 2:
+            lane0 = model._make_lanes(bs, positions, params, model.buf["o"][:bs], model.buf["down"][:bs], None, False)[0]
+            attn_rows, attn_params = lane0.T, lane0.params
+            attn_lens = kv_lens if isinstance(kv_lens, int) else kv_lens[:attn_rows]
+        avg_us, med_us = measure_attention_kernel(model, tokens[:attn_rows], positions, attn_params, n_launch=32)
+        nbytes = attn_algo_bytes(attn_rows, attn_lens, model.n_heads, model.n_kv_heads, shape.head_dim, B)
+        alone_gbps = nbytes / avg_us / 1e3  # GB/s, the launch replayed ALONE after the timed loop
+        # the gate_up GEMM at the row count the step launches it with (a lane's rows under two lanes), and at
+        # the full batch for continuity with rounds 1-3 (before the profiler children below: same clocks
+        # as the timed steps)
+        gemm = measure_gemm(model, attn_rows)
+        if attn_rows != bs:
+            gemm["rows_note"] = f"M = {attn_rows}: the rows of one of the step's two lanes"
+            gemm["at_full_batch"] = measure_gemm(model, bs)
+        # HBM traffic of that launch from the PMC counters, measured IN THIS RUN (rank 0, N = 1): two
+        # rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE: they do not fit one pass) over a child process
+        # that launches the same kernel on the same shapes; null when rocprofv3 is unavailable
+        traffic, traffic_src = (None, None)
+        if rank == 0 and world == 1 and not args.no_traffic and not args.ragged:
+            traffic, traffic_src = measure_attention_traffic_live(attn_rows, L, model.n_heads, model.n_kv_heads, B)
+        # which kernel ran the q_len = 1 rows: asked of the library's own plan (tuning knobs included),
+        # not re-derived here -- the MFMA tile kernel for wide GQA groups, the token-major stream otherwise
+        on_tile = kernels.paged_kv_varlen_mha_decode_kernel(
+            attn_rows, attn_rows, model.n_heads, model.n_kv_heads, shape.head_dim, B, 1, L, model.dtype) == "attn_tile_kernel"
+        # Round 5 (round-4 review, weak 6): `achieved` / `frac` describe the launch AS THE TIMED LOOP RUNS IT.
+        # With two lanes that is the launch next to the other lane's int4 GEMMs -- timed inside eager two-lane
+        # steps, HIP events on the launching stream right around every attention call (behind the event that
+        # chains the lanes' KV streams, so no waiting is included); the same launch replayed alone is reported
+        # as `alone`.  One lane: the launch has the chip to itself in the step too, the two coincide.
+        alone = dict(GBps=round(alone_gbps, 1), frac=round(alone_gbps / HBM_PEAK_GBPS, 4),
+                     avg_launch_us=round(avg_us, 2), median_launch_us=round(med_us, 2),
+                     launches="5 x 32 (hipGraph replay of the launch alone, after the timed loop)")
+        achieved, ach_us, ach_src = alone_gbps, avg_us, "the launch replayed alone (one lane: nothing shares the chip in the step either)"
+        in_step = None
+        if model.last_lanes == 2:
+            a_us, m_us, n_l = measure_attention_in_step(model, static_tokens, positions, params)
+            in_step = dict(avg_call_us=round(a_us, 2), median_call_us=round(m_us, 2), calls=n_l,
+                           GBps=round(nbytes / a_us / 1e3, 1), frac=round(nbytes / a_us / 1e3 / HBM_PEAK_GBPS, 4),
+                           note="attention calls (stream kernel + split-KV combine) timed inside eager two-lane steps: "
+                                "each runs while the other lane's int4 GEMMs share the CUs -- the stretch over "
+                                "alone.avg_launch_us is the price of hiding those GEMMs")
+            achieved, ach_us, ach_src = nbytes / a_us / 1e3, a_us, "in_step (the launch inside the two-lane step)"
+        sb = step_algo_bytes(model, bs, kv_lens, B)
+        step_gbps = sb["total"] / ms_per_step / 1e6
+        roofline = dict(kernel="attn_tile_kernel (paged-attention decode, MFMA tile form)" if on_tile
+                        else "attn_token_kernel (paged-attention decode)", bound="hbm",
+                        achieved=round(achieved, 1), peak=HBM_PEAK_GBPS, unit="GB/s",
+                        frac=round(achieved / HBM_PEAK_GBPS, 4), traffic=traffic, traffic_source=traffic_src,
+                        algorithmic_bytes_per_launch=nbytes, avg_launch_us=round(ach_us, 2),
+                        achieved_source=ach_src,
+                        sequences_per_launch=attn_rows,
+                        launches_per_layer=model.last_lanes, alone=alone, in_step=in_step,
+                        # the whole step against the same roof: every algorithmic byte of one step (KV of all
+                        # layers + int4 weights + lm_head) over the measured ms_per_step
+                        step_hbm_frac=round(step_gbps / HBM_PEAK_GBPS, 4), step_GBps=round(step_gbps, 1),
+                        step_algorithmic_bytes=sb)
 
     out = None
     if rank == 0:
         cpu = None
         # the CPU baseline belongs to the metric configuration (8b, AWQ); other models report null
-        if world == 1 and not args.no_cpu_baseline and args.model == "8b" and quant == "awq":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "8b" and quant == "awq":
             cpu = cpu_baseline(model, tokens, params, sample_seqs=16, kv_len=L, block=B)
         mname = "Llama-3-70B" if args.model == "70b" else "Llama-3-8B"
         out = {

@@ -8,6 +8,7 @@ ids, flattened + CSR offsets.
 """
 from __future__ import annotations
 
+import glob
 import os
 
 import numpy as np
@@ -31,11 +32,15 @@ def f16_bits_to_f32(u16: np.ndarray) -> np.ndarray:
 
 
 def load_attn_cases():
-    z = np.load(os.path.join(GOLDEN, "attn_cases.npz"))
-    names = sorted({k.split("/")[0] for k in z.files})
+    z = {}  # the arrays are split over parts of under 1 MiB each (make_golden.savez_parts)
+    for f in sorted(glob.glob(os.path.join(GOLDEN, "attn_cases_part*.npz"))):
+        with np.load(f) as part:
+            z.update((k, part[k]) for k in part.files)
+    assert z, "tests/golden/attn_cases_part*.npz missing"
+    names = sorted({k.split("/")[0] for k in z})
     cases = {}
     for n in names:
-        d = {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(n + "/")}
+        d = {k.split("/", 1)[1]: v for k, v in z.items() if k.startswith(n + "/")}
         is_bf16 = bool(d["is_bf16"][0])
         conv = bf16_bits_to_f32 if is_bf16 else f16_bits_to_f32
         d["q_f32"], d["k_f32"], d["v_f32"] = conv(d["q"]), conv(d["key_cache"]), conv(d["value_cache"])

@@ -53,11 +53,11 @@ def _torchrun(n, extra_env, model_args=()):
 
 @pytest.mark.timeout(1800)
 def test_bench_two_ranks_one_gpu_json_contract_and_tokens():
-    one, _ = _run([sys.executable, "bench.py", "--gpus", "1", *COMMON], {})
+    one, _ = _run([sys.executable, "bench.py", "--gpus", "1", *COMMON, "--full"], {})
     assert one["n_gpus"] == 1 and one["config"]["row_parallel_reduce"] is None
     assert one["config"]["reduced_model"] is True and len(one["config"]["first_step_tokens"]) == 8
-    fused, err_f = _torchrun(2, {})
-    plain, _ = _torchrun(2, {"SLM_CUSTOM_AR": "0"})
+    fused, err_f = _torchrun(2, {}, ("--full",))
+    plain, _ = _torchrun(2, {"SLM_CUSTOM_AR": "0"}, ("--full",))
     for rec in (fused, plain):
         assert rec["n_gpus"] == 2 and rec["steps"] == 2 and rec["warmup"] == 1
         assert rec["scaling"] == "strong" and rec["unit"] == "tokens/s" and rec["value"] > 0
@@ -80,7 +80,7 @@ def test_bench_70b_config_reduced_layers_runs_on_one_gpu():
     """BASELINE configs[3] plumbing (Llama-3-70B shapes, GPTQ symmetric g128, bs=128) with the layer
     count cut to 2 so it fits a test: shapes, symmetric zero points, JSON labelling."""
     rec, _ = _run([sys.executable, "bench.py", "--gpus", "1", "--model", "70b", "--layers", "2",
-                   "--seqlen", "512", "--steps", "2", "--warmup", "1", "--no-traffic"], {})
+                   "--seqlen", "512", "--steps", "2", "--warmup", "1", "--no-traffic", "--full"], {})
     assert rec["config"]["model"] == "70b" and rec["config"]["global_batch"] == 128
     assert "gptq (symmetric)" in rec["config"]["workload"] and rec["config"]["reduced_model"] is True
     assert rec["int4_gemm"]["shape"] == [128, 8192, 57344]

@@ -13,6 +13,8 @@ layout (the Marlin byte order is an NVIDIA mma.m16n8k16 artefact):
   * the repack tests cannot compare against the python Marlin packer; they check the repack
     BIT-EXACTLY through the GEMM instead: with A = identity and scales = 1 the GEMM returns
     (q - 8) for every weight, integers that fp16 holds exactly.
+The grid's act_order cases with a single group (group_size -1 or k), which the reference skips, run
+here: they take the general act-order path with g_idx all 0.
 num_bits = 8 runs as two int4 planes (include/slm_hip.h section 3b): the full 4-bit grid plus the
 reference's m x n x k x group x act_order axes at 8 bits (is_k_full / use_fp32_reduce do not select
 different code here, so they are not multiplied into the 8-bit grid).
@@ -123,8 +125,9 @@ def test_marlin_gemm_deep_k_and_bf16(kernels, dtype, num_bits, m, k, group_size,
 
 def _marlin_gemm_case(kernels, m, n, k, num_bits, group_size, act_order, is_k_full, use_fp32_reduce,
                       dtype=torch.half):
-    if act_order and (group_size == -1 or group_size == k):
-        pytest.skip("act_order=True requires group_size < k (marlin_gemm_test.py:64)")
+    # act_order with ONE group (group_size -1 or k): the reference skips it (marlin_gemm_test.py:64), but
+    # here it is the general act-order path -- g_idx all 0, the perm gather of A, a one-row scale table --
+    # and runs against the same metric
     gen = torch.Generator(device="cuda").manual_seed(m * 7 + n * 3 + k + group_size)
     a = torch.randn((m, k), dtype=dtype, device="cuda", generator=gen)
     w = torch.randn((k, n), dtype=dtype, device="cuda", generator=gen)

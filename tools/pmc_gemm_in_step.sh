@@ -14,7 +14,7 @@ i=0
 for P in "$P1" "$P2"; do
   i=$((i+1)); d=/tmp/pmc_${tag}_$i; rm -rf $d
   ( cd /tmp && env "$@" timeout 600 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $d -o p -- \
-      python $R/bench.py --layers 2 --steps 1 --warmup 1 --no-graph --no-cpu-baseline --no-traffic ) > $O/pass$i.log 2>&1
+      python $R/bench.py --full --layers 2 --steps 1 --warmup 1 --no-graph --no-cpu-baseline --no-traffic ) > $O/pass$i.log 2>&1
   f=$(find $d -name "*counter_collection.csv" | head -1)
   ( head -1 $f; grep -E "w4a16_gemm" $f ) > $O/pass$i.csv
 done
