@@ -44,7 +44,8 @@ typedef enum slm_status {
 
 typedef enum slm_dtype {
   SLM_F16 = 0,  /* IEEE half   (torch::kHalf)     */
-  SLM_BF16 = 1  /* bfloat16    (torch::kBFloat16) */
+  SLM_BF16 = 1, /* bfloat16    (torch::kBFloat16) */
+  SLM_F32 = 2   /* IEEE float  (torch::kFloat32): the logits of section 8 only */
 } slm_dtype;
 
 SLM_API const char* slm_status_string(int status);
@@ -565,6 +566,97 @@ SLM_API int slm_decode_lane_policy_record(const slm_lane_query* q, float one_lan
 SLM_API int slm_decode_lane_policy_clear(void);
 /* 1 if a recorded measurement (not the constants) would decide q, else 0 */
 SLM_API int32_t slm_decode_lane_policy_measured(const slm_lane_query* q);
+
+/* ========================================================================== */
+/* 8. Logits processing and sampling (one launch per call)                    */
+/*    replaces  LogitsProcessor::create + Sampler::forward as Worker::        */
+/*              execute_model runs them (src/engine/worker.cpp:154-187):      */
+/*              kernel::apply_frequency_presence_penalty / apply_repetition_  */
+/*              penalty / apply_temperature_penalty (src/kernels/sampling/    */
+/*              penalty_kernels.cu:9-143), TopKTopPLogitsProcessor            */
+/*              (src/sampling/logits_processor.h:224-284) and Sampler         */
+/*              (src/sampling/sampler.cpp:19-70).                             */
+/*    Per row r of logits [n_rows, vocab], all arithmetic in fp32 on the      */
+/*    widened logits, rounded nowhere in between, in this order:              */
+/*     1. for the first lens[r] entries j with counts[j] > 0 (padding beyond  */
+/*        lens is never touched -- the GPU kernel's semantics; the CPU        */
+/*        detail:: version of the reference also penalises padding id 0):     */
+/*          l[id] -= (float)count * freq;  l[id] -= pres   (two roundings)    */
+/*     2. for the first lens[r] ids:  l = l < 0 ? l * rep : l / rep           */
+/*     3. l *= (1.0f / t)   (IEEE reciprocal, as the reference's kernel;      */
+/*        t == 0 counts as 1)                                                 */
+/*     4. top-k: k <= 0 or k >= vocab is off; keep the k largest              */
+/*     5. top-p: p = softmax over the top-k survivors; in descending order    */
+/*        keep rank j iff (mass ranked before j) <= top_p -- rank 0 always;   */
+/*        top_p >= 1 is off.  The masses are summed in 64-bit fixed point     */
+/*        (2^-40 units) with integer atomics: exact and order-independent.    */
+/*     6. processed = l where kept, -inf elsewhere; probs = softmax(processed)*/
+/*        do_sample[r] == 0: argmax(processed), else argmax(probs / E) with   */
+/*        E_i ~ Exp(1) drawn for the survivors only                           */
+/*     7. logprob = log_softmax(processed) at the token; top-n (n <= 20)      */
+/*        values and ids of log_softmax(processed), descending                */
+/*    Ties: every ordering (top-k, top-p, argmax, top-n) is stable by index:  */
+/*    among equal values the lower vocab id ranks first (-0 == +0).           */
+/*    RNG: counter-based and stateless (graph replay safe).  Philox4x32-10,  */
+/*    key = seeds[r] (lo, hi words), counter = (lo32(i >> 2), hi32(i >> 2),  */
+/*    positions[r], 0), output word i & 3 -- rocRAND's                        */
+/*    philox4x32_10_engine(seed, positions[r], i).next().  With x that word:  */
+/*    u = ((x >> 8) + 0.5) * 2^-24 and E = -ln(u), evaluated as -logf(u) for */
+/*    u < 1/2 and -log1pf(-(1 - u)) above (both operands exact in fp32).     */
+/*    A row's outputs depend only on its logits, parameters, seed and         */
+/*    position: not on its row index, the batch, or eager vs graph replay.    */
+/*    Bit-identical across repeats (no float atomics; fixed reduction order). */
+/*    Finite logits assumed.  One 1024-thread workgroup per row.              */
+/* ========================================================================== */
+#define SLM_SAMPLE_MAX_TOP 20
+typedef struct slm_sampling_args {
+  const void* logits;               /* [n_rows, vocab], row stride logits_stride (elements)    */
+  int64_t logits_stride;
+  int32_t dtype;                    /* SLM_F16, SLM_BF16 or SLM_F32                              */
+  int32_t n_rows;
+  int32_t vocab;                    /* <= 2^22; <= 2^19 when a penalty is given                  */
+  int32_t max_unique;               /* row stride of unique_ids / unique_counts                  */
+  /* per-row parameters [n_rows], each NULL = neutral.  fp32: the reference holds them in the
+   * logits dtype (sampling/parameters.h:42-67); a caller that wants its exact bits widens those. */
+  const float* frequency_penalties;
+  const float* presence_penalties;
+  const float* repetition_penalties;
+  const float* temperatures;
+  const float* top_p;
+  const int64_t* top_k;             /* LongTensor, as the reference                              */
+  /* the penalised tokens: unique ids (int64, as the reference's tensors hold them; unique within a
+   * row's first lens entries, ids outside [0, vocab) are skipped), counts, lens */
+  const int64_t* unique_ids;        /* [n_rows, max_unique]                                      */
+  const int32_t* unique_counts;     /* [n_rows, max_unique]   (needed by frequency / presence)   */
+  const int32_t* unique_lens;       /* [n_rows]                                                  */
+  const uint8_t* do_sample;         /* [n_rows] bool, NULL = all greedy                          */
+  const uint64_t* seeds;            /* [n_rows], NULL = 0                                        */
+  const int32_t* positions;         /* [n_rows] position of the row's last input token, NULL = 0 */
+  /* outputs, each NULL = not wanted */
+  int32_t* next_tokens;             /* [n_rows] (slm_sample: required)                           */
+  void* processed;                  /* [n_rows, processed_stride] dtype: processed logits, rounded
+                                       once; may be `logits` itself (in place)                   */
+  int64_t processed_stride;
+  float* probs;                     /* [n_rows, vocab] fp32, contiguous                          */
+  float* logprobs;                  /* [n_rows]                                                  */
+  float* top_logprobs;              /* [n_rows, n_top]                                           */
+  int32_t* top_tokens;              /* [n_rows, n_top]                                           */
+  int32_t n_top;                    /* 0 .. min(SLM_SAMPLE_MAX_TOP, vocab)                       */
+  int32_t reserved;
+  void* workspace;                  /* penalised values: slm_sample_workspace_bytes              */
+  size_t workspace_bytes;
+} slm_sampling_args;
+
+/* scratch the call needs (0 without penalties); a pure function of host-side sizes */
+SLM_API size_t slm_sample_workspace_bytes(const slm_sampling_args* a);
+/* steps 1-7: next_tokens (+ the optional outputs).  SLM_ERR_INVALID_ARG: NULL logits / next_tokens,
+ * n_top outside 0..20 or > vocab, a penalty without its ids / counts / lens, bad sizes;
+ * SLM_ERR_UNSUPPORTED: dtype, vocab too large; SLM_ERR_WORKSPACE; n_rows == 0 is a no-op. */
+SLM_API int slm_sample(const slm_sampling_args* a, void* stream);
+/* steps 1-5 only: writes `processed` (required; do_sample / seeds / the other outputs are ignored).
+ * In place with penalties alone it touches only the penalised entries -- the drop-in form of
+ * kernel::apply_*_penalty, each rounding to the dtype when its call ends as the reference's do. */
+SLM_API int slm_logits_process(const slm_sampling_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libslm_hip.so")
 
 SLM_F16, SLM_BF16 = 0, 1
+SLM_F32 = 2  # logits of the sampling entry points (slm_hip.h section 8) only
+SLM_SAMPLE_MAX_TOP = 20
 SLM_W4_GPTQ, SLM_W4_AWQ = 0, 1
 SLM_W8_GPTQ, SLM_W8_AWQ = 2, 3  # 8-bit checkpoints: slm_w8_prepack_* (two int4 planes)
 SLM_W4_PAIRED = 0x10
@@ -85,6 +87,23 @@ class ArArgs(C.Structure):
         ("eps", C.c_float), ("dtype", C.c_int32),
         ("M", C.c_int64), ("H", C.c_int64),
         ("end_barrier", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SamplingArgs(C.Structure):
+    """struct slm_sampling_args (include/slm_hip.h section 8)."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("logits_stride", C.c_int64),
+        ("dtype", C.c_int32), ("n_rows", C.c_int32), ("vocab", C.c_int32), ("max_unique", C.c_int32),
+        ("frequency_penalties", C.c_void_p), ("presence_penalties", C.c_void_p),
+        ("repetition_penalties", C.c_void_p), ("temperatures", C.c_void_p), ("top_p", C.c_void_p),
+        ("top_k", C.c_void_p),
+        ("unique_ids", C.c_void_p), ("unique_counts", C.c_void_p), ("unique_lens", C.c_void_p),
+        ("do_sample", C.c_void_p), ("seeds", C.c_void_p), ("positions", C.c_void_p),
+        ("next_tokens", C.c_void_p), ("processed", C.c_void_p), ("processed_stride", C.c_int64),
+        ("probs", C.c_void_p), ("logprobs", C.c_void_p), ("top_logprobs", C.c_void_p),
+        ("top_tokens", C.c_void_p), ("n_top", C.c_int32), ("reserved", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
     ]
 
 
@@ -192,6 +211,9 @@ def lib() -> C.CDLL:
         ("slm_decode_lane_policy_record", C.c_int, [C.POINTER(LaneQuery), C.c_float, C.c_float]),
         ("slm_decode_lane_policy_clear", C.c_int, []),
         ("slm_decode_lane_policy_measured", C.c_int32, [C.POINTER(LaneQuery)]),
+        ("slm_sample_workspace_bytes", C.c_size_t, [C.POINTER(SamplingArgs)]),
+        ("slm_sample", C.c_int, [C.POINTER(SamplingArgs), C.c_void_p]),
+        ("slm_logits_process", C.c_int, [C.POINTER(SamplingArgs), C.c_void_p]),
     ]:
         fn = getattr(L, name)  # AttributeError here = library/header mismatch: fail loudly
         fn.restype = restype

@@ -37,6 +37,23 @@ def cpp_params(params):
     return q
 
 
+def cpp_sampling_params(sp):
+    """sampling.SamplingParameters -> slm::SamplingParameters (slm_sampling_hip.h), tensors shared (so an
+    in-place refresh of the Python object is what a captured C++ step reads)."""
+    shim = load_shim()
+    q = shim.SamplingParameters()
+    names = ["temperatures", "top_p", "top_k", "do_sample", "seeds"]
+    if sp.unique_token_ids is not None:  # without penalised tokens the penalties are no-ops (processing_kwargs)
+        names += ["frequency_penalties", "presence_penalties", "repetition_penalties", "unique_token_ids",
+                  "unique_token_counts", "unique_token_ids_lens"]
+    for name in names:
+        t = getattr(sp, name)
+        if t is not None:
+            setattr(q, name, t)
+    q.logprobs, q.max_top_logprobs = bool(sp.logprobs), int(sp.max_top_logprobs)
+    return q
+
+
 def from_decode_step(step, block_size: int, max_tokens: int, fused: bool = True, lanes: int = -1,
                      lanes_chain: bool = True, rank: int = 0, world_size: int = 1, kv_step=None):
     """slm::LlamaForCausalLMHip over the checkpoint tensors (LlamaDecodeStep(keep_checkpoint=True)), the

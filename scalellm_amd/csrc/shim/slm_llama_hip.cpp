@@ -556,4 +556,30 @@ torch::Tensor LlamaForCausalLMHip::decode_step(const torch::Tensor& tokens, cons
   return torch::argmax(lg, -1).to(torch::kInt);  // (16-bit logits: same index as the fp32 argmax, no 4-byte copy)
 }
 
+SampleOutput LlamaForCausalLMHip::sample_step(const torch::Tensor& tokens, const torch::Tensor& positions,
+                                              std::vector<KVCache>& kv_caches, const InputParameters& input_params,
+                                              const SamplingParameters& sampling) {
+  const auto h = forward(tokens, positions, kv_caches, input_params);
+  using torch::indexing::Slice;
+  const auto last = (input_params.q_cu_seq_lens.index({Slice(1, torch::indexing::None)}) - 1).to(torch::kLong);
+  const auto lg = logits(h, last);
+  const int64_t n = lg.size(0);
+  if (!sample_tok_.defined()) {  // static outputs at the maximum batch (a captured step keeps their addresses)
+    const int64_t T = opt_.max_tokens, K = SLM_SAMPLE_MAX_TOP;
+    sample_tok_ = torch::empty({T}, lg.options().dtype(torch::kInt));
+    sample_lp_ = torch::empty({T}, lg.options().dtype(torch::kFloat));
+    sample_top_lp_ = torch::empty({T * K}, lg.options().dtype(torch::kFloat));
+    sample_top_tok_ = torch::empty({T * K}, lg.options().dtype(torch::kInt));
+  }
+  const int64_t k = sampling.logprobs ? sampling.max_top_logprobs : 0;
+  SampleOutput out;
+  out.next_tokens = sample_tok_.narrow(0, 0, n);
+  if (sampling.logprobs) out.logprobs = sample_lp_.narrow(0, 0, n);
+  if (k > 0) {
+    out.top_logprobs = sample_top_lp_.narrow(0, 0, n * k).view({n, k});
+    out.top_tokens = sample_top_tok_.narrow(0, 0, n * k).view({n, k});
+  }
+  return sample(lg, sampling.narrow(n), positions.index_select(0, last), &out);
+}
+
 }  // namespace slm

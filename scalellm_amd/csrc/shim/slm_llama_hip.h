@@ -36,6 +36,7 @@
 
 #include "slm_attn_handler_hip.h"
 #include "slm_qlinear_hip.h"
+#include "slm_sampling_hip.h"
 #include "slm_torch_shim.h"
 
 namespace slm {
@@ -92,6 +93,14 @@ class LlamaForCausalLMHip {
   torch::Tensor decode_step(const torch::Tensor& tokens, const torch::Tensor& positions,
                             std::vector<KVCache>& kv_caches, const InputParameters& input_params,
                             bool return_logits);
+  // one decode step with sampling (Worker::execute_model, worker.cpp:154-187): forward -> logits of every
+  // sequence's last token -> slm::sample (processing + sampling, one launch) into static output buffers
+  // (views; capturable).  RNG position of a sequence = positions[q_cu_seq_lens[1:] - 1].  `sampling` has
+  // >= n_seqs rows (the caller owns it at the maximum batch and refreshes it in place before a replay).
+  // Under TP the gathered logits are sampled.  Mirror: decode.LlamaDecodeStep.forward(..., sampling=...)
+  SampleOutput sample_step(const torch::Tensor& tokens, const torch::Tensor& positions,
+                           std::vector<KVCache>& kv_caches, const InputParameters& input_params,
+                           const SamplingParameters& sampling);
   int last_lanes() const { return last_lanes_; }
   HipAttnHandler& handler() { return *handler_; }
   int64_t n_local_heads() const { return n_heads_; }
@@ -140,6 +149,7 @@ class LlamaForCausalLMHip {
   std::unique_ptr<HipAttnHandler> handler_;
   std::unique_ptr<AttentionImpl> atten_;
   std::vector<Layer> layers_;
+  torch::Tensor sample_tok_, sample_lp_, sample_top_lp_, sample_top_tok_;  // sample_step's outputs
   torch::Tensor embed_, final_norm_, lm_head_;  // embed [vocab, hidden / tp], lm_head [hidden, vocab / tp]
   bool embed_loaded_ = false, norm_loaded_ = false, lm_head_loaded_ = false;
   // static activation buffers [max_tokens, ...]

@@ -10,6 +10,7 @@
 #include "slm_attn_handler_hip.h"
 #include "slm_llama_hip.h"
 #include "slm_qlinear_hip.h"
+#include "slm_sampling_hip.h"
 #include "slm_torch_shim.h"
 
 namespace py = pybind11;
@@ -125,6 +126,46 @@ PYBIND11_MODULE(_slm_shim, m) {
       .def("block_size", &slm::KVCache::block_size)
       .def("get_kv_cache", &slm::KVCache::get_kv_cache)
       .def("set_kv_cache", &slm::KVCache::set_kv_cache);
+  // sampling (slm_sampling_hip.h): the reference's kernel-level functions and objects
+  m.def("apply_temperature_penalty", &llm::kernel::apply_temperature_penalty, py::arg("logits"), py::arg("temperatures"));
+  m.def("apply_repetition_penalty", &llm::kernel::apply_repetition_penalty, py::arg("logits"), py::arg("token_ids"),
+        py::arg("token_ids_lens"), py::arg("penalities"));
+  m.def("apply_frequency_presence_penalty", &llm::kernel::apply_frequency_presence_penalty, py::arg("logits"),
+        py::arg("token_ids"), py::arg("token_counts"), py::arg("token_ids_lens"), py::arg("frequency_penalties"),
+        py::arg("presence_penalties"));
+  m.def("invoke_softmax", &llm::kernel::invoke_softmax, py::arg("logits"));
+  py::class_<slm::SamplingParameters>(m, "SamplingParameters")
+      .def(py::init<>())
+      .def_readwrite("frequency_penalties", &slm::SamplingParameters::frequency_penalties)
+      .def_readwrite("presence_penalties", &slm::SamplingParameters::presence_penalties)
+      .def_readwrite("repetition_penalties", &slm::SamplingParameters::repetition_penalties)
+      .def_readwrite("temperatures", &slm::SamplingParameters::temperatures)
+      .def_readwrite("top_p", &slm::SamplingParameters::top_p)
+      .def_readwrite("top_k", &slm::SamplingParameters::top_k)
+      .def_readwrite("unique_token_ids", &slm::SamplingParameters::unique_token_ids)
+      .def_readwrite("unique_token_counts", &slm::SamplingParameters::unique_token_counts)
+      .def_readwrite("unique_token_ids_lens", &slm::SamplingParameters::unique_token_ids_lens)
+      .def_readwrite("do_sample", &slm::SamplingParameters::do_sample)
+      .def_readwrite("seeds", &slm::SamplingParameters::seeds)
+      .def_readwrite("logprobs", &slm::SamplingParameters::logprobs)
+      .def_readwrite("max_top_logprobs", &slm::SamplingParameters::max_top_logprobs);
+  py::class_<slm::SampleOutput>(m, "SampleOutput")
+      .def_readonly("next_tokens", &slm::SampleOutput::next_tokens)
+      .def_readonly("probs", &slm::SampleOutput::probs)
+      .def_readonly("logprobs", &slm::SampleOutput::logprobs)
+      .def_readonly("top_logprobs", &slm::SampleOutput::top_logprobs)
+      .def_readonly("top_tokens", &slm::SampleOutput::top_tokens);
+  m.def("sample", [](const torch::Tensor& logits, const slm::SamplingParameters& p, const torch::Tensor& positions,
+                     bool want_probs) { return slm::sample(logits, p, positions, nullptr, want_probs); },
+        py::arg("logits"), py::arg("params"), py::arg("positions"), py::arg("want_probs") = false);
+  m.def("logits_process", [](const torch::Tensor& logits, const slm::SamplingParameters& p, const torch::Tensor& ids,
+                             const torch::Tensor& counts, const torch::Tensor& lens) {
+          return slm::LogitsProcessor::create(p)->forward(logits, ids, counts, lens);
+        });
+  m.def("sampler_forward", [](const torch::Tensor& logits, const torch::Tensor& do_sample, bool logprobs,
+                              int64_t max_top_logprobs, const torch::Tensor& seeds, const torch::Tensor& positions) {
+          return slm::Sampler(do_sample, logprobs, max_top_logprobs, seeds, positions).forward(logits);
+        });
   py::class_<slm::InputParameters>(m, "InputParameters")
       .def(py::init<>())
       .def_readwrite("num_sequences", &slm::InputParameters::num_sequences)
@@ -232,6 +273,12 @@ PYBIND11_MODULE(_slm_shim, m) {
              return self.model->decode_step(tokens, positions, self.kv, params, return_logits);
            },
            py::arg("tokens"), py::arg("positions"), py::arg("params"), py::arg("return_logits") = false)
+      .def("sample_step",
+           [](PyLlama& self, const torch::Tensor& tokens, const torch::Tensor& positions,
+              const slm::InputParameters& params, const slm::SamplingParameters& sampling) {
+             return self.model->sample_step(tokens, positions, self.kv, params, sampling);
+           },
+           py::arg("tokens"), py::arg("positions"), py::arg("params"), py::arg("sampling"))
       .def("forward",
            [](PyLlama& self, const torch::Tensor& tokens, const torch::Tensor& positions,
               const slm::InputParameters& params) { return self.model->forward(tokens, positions, self.kv, params); })

@@ -199,6 +199,7 @@ class LlamaDecodeStep:
         self.lanes_chain = os.environ.get("SLM_DECODE_LANES_CHAIN", "1") != "0"
         self._side_stream = None
         self._lane_bufs = {}
+        self._sample_bufs = None  # static outputs of forward(sampling=...)
         self.last_lanes = 1
         self._pinned_lanes = None   # graph_variant(): 1 / 2 lanes pinned while a graph variant is captured
         tp = pa.world_size
@@ -665,8 +666,12 @@ class LlamaDecodeStep:
                 self._run_norm(ln, ln.pend)
 
     def forward(self, tokens: torch.Tensor, positions: torch.Tensor, params: InputParameters,
-                return_logits: bool = False) -> torch.Tensor:
-        """tokens/positions [T] int32 -> next-token ids [n_seqs] (greedy), last token per sequence."""
+                return_logits: bool = False, sampling=None):
+        """tokens/positions [T] int32 -> next-token ids [n_seqs] (greedy), last token per sequence.
+        sampling (sampling.SamplingParameters, >= n_seqs rows): the logits go through the fused
+        processing + sampling kernel instead, and the result is a sampling.SampleOutput whose tensors are
+        views of static buffers (capturable).  The RNG position of a sequence is the position of its
+        last input token."""
         s, b, pa = self.shape, self.buf, self.pa
         T = tokens.numel()
         if getattr(params, "kv_total_len", 0) == 0 and not torch.cuda.is_current_stream_capturing():
@@ -702,6 +707,15 @@ class LlamaDecodeStep:
         last = (params.q_cu_seq_lens[1:] - 1).long()
         self.last_hidden = normed[last]  # final-norm output of each sequence's last token (tests)
         logits = self.last_hidden @ self.lm_head  # plain library GEMM (hipBLASLt): not on the graded path
+        if sampling is not None and return_logits:
+            raise ValueError("forward(): return_logits and sampling exclude each other")
+        if sampling is not None:
+            # under TP the gathered logits are sampled: the kernel is deterministic, so every rank
+            # picks the same token (the greedy-over-shards exchange below stays greedy-only)
+            if pa.world_size > 1:
+                from .model_parallel import gather_from_model_parallel_region
+                logits = gather_from_model_parallel_region(logits, pa)
+            return self._sample(logits, positions[last], sampling)
         if ar is not None and not return_logits and last.numel() <= ar.max_tokens \
                 and 4 * pa.world_size <= s.hidden:
             return self._greedy_over_vocab_shards(logits, ar)
@@ -714,6 +728,23 @@ class LlamaDecodeStep:
         # argmax would give -- without writing and re-reading a 4-byte copy of [n_seqs, vocab])
         return torch.argmax(logits, dim=-1).to(torch.int32)
 
+
+    def _sample(self, logits: torch.Tensor, last_positions: torch.Tensor, sampling):
+        """The fused kernel over [n_seqs, vocab] logits into static output buffers (one set per step
+        object, sized at max_batch_tokens, so a captured step keeps its addresses)."""
+        from .sampling import SampleOutput, sample_logits
+        from ._lib import SLM_SAMPLE_MAX_TOP
+        n = logits.size(0)
+        T = self.buf["resid"].size(0)
+        if self._sample_bufs is None:
+            e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)  # noqa: E731
+            self._sample_bufs = dict(tok=e(T, dt=torch.int32), lp=e(T), top_lp=e(T * SLM_SAMPLE_MAX_TOP),
+                                     top_tok=e(T * SLM_SAMPLE_MAX_TOP, dt=torch.int32))
+        b, k = self._sample_bufs, sampling.max_top_logprobs
+        out = SampleOutput(b["tok"][:n], None, b["lp"][:n] if sampling.logprobs else None,
+                           b["top_lp"][:n * k].view(n, k) if sampling.logprobs and k else None,
+                           b["top_tok"][:n * k].view(n, k) if sampling.logprobs and k else None)
+        return sample_logits(logits, sampling.narrow(n), last_positions, out=out)
 
     def _greedy_over_vocab_shards(self, logits: torch.Tensor, ar) -> torch.Tensor:
         """argmax over the vocab-sharded logits without gathering them (and without RCCL): every

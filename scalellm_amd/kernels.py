@@ -94,6 +94,7 @@ _deferred_ws = {}    # slot 0
 _deferred_ws_b = {}  # slot 1: where a GEMM that CONSUMES slot-0 slabs (norm prologue) leaves its own
 _retired = []  # buffers replaced by bigger ones: still referenced by graphs captured before
 _deferred_gen = {}  # (device, slot) -> generation counter of that deferred-partials buffer
+_sampling_ws = {}   # penalised values of sample / logits_process (slm_sample_workspace_bytes)
 
 
 # scratch lane of the calling code path (workspace_lane): 0 unless a step runs two streams.  Per THREAD:
@@ -140,8 +141,10 @@ def _grow(table, nbytes: int, dev: torch.device, what: str) -> torch.Tensor:
     ws = table.get(key)
     if ws is None or ws.numel() < nbytes:
         if torch.cuda.is_current_stream_capturing():
+            kw = "sampling_nbytes" if table is _sampling_ws else \
+                "deferred_nbytes" if table is _deferred_ws or table is _deferred_ws_b else "nbytes"
             raise SlmError(f"{what} must be reserved before graph capture "
-                           f"(need {nbytes} bytes): call reserve_workspace() first")
+                           f"(need {nbytes} bytes): call reserve_workspace({kw}=...) first")
         size = max(int(nbytes), 1 << 20, 2 * ws.numel() if ws is not None else 0)
         if ws is not None:
             _retired.append(ws)  # never freed: earlier captures still point into it
@@ -151,12 +154,15 @@ def _grow(table, nbytes: int, dev: torch.device, what: str) -> torch.Tensor:
 
 
 def reserve_workspace(nbytes: int, device: Optional[torch.device] = None,
-                      deferred_nbytes: int = 0) -> torch.Tensor:
+                      deferred_nbytes: int = 0, sampling_nbytes: int = 0) -> torch.Tensor:
     """Size the per-device scratch once, before graph capture.  deferred_nbytes sizes BOTH deferred
     split-K slab buffers (slot 0 and slot 1: a GEMM whose norm prologue consumes slot-0 slabs leaves
     its own in slot 1), so a capture needs no warm-up of exactly that path and nothing is retired
-    later."""
+    later.  sampling_nbytes sizes the penalised-value scratch of sample / logits_process
+    (slm_sample_workspace_bytes: n_rows * max_unique * 4 bytes)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    if sampling_nbytes:
+        _grow(_sampling_ws, sampling_nbytes, dev, "sampling workspace")
     if deferred_nbytes:
         _grow(_deferred_ws, deferred_nbytes, dev, "deferred split-K buffer")
         _grow(_deferred_ws_b, deferred_nbytes, dev, "deferred split-K buffer (slot 1)")
@@ -927,3 +933,140 @@ def silu_and_mul(out: torch.Tensor, x: torch.Tensor) -> None:
     d = x.size(-1) // 2
     check(L.slm_silu_mul(out.data_ptr(), x.data_ptr(), x.numel() // (2 * d), d, _dtype_code(x),
                          _stream()), "slm_silu_mul")
+
+
+# ---------------------------------------------------------------------------------------
+# logits processing and sampling (include/slm_hip.h section 8, csrc/sampling.hip)
+#   apply_temperature_penalty / apply_repetition_penalty / apply_frequency_presence_penalty
+#       <- llm::kernel::*  src/kernels/sampling/sampling_kernels.h:7-25 (in place, rounded once)
+#   sample / logits_process
+#       <- LogitsProcessor::create + Sampler::forward, src/engine/worker.cpp:154-187 (fused)
+# ---------------------------------------------------------------------------------------
+
+
+def _logits_dtype_code(t: torch.Tensor) -> int:
+    return _lib.SLM_F32 if t.dtype == torch.float32 else _dtype_code(t)
+
+
+def _rows(t: Optional[torch.Tensor], n: int, dtype: torch.dtype, what: str) -> Optional[torch.Tensor]:
+    """A per-row parameter as a contiguous [n] tensor of `dtype` (the reference keeps them as
+    [n, 1] columns in the logits dtype: parameters.h:42-67, logits_processor.h:126-127)."""
+    if t is None:
+        return None
+    _require_gpu(t)
+    t = t.reshape(-1)
+    if t.numel() != n:
+        raise SlmError(f"{what}: {t.numel()} values for {n} rows")
+    return t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _sampling_call(fn, what: str, logits: torch.Tensor, *, frequency_penalties=None, presence_penalties=None,
+                   repetition_penalties=None, temperatures=None, top_k=None, top_p=None, unique_token_ids=None,
+                   unique_token_counts=None, unique_token_lens=None, do_sample=None, seeds=None, positions=None,
+                   next_tokens=None, processed=None, probs=None, logprobs=None, top_logprobs=None,
+                   top_tokens=None) -> None:
+    _require_gpu(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise SlmError("logits must be [n_rows, vocab] with contiguous rows")
+    n, V = logits.shape
+    a = _lib.SamplingArgs()
+    a.logits, a.logits_stride, a.dtype = logits.data_ptr(), logits.stride(0), _logits_dtype_code(logits)
+    a.n_rows, a.vocab = n, V
+    keep = []  # converted copies stay alive until the launch is issued
+
+    def rows(t, dtype, name):
+        t = _rows(t, n, dtype, name)
+        keep.append(t)
+        return _ptr(t)
+    a.frequency_penalties = rows(frequency_penalties, torch.float32, "frequency_penalties")
+    a.presence_penalties = rows(presence_penalties, torch.float32, "presence_penalties")
+    a.repetition_penalties = rows(repetition_penalties, torch.float32, "repetition_penalties")
+    a.temperatures = rows(temperatures, torch.float32, "temperatures")
+    a.top_p = rows(top_p, torch.float32, "top_p")
+    a.top_k = rows(top_k, torch.int64, "top_k")
+    a.do_sample = rows(do_sample, torch.bool, "do_sample")
+    a.seeds = rows(seeds, torch.int64, "seeds")   # uint64 seeds travel as their int64 bit pattern
+    a.positions = rows(positions, torch.int32, "positions")
+    if unique_token_ids is not None:
+        _require_gpu(unique_token_ids)
+        ids = unique_token_ids.reshape(n, -1)
+        ids = ids if (ids.dtype == torch.int64 and ids.is_contiguous()) else ids.to(torch.int64).contiguous()
+        a.unique_ids, a.max_unique = ids.data_ptr(), ids.size(1)
+        keep.append(ids)
+        if unique_token_counts is not None:
+            cnt = unique_token_counts.reshape(n, -1)
+            if cnt.size(1) != ids.size(1):
+                raise SlmError("unique_token_counts and unique_token_ids differ in shape")
+            cnt = cnt if (cnt.dtype == torch.int32 and cnt.is_contiguous()) else cnt.to(torch.int32).contiguous()
+            a.unique_counts = cnt.data_ptr()
+            keep.append(cnt)
+        a.unique_lens = rows(unique_token_lens, torch.int32, "unique_token_lens")
+    for t, name in ((next_tokens, "next_tokens"), (logprobs, "logprobs")):
+        if t is not None and (not t.is_contiguous() or t.numel() != n):
+            raise SlmError(f"{name} must be contiguous with one entry per row")
+    if next_tokens is not None and next_tokens.dtype != torch.int32:
+        raise SlmError("next_tokens must be int32")
+    a.next_tokens, a.logprobs = _ptr(next_tokens), _ptr(logprobs)
+    if processed is not None:
+        if processed.dtype != logits.dtype or processed.shape != logits.shape or processed.stride(1) != 1:
+            raise SlmError("processed must have the logits' dtype and shape")
+        a.processed, a.processed_stride = processed.data_ptr(), processed.stride(0)
+    if probs is not None:
+        if probs.dtype != torch.float32 or not probs.is_contiguous() or probs.shape != logits.shape:
+            raise SlmError("probs must be contiguous fp32 [n_rows, vocab]")
+        a.probs = probs.data_ptr()
+    if top_logprobs is not None or top_tokens is not None:
+        if top_logprobs is None or top_tokens is None or not top_logprobs.is_contiguous() or \
+                not top_tokens.is_contiguous() or top_tokens.dtype != torch.int32 or \
+                top_logprobs.dtype != torch.float32 or top_logprobs.shape != top_tokens.shape:
+            raise SlmError("top_logprobs (fp32) and top_tokens (int32) must be contiguous [n_rows, n_top]")
+        a.top_logprobs, a.top_tokens, a.n_top = top_logprobs.data_ptr(), top_tokens.data_ptr(), top_tokens.size(-1)
+    L = _lib.lib()
+    need = L.slm_sample_workspace_bytes(C.byref(a))
+    if need:
+        ws = _grow(_sampling_ws, need, logits.device, "sampling workspace")
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(fn(C.byref(a), _stream()), what)
+
+
+def sample(logits: torch.Tensor, next_tokens: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+    """Steps 1-7 of slm_hip.h section 8 in one launch: penalties, temperature, top-k / top-p, greedy or
+    seeded random sampling per row, optional processed logits / probs / logprobs / top logprobs (pass
+    the output tensors).  Returns next_tokens (int32 [n_rows])."""
+    if next_tokens is None:
+        next_tokens = torch.empty(logits.size(0), dtype=torch.int32, device=logits.device)
+    _sampling_call(_lib.lib().slm_sample, "slm_sample", logits, next_tokens=next_tokens, **kw)
+    return next_tokens
+
+
+def logits_process(logits: torch.Tensor, processed: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+    """Steps 1-5 only (penalties, temperature, top-k / top-p) into `processed` (default: in place),
+    rounded once to the logits dtype; filtered tokens are -inf."""
+    processed = logits if processed is None else processed
+    _sampling_call(_lib.lib().slm_logits_process, "slm_logits_process", logits, processed=processed, **kw)
+    return processed
+
+
+def apply_temperature_penalty(logits: torch.Tensor, temperatures: torch.Tensor) -> None:
+    """llm::kernel::apply_temperature_penalty (penalty_kernels.cu:9-55): logits *= 1 / t in place."""
+    logits_process(logits, temperatures=temperatures)
+
+
+def apply_repetition_penalty(logits: torch.Tensor, token_ids: torch.Tensor, token_ids_lens: torch.Tensor,
+                             penalities: torch.Tensor) -> None:
+    """llm::kernel::apply_repetition_penalty (penalty_kernels.cu:57-111), in place."""
+    logits_process(logits, unique_token_ids=token_ids, unique_token_lens=token_ids_lens,
+                   repetition_penalties=penalities)
+
+
+def apply_frequency_presence_penalty(logits: torch.Tensor, token_ids: torch.Tensor, token_counts: torch.Tensor,
+                                     token_ids_lens: torch.Tensor, frequency_penalties: torch.Tensor,
+                                     presence_penalties: torch.Tensor) -> None:
+    """llm::kernel::apply_frequency_presence_penalty (penalty_kernels.cu:113-182), in place."""
+    logits_process(logits, unique_token_ids=token_ids, unique_token_counts=token_counts,
+                   unique_token_lens=token_ids_lens, frequency_penalties=frequency_penalties,
+                   presence_penalties=presence_penalties)
