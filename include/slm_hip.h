@@ -658,6 +658,104 @@ SLM_API int slm_sample(const slm_sampling_args* a, void* stream);
  * kernel::apply_*_penalty, each rounding to the dtype when its call ends as the reference's do. */
 SLM_API int slm_logits_process(const slm_sampling_args* a, void* stream);
 
+/* ========================================================================== */
+/* 9. Rejection sampling: validation of speculative drafts (two launches)     */
+/*    replaces  RejectionSampler::forward / random_sample / greedy_sample     */
+/*              (src/speculative/rejection_sampler.cpp:22-226) as             */
+/*              SpeculativeEngine::validate calls them                        */
+/*              (src/engine/speculative_engine.cpp:187-238).                  */
+/*    Sequence s in [0, n_seqs) brings k draft tokens d_j (j < k) and target  */
+/*    rows j = 0..k (logits form) or j = 0..k-1 (probability form).  All      */
+/*    arithmetic is fp32 without contraction, on the widened target values.   */
+/*    Per row j < k, with l = target[s, j, :]:                                */
+/*     1. logits form: m = max_i l_i, S = sum_i expf(l_i - m) (accumulated    */
+/*        with online rescaling in a fixed order: within a few ulp of the    */
+/*        plain sum), p_i = expf(l_i - m) / S (IEEE division).                */
+/*        probability form: p_i = target[s, j, i].                           */
+/*     2. sampled sequence (do_sample[s] != 0): d = draft_token_ids[s, j],    */
+/*        q_d = draft_probs[s, j, d], ratio = p_d / q_d (IEEE division);      */
+/*        the row is ACCEPTED iff u < ratio -- NaN (0 / 0) rejects, q_d == 0  */
+/*        with p_d > 0 accepts; d outside [0, vocab) rejects (nothing is read */
+/*        at d).  u = uniform[s, j] when `uniform` is given, else             */
+/*        u = ((x >> 8) + 0.5) * 2^-24 with                                   */
+/*        x = philox_word(seed, positions[s] + j, stream 1, word 0).          */
+/*     3. the RECOVERED token of a rejected sampled row:                      */
+/*          argmax_i max(p_i - q_i, 0) / E_i,                                 */
+/*        E_i = -ln(u_i) of x = philox_word(seed, positions[s] + j, stream 2, */
+/*        i), evaluated exactly as section 8's E.  The reference's division   */
+/*        by the clamped sum (rejection_sampler.cpp:162-166) is a common      */
+/*        positive factor and is dropped.  A row of zeros gives token 0 (the  */
+/*        reference's argmax over a zero row).                                */
+/*     greedy sequence: t_j = argmax_i l_i; accepted iff t_j == d; token t_j. */
+/*    Ties: every argmax and the top-n order are stable by index (the lower   */
+/*    id wins; -0 == +0).  Target values are finite or -inf (a token that     */
+/*    slm_logits_process filtered: probability 0).                            */
+/*    Outputs: next_tokens[s, j < k] = d_j if accepted, else the recovered    */
+/*    token (sampled) or t_j (greedy); next_tokens[s, k] = bonus_token_ids[s] */
+/*    (copied as given, never checked against vocab).  Let f be the first     */
+/*    rejected j, or k if none.  mask_out_rejected != 0: every entry after f  */
+/*    is -1 (build_accepted_mask).  accepted_lens[s] = f + 1: the verify-row  */
+/*    inputs of s whose KV entries stay valid (an addition: a captured loop   */
+/*    advances kv_cached by it without reading tokens on the host).           */
+/*    logprobs[s, j] (j = 0..k) = log_softmax(l_j) at the UNMASKED token of   */
+/*    row j, as the reference takes it (a bonus id outside [0, vocab) gives   */
+/*    NaN); top-n values / ids of log_softmax(l_j), descending.  Logits form  */
+/*    only.                                                                   */
+/*    RNG: Philox4x32-10 as section 8 with key seeds[s] and counter           */
+/*    (lo32(i >> 2), hi32(i >> 2), positions[s] + j, stream), word i & 3 --   */
+/*    rocRAND's philox4x32_10_engine(seed, pos | stream << 32, i).  Streams 1 */
+/*    (acceptance) and 2 (race) never meet slm_sample's stream 0.  Outputs of */
+/*    s depend only on its own inputs, seed and position: not on its index    */
+/*    in the batch, the batch, or eager vs graph replay; bit-identical across */
+/*    repeats (no float atomics, fixed reduction order).                      */
+/*    Plan: launch 1, one workgroup per (s, row): rows 0..k-1 (+ row k when   */
+/*    logprobs are wanted) stream once -- max, sum, greedy argmax, the        */
+/*    acceptance decision (and top-n) -- into a 16-byte workspace record.     */
+/*    Launch 2: the race.  Masked without logprobs: one workgroup per         */
+/*    sequence races its first rejected row only; otherwise one per (s, j).   */
+/* ========================================================================== */
+#define SLM_REJECTION_MAX_K 16
+typedef struct slm_rejection_args {
+  int32_t n_seqs;
+  int32_t k;                        /* draft tokens per sequence, 1..SLM_REJECTION_MAX_K         */
+  int32_t vocab;                    /* <= 2^22                                                   */
+  int32_t dtype;                    /* target: SLM_F16, SLM_BF16 or SLM_F32 (probability form:
+                                       SLM_F32)                                                  */
+  int32_t target_is_probs;          /* != 0: target holds fp32 probabilities of rows 0..k-1      */
+  int32_t mask_out_rejected;
+  const int32_t* draft_token_ids;   /* [n_seqs, k], contiguous                                  */
+  const float* draft_probs;         /* [s, j, vocab] fp32 (slm_sample's `probs`); NULL = every
+                                       sequence greedy (do_sample is not read)                   */
+  int64_t draft_seq_stride, draft_row_stride;    /* elements: row stride >= vocab, seq stride >= 0 */
+  const void* target;               /* [s, j, vocab]: logits rows 0..k or probabilities 0..k-1  */
+  int64_t target_seq_stride, target_row_stride;  /* elements: row stride >= vocab, seq stride >= 0
+                                       (inputs are only read: sequences may interleave, e.g. a
+                                       [k + 1, n, vocab] buffer viewed as [n, k + 1, vocab])     */
+  const int32_t* bonus_token_ids;   /* [n_seqs]                                                  */
+  const uint8_t* do_sample;         /* [n_seqs] bool, NULL = all greedy                          */
+  const uint64_t* seeds;            /* [n_seqs], NULL = 0                                        */
+  const int32_t* positions;         /* [n_seqs] position of the input token of row 0, NULL = 0   */
+  const float* uniform;             /* [n_seqs, k] contiguous: replaces the acceptance draw      */
+  /* outputs */
+  int32_t* next_tokens;             /* [n_seqs, k + 1] contiguous (required)                     */
+  int32_t* accepted_lens;           /* [n_seqs]                                                  */
+  float* logprobs;                  /* [n_seqs, k + 1]                                           */
+  float* top_logprobs;              /* [n_seqs, k + 1, n_top]                                    */
+  int32_t* top_tokens;              /* [n_seqs, k + 1, n_top]                                    */
+  int32_t n_top;                    /* 0 .. min(SLM_SAMPLE_MAX_TOP, vocab)                       */
+  int32_t reserved;
+  void* workspace;                  /* slm_rejection_sample_workspace_bytes                      */
+  size_t workspace_bytes;
+} slm_rejection_args;
+
+/* scratch the call needs; a pure function of host-side sizes (n_seqs, k) */
+SLM_API size_t slm_rejection_sample_workspace_bytes(const slm_rejection_args* a);
+/* SLM_ERR_INVALID_ARG: NULL draft_token_ids / target / bonus_token_ids / next_tokens, k outside
+ * 1..16, n_top outside 0..20 or > vocab, top-n without both outputs, logprobs with target_is_probs,
+ * a row stride < vocab or a negative sequence stride (target, or draft when given); SLM_ERR_UNSUPPORTED: dtype (or a non-fp32 probability target), vocab
+ * > 2^22; SLM_ERR_WORKSPACE: missing or too small; n_seqs == 0 is a no-op. */
+SLM_API int slm_rejection_sample(const slm_rejection_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

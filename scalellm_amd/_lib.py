@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libslm_hip.so")
 SLM_F16, SLM_BF16 = 0, 1
 SLM_F32 = 2  # logits of the sampling entry points (slm_hip.h section 8) only
 SLM_SAMPLE_MAX_TOP = 20
+SLM_REJECTION_MAX_K = 16
 SLM_W4_GPTQ, SLM_W4_AWQ = 0, 1
 SLM_W8_GPTQ, SLM_W8_AWQ = 2, 3  # 8-bit checkpoints: slm_w8_prepack_* (two int4 planes)
 SLM_W4_PAIRED = 0x10
@@ -103,6 +104,22 @@ class SamplingArgs(C.Structure):
         ("next_tokens", C.c_void_p), ("processed", C.c_void_p), ("processed_stride", C.c_int64),
         ("probs", C.c_void_p), ("logprobs", C.c_void_p), ("top_logprobs", C.c_void_p),
         ("top_tokens", C.c_void_p), ("n_top", C.c_int32), ("reserved", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class RejectionArgs(C.Structure):
+    """struct slm_rejection_args (include/slm_hip.h section 9)."""
+    _fields_ = [
+        ("n_seqs", C.c_int32), ("k", C.c_int32), ("vocab", C.c_int32), ("dtype", C.c_int32),
+        ("target_is_probs", C.c_int32), ("mask_out_rejected", C.c_int32),
+        ("draft_token_ids", C.c_void_p), ("draft_probs", C.c_void_p),
+        ("draft_seq_stride", C.c_int64), ("draft_row_stride", C.c_int64),
+        ("target", C.c_void_p), ("target_seq_stride", C.c_int64), ("target_row_stride", C.c_int64),
+        ("bonus_token_ids", C.c_void_p), ("do_sample", C.c_void_p), ("seeds", C.c_void_p),
+        ("positions", C.c_void_p), ("uniform", C.c_void_p),
+        ("next_tokens", C.c_void_p), ("accepted_lens", C.c_void_p), ("logprobs", C.c_void_p),
+        ("top_logprobs", C.c_void_p), ("top_tokens", C.c_void_p), ("n_top", C.c_int32), ("reserved", C.c_int32),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
     ]
 
@@ -214,6 +231,8 @@ def lib() -> C.CDLL:
         ("slm_sample_workspace_bytes", C.c_size_t, [C.POINTER(SamplingArgs)]),
         ("slm_sample", C.c_int, [C.POINTER(SamplingArgs), C.c_void_p]),
         ("slm_logits_process", C.c_int, [C.POINTER(SamplingArgs), C.c_void_p]),
+        ("slm_rejection_sample_workspace_bytes", C.c_size_t, [C.POINTER(RejectionArgs)]),
+        ("slm_rejection_sample", C.c_int, [C.POINTER(RejectionArgs), C.c_void_p]),
     ]:
         fn = getattr(L, name)  # AttributeError here = library/header mismatch: fail loudly
         fn.restype = restype

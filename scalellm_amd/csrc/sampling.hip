@@ -30,6 +30,8 @@
 
 #pragma clang fp contract(off)
 
+#include "philox.h"  // philox_word, exp_draw (shared with rejection.hip)
+
 namespace slm {
 namespace {
 
@@ -72,30 +74,6 @@ __device__ __forceinline__ void st(void* row, int i, float x) {
 }
 template <int DT>
 constexpr int elem_bytes() { return DT == SLM_F32 ? 4 : 2; }
-
-// ---- Philox4x32-10 (Salmon et al., SC'11; the constants of Random123, rocRAND and torch) -------
-// key (seed lo, seed hi); counter (lo32(i >> 2), hi32(i >> 2), pos, stream); word i & 3
-__device__ __forceinline__ uint32_t philox_word(u64 seed, uint32_t pos, uint32_t stream, uint32_t i) {
-  uint32_t c0 = i >> 2, c1 = 0u, c2 = pos, c3 = stream;  // i < 2^22: hi32(i >> 2) = 0
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int rnd = 0; rnd < 10; ++rnd) {
-    const u64 p0 = (u64)0xD2511F53u * c0, p1 = (u64)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  const uint32_t w = i & 3u;
-  return w == 0 ? c0 : w == 1 ? c1 : w == 2 ? c2 : c3;
-}
-// E = -ln(u), u = ((x >> 8) + 0.5) 2^-24 in (0, 1): from u itself below 1/2, from 1 - u above
-// (both exact in fp32, so E never rounds to 0 and keeps its precision next to u = 1)
-__device__ __forceinline__ float exp_draw(uint32_t x) {
-  const uint32_t m = x >> 8;
-  if (m < (1u << 23)) return -logf(((float)m + 0.5f) * 0x1p-24f);
-  return -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
-}
 
 struct Smem {
   u64 hist[256];

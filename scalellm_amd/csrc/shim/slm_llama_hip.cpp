@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "slm_hip.h"
+#include "slm_rejection_sampler_hip.h"
 
 namespace slm {
 namespace {
@@ -580,6 +581,51 @@ SampleOutput LlamaForCausalLMHip::sample_step(const torch::Tensor& tokens, const
     out.top_tokens = sample_top_tok_.narrow(0, 0, n * k).view({n, k});
   }
   return sample(lg, sampling.narrow(n), positions.index_select(0, last), &out);
+}
+
+SampleOutput LlamaForCausalLMHip::verify_step(const torch::Tensor& tokens, const torch::Tensor& positions,
+                                              std::vector<KVCache>& kv_caches, const InputParameters& input_params,
+                                              const torch::Tensor& draft_token_ids, const torch::Tensor& draft_probs,
+                                              const SamplingParameters& sampling, bool mask_out_rejected_tokens) {
+  TORCH_CHECK(draft_token_ids.dim() == 2, "verify_step: draft_token_ids must be [n_seqs, k]");
+  const int64_t n = draft_token_ids.size(0), k = draft_token_ids.size(1), T = tokens.numel();
+  TORCH_CHECK(T == n * (k + 1), "verify_step: ", T, " rows for ", n, " sequences of k + 1 = ", k + 1);
+  const auto h = forward(tokens, positions, kv_caches, input_params);
+  auto lg = logits(h, torch::Tensor());  // every row is selected
+  const auto sp = sampling.narrow(T);
+  LogitsProcessor(sp).forward(lg, sp.unique_token_ids, sp.unique_token_counts, sp.unique_token_ids_lens);
+  verify_logits_ = lg;
+  const int64_t V = lg.size(1);
+  const auto rows = lg.view({n, k + 1, V});
+  const auto pos = positions.view({n, k + 1});
+  SamplingParameters last;  // the bonus row of each sequence: its do_sample and seed
+  if (sp.do_sample.defined()) last.do_sample = sp.do_sample.slice(0, k, T, k + 1);
+  if (sp.seeds.defined()) last.seeds = sp.seeds.slice(0, k, T, k + 1);
+  if (!verify_tok_.defined()) {  // static outputs at the maximum batch (a captured step keeps their addresses)
+    const int64_t Tm = opt_.max_tokens, K = SLM_SAMPLE_MAX_TOP;
+    const auto i = lg.options().dtype(torch::kInt), f = lg.options().dtype(torch::kFloat);
+    verify_tok_ = torch::empty({Tm}, i);
+    verify_bonus_ = torch::empty({Tm}, i);
+    verify_acc_ = torch::empty({Tm}, i);
+    verify_lp_ = torch::empty({Tm}, f);
+    verify_top_lp_ = torch::empty({Tm * K}, f);
+    verify_top_tok_ = torch::empty({Tm * K}, i);
+  }
+  SampleOutput bonus;
+  bonus.next_tokens = verify_bonus_.narrow(0, 0, n);
+  sample(rows.select(1, k), last, pos.select(1, k), &bonus);
+  const int64_t nt = sampling.logprobs ? sampling.max_top_logprobs : 0;
+  SampleOutput out;
+  out.next_tokens = verify_tok_.narrow(0, 0, T).view({n, k + 1});
+  out.accepted_lens = verify_acc_.narrow(0, 0, n);
+  if (sampling.logprobs) out.logprobs = verify_lp_.narrow(0, 0, T).view({n, k + 1});
+  if (nt > 0) {
+    out.top_logprobs = verify_top_lp_.narrow(0, 0, T * nt).view({n, k + 1, nt});
+    out.top_tokens = verify_top_tok_.narrow(0, 0, T * nt).view({n, k + 1, nt});
+  }
+  return rejection_sample(draft_token_ids, draft_probs, rows, bonus.next_tokens, /*target_is_probs=*/false,
+                          mask_out_rejected_tokens, last.do_sample, last.seeds, pos.select(1, 0), torch::Tensor(),
+                          sampling.logprobs, nt, &out);
 }
 
 }  // namespace slm

@@ -101,6 +101,19 @@ class LlamaForCausalLMHip {
   SampleOutput sample_step(const torch::Tensor& tokens, const torch::Tensor& positions,
                            std::vector<KVCache>& kv_caches, const InputParameters& input_params,
                            const SamplingParameters& sampling);
+  // the verify step of speculative decoding: every sequence brings k + 1 rows (last accepted token, k drafts).
+  // forward -> logits of all rows -> slm_logits_process in place (`sampling`: >= n_seqs * (k + 1) rows, one per
+  // row) -> the bonus token sampled from each sequence's last processed row (strided, no gather) -> the
+  // rejection kernel on the processed buffer.  A sequence's do_sample / seed: those of its last row; the
+  // rejection draws use the position of its row-0 input token.  Outputs (next_tokens [n, k + 1], accepted_lens
+  // [n], logprobs) view static buffers (capturable).  draft_probs undefined: every sequence greedy.
+  // Mirror: decode.LlamaDecodeStep.verify
+  SampleOutput verify_step(const torch::Tensor& tokens, const torch::Tensor& positions,
+                           std::vector<KVCache>& kv_caches, const InputParameters& input_params,
+                           const torch::Tensor& draft_token_ids, const torch::Tensor& draft_probs,
+                           const SamplingParameters& sampling, bool mask_out_rejected_tokens = true);
+  // the processed logits [n_seqs * (k + 1), vocab] of the last verify_step
+  const torch::Tensor& last_verify_logits() const { return verify_logits_; }
   int last_lanes() const { return last_lanes_; }
   HipAttnHandler& handler() { return *handler_; }
   int64_t n_local_heads() const { return n_heads_; }
@@ -150,6 +163,8 @@ class LlamaForCausalLMHip {
   std::unique_ptr<AttentionImpl> atten_;
   std::vector<Layer> layers_;
   torch::Tensor sample_tok_, sample_lp_, sample_top_lp_, sample_top_tok_;  // sample_step's outputs
+  torch::Tensor verify_tok_, verify_bonus_, verify_acc_, verify_lp_, verify_top_lp_, verify_top_tok_;  // verify_step's
+  torch::Tensor verify_logits_;
   torch::Tensor embed_, final_norm_, lm_head_;  // embed [vocab, hidden / tp], lm_head [hidden, vocab / tp]
   bool embed_loaded_ = false, norm_loaded_ = false, lm_head_loaded_ = false;
   // static activation buffers [max_tokens, ...]

@@ -51,9 +51,11 @@ struct SamplingParameters {
   SamplingParameters narrow(int64_t n) const;  // rows [0, n) as views
 };
 
-// parameters.h:121-135 (next_tokens int32)
+// parameters.h:121-135 (next_tokens int32).  accepted_lens: the rejection sampler's addition (first rejected
+// row + 1 per sequence; undefined elsewhere).
 struct SampleOutput {
   torch::Tensor next_tokens, probs, logprobs, top_logprobs, top_tokens;
+  torch::Tensor accepted_lens;
 };
 
 // LogitsProcessor + Sampler in one launch.  positions[r]: position of row r's last input token (the RNG

@@ -10,6 +10,7 @@
 #include "slm_attn_handler_hip.h"
 #include "slm_llama_hip.h"
 #include "slm_qlinear_hip.h"
+#include "slm_rejection_sampler_hip.h"
 #include "slm_sampling_hip.h"
 #include "slm_torch_shim.h"
 
@@ -154,7 +155,8 @@ PYBIND11_MODULE(_slm_shim, m) {
       .def_readonly("probs", &slm::SampleOutput::probs)
       .def_readonly("logprobs", &slm::SampleOutput::logprobs)
       .def_readonly("top_logprobs", &slm::SampleOutput::top_logprobs)
-      .def_readonly("top_tokens", &slm::SampleOutput::top_tokens);
+      .def_readonly("top_tokens", &slm::SampleOutput::top_tokens)
+      .def_readonly("accepted_lens", &slm::SampleOutput::accepted_lens);
   m.def("sample", [](const torch::Tensor& logits, const slm::SamplingParameters& p, const torch::Tensor& positions,
                      bool want_probs) { return slm::sample(logits, p, positions, nullptr, want_probs); },
         py::arg("logits"), py::arg("params"), py::arg("positions"), py::arg("want_probs") = false);
@@ -166,6 +168,20 @@ PYBIND11_MODULE(_slm_shim, m) {
                               int64_t max_top_logprobs, const torch::Tensor& seeds, const torch::Tensor& positions) {
           return slm::Sampler(do_sample, logprobs, max_top_logprobs, seeds, positions).forward(logits);
         });
+  // rejection sampling (slm_rejection_sampler_hip.h): the reference's RejectionSampler
+  m.def("rejection_sampler_forward",
+        [](const torch::Tensor& do_sample, bool logprobs, int64_t max_top_logprobs, const torch::Tensor& seeds,
+           const torch::Tensor& positions, const torch::Tensor& draft_token_ids, const torch::Tensor& draft_probs,
+           const torch::Tensor& target_logits, const torch::Tensor& bonus_token_ids, bool mask_out_rejected_tokens) {
+          return slm::RejectionSampler(do_sample, logprobs, max_top_logprobs, seeds, positions)
+              .forward(draft_token_ids, draft_probs, target_logits, bonus_token_ids, mask_out_rejected_tokens);
+        });
+  m.def("rejection_random_sample", &slm::RejectionSampler::random_sample, py::arg("draft_token_ids"),
+        py::arg("draft_probs"), py::arg("target_probs"), py::arg("uniform_rand"), py::arg("bonus_token_ids"),
+        py::arg("mask_out_rejected_tokens"), py::arg("seeds") = torch::Tensor(), py::arg("positions") = torch::Tensor());
+  m.def("rejection_greedy_sample", &slm::RejectionSampler::greedy_sample, py::arg("draft_token_ids"),
+        py::arg("target_probs"), py::arg("bonus_token_ids"), py::arg("mask_out_rejected_tokens"));
+  m.def("build_accepted_mask", &slm::RejectionSampler::build_accepted_mask, py::arg("accepted"));
   py::class_<slm::InputParameters>(m, "InputParameters")
       .def(py::init<>())
       .def_readwrite("num_sequences", &slm::InputParameters::num_sequences)
@@ -279,6 +295,18 @@ PYBIND11_MODULE(_slm_shim, m) {
              return self.model->sample_step(tokens, positions, self.kv, params, sampling);
            },
            py::arg("tokens"), py::arg("positions"), py::arg("params"), py::arg("sampling"))
+      .def("verify_step",
+           [](PyLlama& self, const torch::Tensor& tokens, const torch::Tensor& positions,
+              const slm::InputParameters& params, const torch::Tensor& draft_token_ids,
+              const std::optional<torch::Tensor>& draft_probs, const slm::SamplingParameters& sampling,
+              bool mask_out_rejected_tokens) {
+             return self.model->verify_step(tokens, positions, self.kv, params, draft_token_ids,
+                                            draft_probs ? *draft_probs : torch::Tensor(), sampling,
+                                            mask_out_rejected_tokens);
+           },
+           py::arg("tokens"), py::arg("positions"), py::arg("params"), py::arg("draft_token_ids"),
+           py::arg("draft_probs"), py::arg("sampling"), py::arg("mask_out_rejected_tokens") = true)
+      .def("last_verify_logits", [](PyLlama& self) { return self.model->last_verify_logits(); })
       .def("forward",
            [](PyLlama& self, const torch::Tensor& tokens, const torch::Tensor& positions,
               const slm::InputParameters& params) { return self.model->forward(tokens, positions, self.kv, params); })

@@ -665,13 +665,9 @@ class LlamaDecodeStep:
             if ln.pend is not None:  # the final norm has no projection of ours behind it
                 self._run_norm(ln, ln.pend)
 
-    def forward(self, tokens: torch.Tensor, positions: torch.Tensor, params: InputParameters,
-                return_logits: bool = False, sampling=None):
-        """tokens/positions [T] int32 -> next-token ids [n_seqs] (greedy), last token per sequence.
-        sampling (sampling.SamplingParameters, >= n_seqs rows): the logits go through the fused
-        processing + sampling kernel instead, and the result is a sampling.SampleOutput whose tensors are
-        views of static buffers (capturable).  The RNG position of a sequence is the position of its
-        last input token."""
+    def _trunk(self, tokens: torch.Tensor, positions: torch.Tensor, params: InputParameters):
+        """Embedding and the decoder stack: the final-norm output of all T rows ([T, hidden], a view of the
+        static buffer) and the fused all-reduce of a tensor-parallel step (else None)."""
         s, b, pa = self.shape, self.buf, self.pa
         T = tokens.numel()
         if getattr(params, "kv_total_len", 0) == 0 and not torch.cuda.is_current_stream_capturing():
@@ -704,6 +700,17 @@ class LlamaDecodeStep:
             o_buf, down_buf = b["o"][:T], b["down"][:T]
 
         self._run_layers(T, positions, params, o_buf, down_buf, ar)
+        return normed, ar
+
+    def forward(self, tokens: torch.Tensor, positions: torch.Tensor, params: InputParameters,
+                return_logits: bool = False, sampling=None):
+        """tokens/positions [T] int32 -> next-token ids [n_seqs] (greedy), last token per sequence.
+        sampling (sampling.SamplingParameters, >= n_seqs rows): the logits go through the fused
+        processing + sampling kernel instead, and the result is a sampling.SampleOutput whose tensors are
+        views of static buffers (capturable).  The RNG position of a sequence is the position of its
+        last input token."""
+        s, pa = self.shape, self.pa
+        normed, ar = self._trunk(tokens, positions, params)
         last = (params.q_cu_seq_lens[1:] - 1).long()
         self.last_hidden = normed[last]  # final-norm output of each sequence's last token (tests)
         logits = self.last_hidden @ self.lm_head  # plain library GEMM (hipBLASLt): not on the graded path
@@ -745,6 +752,57 @@ class LlamaDecodeStep:
                            b["top_lp"][:n * k].view(n, k) if sampling.logprobs and k else None,
                            b["top_tok"][:n * k].view(n, k) if sampling.logprobs and k else None)
         return sample_logits(logits, sampling.narrow(n), last_positions, out=out)
+
+    def verify(self, tokens: torch.Tensor, positions: torch.Tensor, params: InputParameters,
+               draft_token_ids: torch.Tensor, draft_probs: Optional[torch.Tensor], sampling,
+               mask_out_rejected_tokens: bool = True):
+        """The verify step of speculative decoding: every sequence s brings k + 1 rows (its last accepted
+        token, then its k drafts draft_token_ids[s]), the reference's speculative graph.  The logits of all
+        rows are processed in place by slm_logits_process with one parameter row per row (`sampling` has
+        >= n_seqs * (k + 1) rows, per-row penalty counts, as the reference's Batch builds them); the bonus
+        token is sampled from each sequence's last processed row (strided, no gather) and the rejection
+        kernel validates the drafts on the processed buffer.  A sequence's do_sample and seed are those of
+        its last row; the rejection draws use the position of its row-0 input token.  Returns a
+        speculative.RejectionOutput (next_tokens [n, k + 1], accepted_lens [n], logprobs) whose tensors view
+        static buffers sized at max_batch_tokens (capturable).  self.verify_logits: the processed rows."""
+        from .speculative import RejectionOutput
+        from ._lib import SLM_SAMPLE_MAX_TOP
+        n, k = draft_token_ids.shape
+        T = tokens.numel()
+        if T != n * (k + 1):
+            raise ValueError(f"verify(): {T} rows for {n} sequences of k + 1 = {k + 1}")
+        normed, _ = self._trunk(tokens, positions, params)
+        self.last_hidden = normed  # every row is selected
+        logits = normed @ self.lm_head  # plain library GEMM (hipBLASLt), as forward()
+        if self.pa.world_size > 1:
+            from .model_parallel import gather_from_model_parallel_region
+            logits = gather_from_model_parallel_region(logits, self.pa)
+        sp = sampling.narrow(T)
+        kernels.logits_process(logits, unique_token_ids=sp.unique_token_ids, unique_token_counts=sp.unique_token_counts,
+                               unique_token_lens=sp.unique_token_ids_lens, **sp.processing_kwargs())
+        self.verify_logits = logits
+        rows = logits.view(n, k + 1, logits.size(1))
+        pos = positions.view(n, k + 1)
+        do_sample = sp.do_sample[k::k + 1] if sp.do_sample is not None else None
+        seeds = sp.seeds[k::k + 1] if sp.seeds is not None else None
+        Tm = self.buf["resid"].size(0)
+        if getattr(self, "_verify_bufs", None) is None:
+            e = lambda *sz, dt=torch.float32: torch.empty(*sz, dtype=dt, device=self.device)  # noqa: E731
+            self._verify_bufs = dict(tok=e(Tm, dt=torch.int32), bonus=e(Tm, dt=torch.int32), acc=e(Tm, dt=torch.int32),
+                                     lp=e(Tm), top_lp=e(Tm * SLM_SAMPLE_MAX_TOP),
+                                     top_tok=e(Tm * SLM_SAMPLE_MAX_TOP, dt=torch.int32))
+        b, nt = self._verify_bufs, sampling.max_top_logprobs if sampling.logprobs else 0
+        bonus = kernels.sample(rows[:, k], next_tokens=b["bonus"][:n], do_sample=do_sample, seeds=seeds,
+                               positions=pos[:, k])
+        out = RejectionOutput(b["tok"][:T].view(n, k + 1), accepted_lens=b["acc"][:n],
+                              logprobs=b["lp"][:T].view(n, k + 1) if sampling.logprobs else None,
+                              top_logprobs=b["top_lp"][:T * nt].view(n, k + 1, nt) if nt else None,
+                              top_tokens=b["top_tok"][:T * nt].view(n, k + 1, nt) if nt else None)
+        kernels.rejection_sample(draft_token_ids, draft_probs, rows, bonus, mask_out_rejected=mask_out_rejected_tokens,
+                                 do_sample=do_sample, seeds=seeds, positions=pos[:, 0], next_tokens=out.next_tokens,
+                                 accepted_lens=out.accepted_lens, logprobs=out.logprobs,
+                                 top_logprobs=out.top_logprobs, top_tokens=out.top_tokens)
+        return out
 
     def _greedy_over_vocab_shards(self, logits: torch.Tensor, ar) -> torch.Tensor:
         """argmax over the vocab-sharded logits without gathering them (and without RCCL): every

@@ -95,6 +95,7 @@ _deferred_ws_b = {}  # slot 1: where a GEMM that CONSUMES slot-0 slabs (norm pro
 _retired = []  # buffers replaced by bigger ones: still referenced by graphs captured before
 _deferred_gen = {}  # (device, slot) -> generation counter of that deferred-partials buffer
 _sampling_ws = {}   # penalised values of sample / logits_process (slm_sample_workspace_bytes)
+_rejection_ws = {}  # per-row records of rejection_sample (slm_rejection_sample_workspace_bytes)
 
 
 # scratch lane of the calling code path (workspace_lane): 0 unless a step runs two streams.  Per THREAD:
@@ -141,7 +142,7 @@ def _grow(table, nbytes: int, dev: torch.device, what: str) -> torch.Tensor:
     ws = table.get(key)
     if ws is None or ws.numel() < nbytes:
         if torch.cuda.is_current_stream_capturing():
-            kw = "sampling_nbytes" if table is _sampling_ws else \
+            kw = "sampling_nbytes" if table is _sampling_ws else "rejection_nbytes" if table is _rejection_ws else \
                 "deferred_nbytes" if table is _deferred_ws or table is _deferred_ws_b else "nbytes"
             raise SlmError(f"{what} must be reserved before graph capture "
                            f"(need {nbytes} bytes): call reserve_workspace({kw}=...) first")
@@ -154,15 +155,19 @@ def _grow(table, nbytes: int, dev: torch.device, what: str) -> torch.Tensor:
 
 
 def reserve_workspace(nbytes: int, device: Optional[torch.device] = None,
-                      deferred_nbytes: int = 0, sampling_nbytes: int = 0) -> torch.Tensor:
+                      deferred_nbytes: int = 0, sampling_nbytes: int = 0,
+                      rejection_nbytes: int = 0) -> torch.Tensor:
     """Size the per-device scratch once, before graph capture.  deferred_nbytes sizes BOTH deferred
     split-K slab buffers (slot 0 and slot 1: a GEMM whose norm prologue consumes slot-0 slabs leaves
     its own in slot 1), so a capture needs no warm-up of exactly that path and nothing is retired
     later.  sampling_nbytes sizes the penalised-value scratch of sample / logits_process
-    (slm_sample_workspace_bytes: n_rows * max_unique * 4 bytes)."""
+    (slm_sample_workspace_bytes: n_rows * max_unique * 4 bytes).  rejection_nbytes sizes the records of
+    rejection_sample (slm_rejection_sample_workspace_bytes: n_seqs * (k + 1) * 16 bytes)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     if sampling_nbytes:
         _grow(_sampling_ws, sampling_nbytes, dev, "sampling workspace")
+    if rejection_nbytes:
+        _grow(_rejection_ws, rejection_nbytes, dev, "rejection workspace")
     if deferred_nbytes:
         _grow(_deferred_ws, deferred_nbytes, dev, "deferred split-K buffer")
         _grow(_deferred_ws_b, deferred_nbytes, dev, "deferred split-K buffer (slot 1)")
@@ -1070,3 +1075,93 @@ def apply_frequency_presence_penalty(logits: torch.Tensor, token_ids: torch.Tens
     logits_process(logits, unique_token_ids=token_ids, unique_token_counts=token_counts,
                    unique_token_lens=token_ids_lens, frequency_penalties=frequency_penalties,
                    presence_penalties=presence_penalties)
+
+
+# ---------------------------------------------------------------------------------------
+#   rejection_sample
+#       <- RejectionSampler::forward / random_sample / greedy_sample,
+#          src/speculative/rejection_sampler.cpp:22-226 (two launches, no host sync)
+# ---------------------------------------------------------------------------------------
+def _rows3(t: torch.Tensor, n: int, rows: int, V: int, what: str):
+    """A [n, >= rows, V] tensor with contiguous vocab: its sequence and row strides (elements)."""
+    if t.dim() != 3 or t.size(0) != n or t.size(1) < rows or t.size(2) != V or t.stride(2) != 1:
+        raise SlmError(f"{what} must be [n_seqs, {rows}, vocab] with contiguous rows, got {tuple(t.shape)}")
+    return t.stride(0), t.stride(1)
+
+
+def rejection_sample_workspace_bytes(n_seqs: int, k: int) -> int:
+    a = _lib.RejectionArgs()
+    a.n_seqs, a.k = n_seqs, k
+    return int(_lib.lib().slm_rejection_sample_workspace_bytes(C.byref(a)))
+
+
+def rejection_sample(draft_token_ids: torch.Tensor, draft_probs: Optional[torch.Tensor], target: torch.Tensor,
+                     bonus_token_ids: torch.Tensor, *, target_is_probs: bool = False, mask_out_rejected: bool = False,
+                     do_sample=None, seeds=None, positions=None, uniform=None, next_tokens=None,
+                     accepted_lens=None, logprobs=None, top_logprobs=None, top_tokens=None) -> torch.Tensor:
+    """slm_hip.h section 9 in two launches: validates k draft tokens per sequence against the target rows.
+    draft_token_ids [n, k]; draft_probs [n, k, V] fp32 (slm_sample's probs; None = every sequence greedy);
+    target [n, k + 1, V] logits (f16 / bf16 / fp32) or, with target_is_probs, [n, k, V] fp32 probabilities;
+    bonus_token_ids [n].  Strided draft / target rows are read in place.  Returns next_tokens
+    (int32 [n, k + 1]); pass accepted_lens ([n] int32), logprobs ([n, k + 1]) and top_logprobs /
+    top_tokens ([n, k + 1, n_top]) to have them written."""
+    _require_gpu(draft_token_ids, draft_probs, target, bonus_token_ids)
+    if draft_token_ids.dim() != 2:
+        raise SlmError("draft_token_ids must be [n_seqs, k]")
+    n, k = draft_token_ids.shape
+    if target.dim() != 3:
+        raise SlmError("target must be [n_seqs, rows, vocab]")
+    V = target.size(2)
+    a = _lib.RejectionArgs()
+    a.n_seqs, a.k, a.vocab = n, k, V
+    a.target_is_probs, a.mask_out_rejected = int(bool(target_is_probs)), int(bool(mask_out_rejected))
+    if target_is_probs and target.dtype != torch.float32:
+        raise SlmError("a probability target must be fp32")
+    a.dtype = _logits_dtype_code(target)
+    a.target = target.data_ptr()
+    a.target_seq_stride, a.target_row_stride = _rows3(target, n, k if target_is_probs else k + 1, V, "target")
+    keep = []
+
+    def rows(t, dtype, name, count=n):
+        if t is None:
+            return None
+        _require_gpu(t)
+        t = t.reshape(-1)
+        if t.numel() != count:
+            raise SlmError(f"{name}: {t.numel()} values, expected {count}")
+        t = t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
+        keep.append(t)
+        return t.data_ptr()
+    a.draft_token_ids = rows(draft_token_ids, torch.int32, "draft_token_ids", n * k)
+    a.bonus_token_ids = rows(bonus_token_ids, torch.int32, "bonus_token_ids")
+    if draft_probs is not None:
+        if draft_probs.dtype != torch.float32:
+            raise SlmError("draft_probs must be fp32")
+        a.draft_probs = draft_probs.data_ptr()
+        a.draft_seq_stride, a.draft_row_stride = _rows3(draft_probs, n, k, V, "draft_probs")
+    a.do_sample = rows(do_sample, torch.bool, "do_sample")
+    a.seeds = rows(seeds, torch.int64, "seeds")  # uint64 seeds travel as their int64 bit pattern
+    a.positions = rows(positions, torch.int32, "positions")
+    a.uniform = rows(uniform, torch.float32, "uniform", n * k)
+    if next_tokens is None:
+        next_tokens = torch.empty(n, k + 1, dtype=torch.int32, device=target.device)
+    for t, name, cnt, dt in ((next_tokens, "next_tokens", n * (k + 1), torch.int32),
+                             (accepted_lens, "accepted_lens", n, torch.int32),
+                             (logprobs, "logprobs", n * (k + 1), torch.float32)):
+        if t is not None and (not t.is_contiguous() or t.numel() != cnt or t.dtype != dt):
+            raise SlmError(f"{name} must be contiguous {dt} with {cnt} entries")
+    a.next_tokens, a.accepted_lens, a.logprobs = _ptr(next_tokens), _ptr(accepted_lens), _ptr(logprobs)
+    if top_logprobs is not None or top_tokens is not None:
+        if top_logprobs is None or top_tokens is None or not top_logprobs.is_contiguous() or \
+                not top_tokens.is_contiguous() or top_tokens.dtype != torch.int32 or \
+                top_logprobs.dtype != torch.float32 or top_logprobs.shape != top_tokens.shape or \
+                top_tokens.numel() != n * (k + 1) * top_tokens.size(-1):
+            raise SlmError("top_logprobs (fp32) and top_tokens (int32) must be contiguous [n_seqs, k + 1, n_top]")
+        a.top_logprobs, a.top_tokens, a.n_top = top_logprobs.data_ptr(), top_tokens.data_ptr(), top_tokens.size(-1)
+    L = _lib.lib()
+    need = L.slm_rejection_sample_workspace_bytes(C.byref(a))
+    if need:
+        ws = _grow(_rejection_ws, need, target.device, "rejection workspace")
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(L.slm_rejection_sample(C.byref(a), _stream()), "slm_rejection_sample")
+    return next_tokens
