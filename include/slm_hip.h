@@ -756,6 +756,139 @@ SLM_API size_t slm_rejection_sample_workspace_bytes(const slm_rejection_args* a)
  * > 2^22; SLM_ERR_WORKSPACE: missing or too small; n_seqs == 0 is a no-op. */
 SLM_API int slm_rejection_sample(const slm_rejection_args* a, void* stream);
 
+/* ========================================================================== */
+/* 10. Mixture of experts: routing, block alignment, grouped int4 GEMM        */
+/*    replaces  llm::kernel::topk_softmax                                     */
+/*              src/kernels/moe/topk_softmax_kernel.cu:272-293,               */
+/*              llm::kernel::grouped_topk_sigmoid                             */
+/*              src/kernels/moe/grouped_topk_sigmoid_kernel.cu:280-315,       */
+/*              llm::kernel::moe::permute_align_block / sum_out               */
+/*              src/kernels/moe/align_block_kernel.cu:192-240, 242-272,       */
+/*              and the grouped GEMM Sm80KernelGroupedGemm                    */
+/*              src/kernels/gemm/ (A[m,k], W[e,n,k], rows gathered through    */
+/*              sorted_token_idxes / expert_ids, output [m*topk, n]) -- here  */
+/*              over int4 experts in the packed layout of section 3.          */
+/*    One launch per entry point, on the given stream, no host sync, no       */
+/*    allocation: every call is capture-safe.  No float atomics and a fixed   */
+/*    order everywhere: repeated runs are bit-identical.  T = n_tokens,       */
+/*    E = n_experts, k = topk, n_flat = T * k; a FLAT INDEX is t * k + j.     */
+/*                                                                            */
+/*  Routing.  logits [T, E] fp32 contiguous -> weights [T, k] fp32, indices   */
+/*  [T, k] int32.  E a power of two <= 256 (the reference's limit,            */
+/*  topk_softmax_kernel.cu:223-266), 1 <= k <= E; finite logits assumed.      */
+/*  Every ordering is stable by index: among equal values the lower expert id */
+/*  ranks first (-0 == +0).  Output j = 0..k-1 is in descending order.        */
+/*   slm_moe_topk_softmax: the k largest LOGITS are selected (no arithmetic   */
+/*    in the selection: the reference's softmax-then-top-k in exact           */
+/*    arithmetic); weights = softmax over all E experts at the selected ones, */
+/*    p = expf(x - max) / sum.  renormalize != 0: divided by the sum of the k */
+/*    weights (added in order j = 0..k-1) -- Mixtral's rule; 0 = reference.   */
+/*   slm_moe_grouped_topk_sigmoid (grouped_topk_sigmoid_ref,                  */
+/*    grouped_topk_sigmoid_kernel_test.cu:25-75): s = 1 / (1 + expf(-x)),     */
+/*    c = s + correction_bias; experts form n_expert_groups consecutive       */
+/*    groups of E / n_expert_groups >= 2; group score = the sum of the two    */
+/*    largest c of the group; the topk_group best groups are kept; top-k of c */
+/*    inside the kept groups (k <= topk_group * group size);                  */
+/*    weights = s[idx] * scaling_factor (the UNBIASED score).                 */
+/*                                                                            */
+/*  Alignment.  topk_ids [T, k] int32 -> sorted_token_idxes: experts in       */
+/*  ascending order, each expert's flat indices in ASCENDING order (stricter  */
+/*  than the reference, whose large path leaves the order to atomics), padded */
+/*  to a multiple of block_size with the padding id n_flat; expert_ids: one   */
+/*  entry per block of block_size entries; empty experts get no block;        */
+/*  n_padded_tokens[0] = entries in use.  The kernel writes every entry of    */
+/*  [0, n_padded) itself, padding included (no pre-fill needed); entries past */
+/*  n_padded are unspecified but never written past the capacities below.     */
+/*  Ids outside [0, E) are dropped.  E <= 1024; block_size in                 */
+/*  {16, 32, 64, 128, 256}.  cu_sum (optional, [E + 1] int32): the padded     */
+/*  start offset of every expert, as the reference's workspace holds it.      */
+/*  Capacity (slm_moe_align_capacity): at most m = min(E, n_flat) experts are */
+/*  non-empty and each adds at most block_size - 1 padding entries, so        */
+/*    max_padded = floor((n_flat + m * (block_size - 1)) / block_size)        */
+/*                 * block_size,   max_blocks = max_padded / block_size       */
+/*  -- tighter than the reference test's n_flat + E * (block_size - 1) when   */
+/*  n_flat < E.  A captured graph sizes its buffers with it once.             */
+/*                                                                            */
+/*  slm_moe_sum (sum_out): out[t, :] = T(sum_j in[t, j, :]) -- fp32, in order */
+/*  j = 0..k-1, one rounding; any k >= 1; contiguous input and output.        */
+/*                                                                            */
+/*  Grouped GEMM.  For every 32-row block b with b * 32 < *n_padded_tokens    */
+/*  (read on the device), e = expert_ids[b], and every non-padding            */
+/*  idx = sorted_token_idxes[b * 32 + r] (0 <= idx < n_flat):                 */
+/*     C[idx, :] = epilogue( A[idx / a_div, :] . dequant(W_e) )               */
+/*  i.e. the align step must have run with block_size 32.  a_div = k when A   */
+/*  is the token matrix [T, K] (gate_up), 1 when A is [n_flat, K] (down).     */
+/*  W_e: the packed layout of slm_w4_prepack (SLM_W4_PAIRED included) at      */
+/*  wq + e * wq_expert_stride, sz + e * sz_expert_stride (bytes, multiples of */
+/*  16 / 4); one expert's tables < 4 GiB each (32-bit offsets inside an       */
+/*  expert; the expert base is a 64-bit pointer).  Epilogue: plain;           */
+/*  SLM_W4_SILU_MUL on paired weights (format must carry SLM_W4_PAIRED; C is  */
+/*  [n_flat, N/2]), bit-identical to the plain grouped GEMM followed by       */
+/*  slm_silu_mul; or row scale: T(acc * row_scale[idx]) -- the fp32           */
+/*  accumulator times the routing weight, one rounding (not with SILU_MUL).   */
+/*  Padding rows may load a clamped row of A and are never stored; blocks     */
+/*  beyond n_padded return at once (the grid is max_blocks x ceil(N / 128)    */
+/*  tiles of 32 x 128, no split-K, no workspace).  f16 / bf16; group_size 32, */
+/*  64, a power of two >= 128, or K (per-channel); K % 128 == 0, N % 64 == 0; */
+/*  GPTQ and AWQ.  SLM_ERR_UNSUPPORTED before any launch: perm (act-order),   */
+/*  bias, the 8-bit formats, other shapes / dtypes.                           */
+/* ========================================================================== */
+SLM_API int slm_moe_topk_softmax(const float* logits /* [T, E] */, float* weights /* [T, k] */,
+                                 int32_t* indices /* [T, k] */, int64_t n_tokens, int32_t n_experts,
+                                 int32_t topk, int32_t renormalize, void* stream);
+SLM_API int slm_moe_grouped_topk_sigmoid(const float* logits /* [T, E] */, const float* correction_bias /* [E] */,
+                                         float* weights /* [T, k] */, int32_t* indices /* [T, k] */,
+                                         int64_t n_tokens, int32_t n_experts, int32_t n_expert_groups,
+                                         int32_t topk_group, int32_t topk, float scaling_factor, void* stream);
+
+/* worst-case sizes of the align step's outputs; SLM_ERR_INVALID_ARG on n_flat < 0, E outside 1..1024 or a
+ * block_size outside {16, 32, 64, 128, 256} */
+SLM_API int slm_moe_align_capacity(int64_t n_flat, int32_t n_experts, int32_t block_size,
+                                   int64_t* max_padded, int64_t* max_blocks);
+
+typedef struct slm_moe_align_args {
+  const int32_t* topk_ids;          /* [n_flat] = [T, k] contiguous                               */
+  int32_t* sorted_token_idxes;      /* [sorted_capacity]                                          */
+  int32_t* expert_ids;              /* [blocks_capacity]                                          */
+  int32_t* n_padded_tokens;         /* [1]                                                        */
+  int32_t* cu_sum;                  /* [n_experts + 1] or NULL                                    */
+  int64_t n_flat;                   /* T * k, < 2^31 - 256                                        */
+  int64_t sorted_capacity;          /* entries of sorted_token_idxes, >= max_padded               */
+  int64_t blocks_capacity;          /* entries of expert_ids, >= max_blocks                       */
+  int32_t n_experts;
+  int32_t block_size;
+} slm_moe_align_args;
+SLM_API int slm_moe_align_block(const slm_moe_align_args* a, void* stream);
+
+SLM_API int slm_moe_sum(void* out /* [T, dim] */, const void* in /* [T, k, dim] */, int64_t n_tokens,
+                        int32_t topk, int64_t dim, int32_t dtype, void* stream);
+
+typedef struct slm_moe_gemm_args {
+  const void* a;                    /* [n_flat / a_div, K] T, row stride lda (elements)           */
+  const void* wq;                   /* expert 0's packed weights                                  */
+  const void* sz;                   /* expert 0's packed scale / zero table                       */
+  const int32_t* perm;              /* must be NULL (act-order experts: unsupported)              */
+  const void* bias;                 /* must be NULL                                               */
+  void* c;                          /* [n_flat, N] T (SILU_MUL: [n_flat, N/2]), row stride ldc    */
+  const float* row_scale;           /* [n_flat] fp32 or NULL                                      */
+  const int32_t* sorted_token_idxes;
+  const int32_t* expert_ids;
+  const int32_t* n_padded_tokens;   /* [1], read on the device                                    */
+  int64_t wq_expert_stride;         /* bytes between experts' packed weights                      */
+  int64_t sz_expert_stride;         /* bytes between experts' scale / zero tables                 */
+  int64_t n_flat;                   /* rows of c = T * k; the padding id                          */
+  int64_t K, N;
+  int64_t lda, ldc;
+  int64_t group_size;               /* K for per-channel                                          */
+  int32_t a_div;                    /* >= 1                                                       */
+  int32_t n_experts;
+  int32_t max_blocks;               /* sizes the grid: slm_moe_align_capacity(n_flat, E, 32)      */
+  int32_t dtype;
+  int32_t format;                   /* slm_w4_format the experts were packed from (| SLM_W4_PAIRED) */
+  int32_t flags;                    /* 0 or SLM_W4_SILU_MUL                                       */
+} slm_moe_gemm_args;
+SLM_API int slm_moe_w4a16_gemm(const slm_moe_gemm_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,32 @@ class RejectionArgs(C.Structure):
     ]
 
 
+class MoeAlignArgs(C.Structure):
+    """struct slm_moe_align_args (include/slm_hip.h section 10)."""
+    _fields_ = [
+        ("topk_ids", C.c_void_p), ("sorted_token_idxes", C.c_void_p), ("expert_ids", C.c_void_p),
+        ("n_padded_tokens", C.c_void_p), ("cu_sum", C.c_void_p),
+        ("n_flat", C.c_int64), ("sorted_capacity", C.c_int64), ("blocks_capacity", C.c_int64),
+        ("n_experts", C.c_int32), ("block_size", C.c_int32),
+    ]
+
+
+class MoeGemmArgs(C.Structure):
+    """struct slm_moe_gemm_args (include/slm_hip.h section 10)."""
+    _fields_ = [
+        ("a", C.c_void_p), ("wq", C.c_void_p), ("sz", C.c_void_p), ("perm", C.c_void_p), ("bias", C.c_void_p),
+        ("c", C.c_void_p), ("row_scale", C.c_void_p),
+        ("sorted_token_idxes", C.c_void_p), ("expert_ids", C.c_void_p), ("n_padded_tokens", C.c_void_p),
+        ("wq_expert_stride", C.c_int64), ("sz_expert_stride", C.c_int64), ("n_flat", C.c_int64),
+        ("K", C.c_int64), ("N", C.c_int64), ("lda", C.c_int64), ("ldc", C.c_int64), ("group_size", C.c_int64),
+        ("a_div", C.c_int32), ("n_experts", C.c_int32), ("max_blocks", C.c_int32), ("dtype", C.c_int32),
+        ("format", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
+SLM_MOE_GEMM_BLOCK = 32  # rows per block of the grouped GEMM: the align step's block_size
+
+
 _lib = None
 
 
@@ -233,6 +259,16 @@ def lib() -> C.CDLL:
         ("slm_logits_process", C.c_int, [C.POINTER(SamplingArgs), C.c_void_p]),
         ("slm_rejection_sample_workspace_bytes", C.c_size_t, [C.POINTER(RejectionArgs)]),
         ("slm_rejection_sample", C.c_int, [C.POINTER(RejectionArgs), C.c_void_p]),
+        ("slm_moe_topk_softmax", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+        ("slm_moe_grouped_topk_sigmoid", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+          C.c_float, C.c_void_p]),
+        ("slm_moe_align_capacity", C.c_int,
+         [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        ("slm_moe_align_block", C.c_int, [C.POINTER(MoeAlignArgs), C.c_void_p]),
+        ("slm_moe_sum", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+        ("slm_moe_w4a16_gemm", C.c_int, [C.POINTER(MoeGemmArgs), C.c_void_p]),
     ]:
         fn = getattr(L, name)  # AttributeError here = library/header mismatch: fail loudly
         fn.restype = restype

@@ -1,0 +1,165 @@
+// slm_moe_hip.cpp -- see slm_moe_hip.h.  Host code only: tensors are unpacked into the C ABI's arguments and
+// handed to the slm_moe_* entry points on torch's current HIP stream.
+#include "slm_moe_hip.h"
+
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+
+#include "slm_hip.h"
+
+namespace {
+
+void check(int rc, const char* what) {
+  TORCH_CHECK(rc == SLM_OK, what, " failed: ", slm_status_string(rc), " (", rc, ")",
+              rc == SLM_ERR_LAUNCH ? slm_last_hip_error() : "");
+}
+
+void* stream_of(const torch::Tensor& t) {
+  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
+}
+
+void check_i32(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt && t.is_contiguous(), "slm moe: ", what,
+              " must be a contiguous int32 GPU tensor");
+}
+
+void check_route(const torch::Tensor& logits, const torch::Tensor& w, const torch::Tensor& idx) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.scalar_type() == torch::kFloat && logits.is_contiguous(),
+              "slm moe: gating_logits must be a contiguous fp32 GPU [n_tokens, n_experts] tensor");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kFloat && w.is_contiguous() && w.dim() == 2 &&
+                  w.size(0) == logits.size(0),
+              "slm moe: topk_weights must be contiguous fp32 [n_tokens, topk]");
+  check_i32(idx, "topk_indices");
+  TORCH_CHECK(idx.sizes() == w.sizes(), "slm moe: topk_indices must have the shape of topk_weights");
+}
+
+int dtype_code(const torch::Tensor& t) {
+  if (t.scalar_type() == torch::kBFloat16) return SLM_BF16;
+  if (t.scalar_type() == torch::kHalf) return SLM_F16;
+  TORCH_CHECK(false, "slm moe: fp16 / bf16 activations only, got ", t.scalar_type());
+  return -1;
+}
+
+}  // namespace
+
+namespace slm {
+
+void moe_topk_softmax(const torch::Tensor& gating_logits, torch::Tensor& topk_weights, torch::Tensor& topk_indices,
+                      bool renormalize) {
+  check_route(gating_logits, topk_weights, topk_indices);
+  check(slm_moe_topk_softmax(gating_logits.const_data_ptr<float>(), topk_weights.data_ptr<float>(),
+                             topk_indices.data_ptr<int32_t>(), gating_logits.size(0),
+                             static_cast<int32_t>(gating_logits.size(1)), static_cast<int32_t>(topk_weights.size(-1)),
+                             renormalize ? 1 : 0, stream_of(gating_logits)),
+        "slm_moe_topk_softmax");
+}
+
+void moe_w4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& wq, const torch::Tensor& sz, torch::Tensor& c,
+                         const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+                         const torch::Tensor& n_padded_tokens, int64_t K, int64_t N, int64_t group_size,
+                         int64_t a_div, int64_t format, const torch::Tensor& row_scale, bool silu_mul) {
+  TORCH_CHECK(a.is_cuda() && c.is_cuda() && a.dim() == 2 && c.dim() == 2 && a.stride(1) == 1 && c.stride(1) == 1,
+              "slm moe: A and C must be 2-D GPU tensors with contiguous rows");
+  TORCH_CHECK(a.scalar_type() == c.scalar_type(), "slm moe: A and C must share a dtype");
+  TORCH_CHECK(wq.is_cuda() && sz.is_cuda() && wq.dim() == 2 && sz.dim() == 2 && wq.size(0) == sz.size(0) &&
+                  wq.stride(1) == 1 && sz.stride(1) == 1 && wq.element_size() == 4 && sz.element_size() == 4,
+              "slm moe: wq / sz must be [n_experts, words] 32-bit GPU tensors");
+  check_i32(sorted_token_idxes, "sorted_token_idxes");
+  check_i32(expert_ids, "expert_ids");
+  check_i32(n_padded_tokens, "n_padded_tokens");
+  TORCH_CHECK(a.size(1) == K && c.size(1) == (silu_mul ? N / 2 : N) && a_div >= 1 && a.size(0) * a_div >= c.size(0),
+              "slm moe: grouped GEMM shape mismatch");
+  TORCH_CHECK(sorted_token_idxes.numel() >= expert_ids.numel() * 32,
+              "slm moe: sorted_token_idxes is shorter than expert_ids.numel() blocks of 32");
+  slm_moe_gemm_args g{};
+  g.a = a.data_ptr();
+  g.wq = wq.data_ptr();
+  g.sz = sz.data_ptr();
+  g.c = c.data_ptr();
+  if (row_scale.defined()) {
+    TORCH_CHECK(row_scale.is_cuda() && row_scale.scalar_type() == torch::kFloat && row_scale.is_contiguous() &&
+                    row_scale.numel() == c.size(0),
+                "slm moe: row_scale must be contiguous fp32 with one entry per row of C");
+    g.row_scale = row_scale.const_data_ptr<float>();
+  }
+  g.sorted_token_idxes = sorted_token_idxes.const_data_ptr<int32_t>();
+  g.expert_ids = expert_ids.const_data_ptr<int32_t>();
+  g.n_padded_tokens = n_padded_tokens.const_data_ptr<int32_t>();
+  g.wq_expert_stride = wq.stride(0) * 4;
+  g.sz_expert_stride = sz.stride(0) * 4;
+  g.n_flat = c.size(0);
+  g.K = K;
+  g.N = N;
+  g.lda = a.stride(0);
+  g.ldc = c.stride(0);
+  g.group_size = group_size;
+  g.a_div = static_cast<int32_t>(a_div);
+  g.n_experts = static_cast<int32_t>(wq.size(0));
+  g.max_blocks = static_cast<int32_t>(expert_ids.numel());
+  g.dtype = dtype_code(a);
+  g.format = static_cast<int32_t>(format);
+  g.flags = silu_mul ? SLM_W4_SILU_MUL : 0;
+  check(slm_moe_w4a16_gemm(&g, stream_of(a)), "slm_moe_w4a16_gemm");
+}
+
+}  // namespace slm
+
+namespace llm::kernel {
+
+void topk_softmax(const torch::Tensor& gating_logits, torch::Tensor& topk_weights, torch::Tensor& topk_indices) {
+  slm::moe_topk_softmax(gating_logits, topk_weights, topk_indices, /*renormalize=*/false);
+}
+
+void grouped_topk_sigmoid(const torch::Tensor& gating_logits, const torch::Tensor& correction_bias,
+                          const int n_expert_groups, const int topk_group, const int topk, float scaling_factor,
+                          torch::Tensor& topk_weights, torch::Tensor& topk_indices) {
+  check_route(gating_logits, topk_weights, topk_indices);
+  TORCH_CHECK(topk_weights.size(-1) == topk, "slm moe: topk_weights must be [n_tokens, topk]");
+  TORCH_CHECK(correction_bias.is_cuda() && correction_bias.scalar_type() == torch::kFloat &&
+                  correction_bias.is_contiguous() && correction_bias.numel() == gating_logits.size(1),
+              "slm moe: correction_bias must be contiguous fp32 [n_experts]");
+  check(slm_moe_grouped_topk_sigmoid(gating_logits.const_data_ptr<float>(), correction_bias.const_data_ptr<float>(),
+                                     topk_weights.data_ptr<float>(), topk_indices.data_ptr<int32_t>(),
+                                     gating_logits.size(0), static_cast<int32_t>(gating_logits.size(1)),
+                                     n_expert_groups, topk_group, topk, scaling_factor, stream_of(gating_logits)),
+        "slm_moe_grouped_topk_sigmoid");
+}
+
+namespace moe {
+
+void permute_align_block(torch::Tensor topk_ids, int64_t n_experts, int64_t block_size,
+                         torch::Tensor sorted_token_idxes, torch::Tensor experts_ids, torch::Tensor n_padded_tokens,
+                         torch::Tensor cu_sum) {
+  check_i32(topk_ids, "topk_ids");
+  check_i32(sorted_token_idxes, "sorted_token_idxes");
+  check_i32(experts_ids, "experts_ids");
+  check_i32(n_padded_tokens, "n_padded_tokens");
+  slm_moe_align_args a{};
+  a.topk_ids = topk_ids.const_data_ptr<int32_t>();
+  a.sorted_token_idxes = sorted_token_idxes.data_ptr<int32_t>();
+  a.expert_ids = experts_ids.data_ptr<int32_t>();
+  a.n_padded_tokens = n_padded_tokens.data_ptr<int32_t>();
+  if (cu_sum.defined() && cu_sum.numel() > 0) {
+    check_i32(cu_sum, "cu_sum");
+    TORCH_CHECK(cu_sum.numel() >= n_experts + 1, "slm moe: cu_sum needs n_experts + 1 entries");
+    a.cu_sum = cu_sum.data_ptr<int32_t>();
+  }
+  a.n_flat = topk_ids.numel();
+  a.sorted_capacity = sorted_token_idxes.numel();
+  a.blocks_capacity = experts_ids.numel();
+  a.n_experts = static_cast<int32_t>(n_experts);
+  a.block_size = static_cast<int32_t>(block_size);
+  check(slm_moe_align_block(&a, stream_of(topk_ids)), "slm_moe_align_block");
+}
+
+void sum_out(const torch::Tensor& input, torch::Tensor& output) {
+  TORCH_CHECK(input.is_cuda() && output.is_cuda() && input.dim() == 3 && input.is_contiguous() &&
+                  output.is_contiguous() && input.scalar_type() == output.scalar_type() && output.dim() == 2 &&
+                  output.size(0) == input.size(0) && output.size(1) == input.size(2),
+              "slm moe: sum_out takes contiguous [n_tokens, topk, dim] -> [n_tokens, dim] of one dtype");
+  check(slm_moe_sum(output.data_ptr(), input.data_ptr(), input.size(0), static_cast<int32_t>(input.size(1)),
+                    input.size(2), dtype_code(input), stream_of(input)),
+        "slm_moe_sum");
+}
+
+}  // namespace moe
+}  // namespace llm::kernel

@@ -1,0 +1,63 @@
+// slm_moe_hip.h -- the mixture-of-experts operators at the libtorch boundary, on top of the C ABI's section 10
+// (include/slm_hip.h; csrc/moe.hip, csrc/w4_moe.hip).
+//
+//   llm::kernel::topk_softmax, llm::kernel::grouped_topk_sigmoid      src/kernels/moe/topk_softmax_kernel.cu:272,
+//                                                                      grouped_topk_sigmoid_kernel.cu:280
+//   llm::kernel::moe::permute_align_block, llm::kernel::moe::sum_out  src/kernels/moe/align_block_kernel.cu:192, 242
+// with exactly the reference's signatures, so its callers compile unchanged, and
+//   slm::moe_w4_grouped_gemm   the grouped int4 GEMM over stacked packed experts (the reference's grouped GEMM,
+//                              src/kernels/gemm/, is a dense fp16 / bf16 kernel; int4 experts have no counterpart).
+// Everything runs on torch's current HIP stream and nothing synchronises with the host.
+// Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
+#pragma once
+#include <torch/torch.h>
+
+namespace llm::kernel {
+
+// the k largest logits per token (ties: the lower expert id), weights = softmax over all experts at those
+void topk_softmax(const torch::Tensor& gating_logits,  // [n_tokens, n_experts] fp32
+                  torch::Tensor& topk_weights,         // [n_tokens, topk] fp32
+                  torch::Tensor& topk_indices          // [n_tokens, topk] int32
+);
+
+void grouped_topk_sigmoid(const torch::Tensor& gating_logits,    // [n_tokens, n_experts] fp32
+                          const torch::Tensor& correction_bias,  // [n_experts] fp32
+                          const int n_expert_groups, const int topk_group, const int topk, float scaling_factor,
+                          torch::Tensor& topk_weights,  // [n_tokens, topk]
+                          torch::Tensor& topk_indices   // [n_tokens, topk]
+);
+
+namespace moe {
+
+// sorted_token_idxes / experts_ids must hold at least slm_moe_align_capacity(n_flat, n_experts, block_size) entries;
+// the kernel writes the padding entries of [0, n_padded) itself, an expert's indices in ascending order
+void permute_align_block(torch::Tensor topk_ids,  // [n_tokens, topk] int32
+                         int64_t n_experts, int64_t block_size,
+                         torch::Tensor sorted_token_idxes,  // [n_padded_permuted_tokens+]
+                         torch::Tensor experts_ids,         // [n_blocks+]
+                         torch::Tensor n_padded_tokens,     // [1]
+                         torch::Tensor cu_sum               // [n_experts+1]
+);
+
+void sum_out(const torch::Tensor& input,  // [n_tokens, topk, dim]
+             torch::Tensor& output);      // [n_tokens, dim]
+
+}  // namespace moe
+}  // namespace llm::kernel
+
+namespace slm {
+
+// topk_softmax with the k weights divided by their sum (Mixtral's rule)
+void moe_topk_softmax(const torch::Tensor& gating_logits, torch::Tensor& topk_weights, torch::Tensor& topk_indices,
+                      bool renormalize);
+
+// C[idx] = epilogue(A[idx / a_div] . dequant(W_e)) over the 32-row blocks of permute_align_block(block_size = 32).
+// wq [E, K * N / 8], sz [E, (K / group_size) * N] int32: slm_w4_prepack images stacked per expert; format: the
+// slm_w4_format they were packed from (| SLM_W4_PAIRED).  row_scale: fp32 [n_flat] or undefined; silu_mul: paired
+// experts, c is [n_flat, N / 2].
+void moe_w4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& wq, const torch::Tensor& sz, torch::Tensor& c,
+                         const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+                         const torch::Tensor& n_padded_tokens, int64_t K, int64_t N, int64_t group_size,
+                         int64_t a_div, int64_t format, const torch::Tensor& row_scale, bool silu_mul);
+
+}  // namespace slm

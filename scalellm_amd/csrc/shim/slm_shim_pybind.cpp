@@ -9,6 +9,7 @@
 
 #include "slm_attn_handler_hip.h"
 #include "slm_llama_hip.h"
+#include "slm_moe_hip.h"
 #include "slm_qlinear_hip.h"
 #include "slm_rejection_sampler_hip.h"
 #include "slm_sampling_hip.h"
@@ -182,6 +183,34 @@ PYBIND11_MODULE(_slm_shim, m) {
   m.def("rejection_greedy_sample", &slm::RejectionSampler::greedy_sample, py::arg("draft_token_ids"),
         py::arg("target_probs"), py::arg("bonus_token_ids"), py::arg("mask_out_rejected_tokens"));
   m.def("build_accepted_mask", &slm::RejectionSampler::build_accepted_mask, py::arg("accepted"));
+  // mixture of experts (slm_moe_hip.h): the reference's routing / alignment functions + the grouped int4 GEMM
+  m.def("moe_topk_softmax", [](const torch::Tensor& logits, torch::Tensor w, torch::Tensor idx) {
+          llm::kernel::topk_softmax(logits, w, idx);
+        }, py::arg("gating_logits"), py::arg("topk_weights"), py::arg("topk_indices"));
+  m.def("moe_topk_softmax_renorm", [](const torch::Tensor& logits, torch::Tensor w, torch::Tensor idx) {
+          slm::moe_topk_softmax(logits, w, idx, true);
+        }, py::arg("gating_logits"), py::arg("topk_weights"), py::arg("topk_indices"));
+  m.def("moe_grouped_topk_sigmoid",
+        [](const torch::Tensor& logits, const torch::Tensor& bias, int n_expert_groups, int topk_group, int topk,
+           float scaling_factor, torch::Tensor w, torch::Tensor idx) {
+          llm::kernel::grouped_topk_sigmoid(logits, bias, n_expert_groups, topk_group, topk, scaling_factor, w, idx);
+        }, py::arg("gating_logits"), py::arg("correction_bias"), py::arg("n_expert_groups"), py::arg("topk_group"),
+        py::arg("topk"), py::arg("scaling_factor"), py::arg("topk_weights"), py::arg("topk_indices"));
+  m.def("moe_permute_align_block", &llm::kernel::moe::permute_align_block, py::arg("topk_ids"), py::arg("n_experts"),
+        py::arg("block_size"), py::arg("sorted_token_idxes"), py::arg("experts_ids"), py::arg("n_padded_tokens"),
+        py::arg("cu_sum"));
+  m.def("moe_sum_out", [](const torch::Tensor& input, torch::Tensor output) { llm::kernel::moe::sum_out(input, output); },
+        py::arg("input"), py::arg("output"));
+  m.def("moe_w4_grouped_gemm",
+        [](const torch::Tensor& a, const torch::Tensor& wq, const torch::Tensor& sz, torch::Tensor c,
+           const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens,
+           int64_t K, int64_t N, int64_t group_size, int64_t a_div, int64_t format,
+           const c10::optional<torch::Tensor>& row_scale, bool silu_mul) {
+          slm::moe_w4_grouped_gemm(a, wq, sz, c, sorted_token_idxes, expert_ids, n_padded_tokens, K, N, group_size,
+                                   a_div, format, row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
+        }, py::arg("a"), py::arg("wq"), py::arg("sz"), py::arg("c"), py::arg("sorted_token_idxes"),
+        py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("K"), py::arg("N"), py::arg("group_size"),
+        py::arg("a_div"), py::arg("format"), py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
   py::class_<slm::InputParameters>(m, "InputParameters")
       .def(py::init<>())
       .def_readwrite("num_sequences", &slm::InputParameters::num_sequences)

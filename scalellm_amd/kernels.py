@@ -1165,3 +1165,167 @@ def rejection_sample(draft_token_ids: torch.Tensor, draft_probs: Optional[torch.
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
     check(L.slm_rejection_sample(C.byref(a), _stream()), "slm_rejection_sample")
     return next_tokens
+
+
+# ---------------------------------------------------------------------------------------
+# mixture of experts (include/slm_hip.h section 10): routing, block alignment, grouped int4 GEMM
+#   moe_topk_softmax / moe_grouped_topk_sigmoid <- llm::kernel::topk_softmax / grouped_topk_sigmoid
+#   moe_align_block / moe_sum                   <- llm::kernel::moe::permute_align_block / sum_out
+#   moe_w4_grouped_gemm                         <- the grouped GEMM of src/kernels/gemm/ over int4 experts
+# ---------------------------------------------------------------------------------------
+MOE_GEMM_BLOCK = _lib.SLM_MOE_GEMM_BLOCK
+
+
+class PackedMoeW4:
+    """The packed int4 weights of E experts of one shape, stacked: wq [E, K * N / 8] and sz [E, G * N] int32,
+    expert e in row e (each row is one PackedW4 image, include/slm_hip.h section 3)."""
+
+    def __init__(self, wq, sz, K, N, group_size, dtype, fmt, paired=False):
+        self.wq, self.sz = wq, sz
+        self.K, self.N, self.group_size, self.dtype = K, N, group_size, dtype
+        self.fmt, self.paired = fmt, paired
+        self.n_experts = wq.size(0)
+
+    def expert(self, e: int) -> PackedW4:
+        """Expert e as a dense-GEMM weight (a view: no copy)."""
+        return PackedW4(self.wq[e], self.sz[e], None, self.K, self.N, self.group_size, self.dtype, self.paired)
+
+    def nbytes(self) -> int:
+        return (self.wq.numel() + self.sz.numel()) * 4
+
+
+def moe_stack_experts(experts, fmt: int) -> PackedMoeW4:
+    """Stack per-expert PackedW4 images (all of one shape, no act-order perm) into a PackedMoeW4.
+    fmt: _lib.SLM_W4_GPTQ or _lib.SLM_W4_AWQ, the checkpoint format they were packed from."""
+    p0 = experts[0]
+    for p in experts:
+        if p.perm is not None:
+            raise SlmError("act-order (perm) and 8-bit experts are not supported by the grouped GEMM")
+        if (p.K, p.N, p.group_size, p.dtype, p.paired) != (p0.K, p0.N, p0.group_size, p0.dtype, p0.paired):
+            raise SlmError("all experts must share K, N, group_size, dtype and pairing")
+    wq = torch.stack([p.wq.view(-1) for p in experts]).contiguous()
+    sz = torch.stack([p.sz.view(-1) for p in experts]).contiguous()
+    return PackedMoeW4(wq, sz, p0.K, p0.N, p0.group_size, p0.dtype, fmt, p0.paired)
+
+
+def _route_out(logits, topk, weights, indices):
+    _require_gpu(logits, weights, indices)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise SlmError("router logits must be contiguous fp32 [n_tokens, n_experts]")
+    T = logits.size(0)
+    if weights is None:
+        weights = torch.empty(T, topk, dtype=torch.float32, device=logits.device)
+    if indices is None:
+        indices = torch.empty(T, topk, dtype=torch.int32, device=logits.device)
+    for t, dt, name in ((weights, torch.float32, "topk_weights"), (indices, torch.int32, "topk_indices")):
+        if t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != (T, topk):
+            raise SlmError(f"{name} must be contiguous {dt} [n_tokens, topk]")
+    return weights, indices
+
+
+def moe_topk_softmax(logits: torch.Tensor, topk: int, renormalize: bool = False,
+                     weights: Optional[torch.Tensor] = None, indices: Optional[torch.Tensor] = None):
+    """llm::kernel::topk_softmax: the k largest logits per token (ties: the lower expert id), weights =
+    softmax over all experts at those; renormalize: divided by their sum.  Returns (weights, indices)."""
+    weights, indices = _route_out(logits, topk, weights, indices)
+    check(_lib.lib().slm_moe_topk_softmax(logits.data_ptr(), weights.data_ptr(), indices.data_ptr(), logits.size(0),
+                                          logits.size(1), topk, 1 if renormalize else 0, _stream()),
+          "slm_moe_topk_softmax")
+    return weights, indices
+
+
+def moe_grouped_topk_sigmoid(logits: torch.Tensor, correction_bias: torch.Tensor, n_expert_groups: int,
+                             topk_group: int, topk: int, scaling_factor: float,
+                             weights: Optional[torch.Tensor] = None, indices: Optional[torch.Tensor] = None):
+    """llm::kernel::grouped_topk_sigmoid (DeepSeek-V3 style routing).  Returns (weights, indices)."""
+    weights, indices = _route_out(logits, topk, weights, indices)
+    _require_gpu(correction_bias)
+    if correction_bias.dtype != torch.float32 or not correction_bias.is_contiguous() or \
+            correction_bias.numel() != logits.size(1):
+        raise SlmError("correction_bias must be contiguous fp32 [n_experts]")
+    check(_lib.lib().slm_moe_grouped_topk_sigmoid(logits.data_ptr(), correction_bias.data_ptr(), weights.data_ptr(),
+                                                  indices.data_ptr(), logits.size(0), logits.size(1),
+                                                  n_expert_groups, topk_group, topk, float(scaling_factor),
+                                                  _stream()), "slm_moe_grouped_topk_sigmoid")
+    return weights, indices
+
+
+def moe_align_capacity(n_flat: int, n_experts: int, block_size: int):
+    """(max_padded, max_blocks): the worst case of moe_align_block's outputs for n_flat = T * k assignments."""
+    mp, mb = C.c_int64(0), C.c_int64(0)
+    check(_lib.lib().slm_moe_align_capacity(n_flat, n_experts, block_size, C.byref(mp), C.byref(mb)),
+          "slm_moe_align_capacity")
+    return mp.value, mb.value
+
+
+def moe_align_block(topk_ids: torch.Tensor, n_experts: int, block_size: int, sorted_token_idxes: torch.Tensor,
+                    expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor,
+                    cu_sum: Optional[torch.Tensor] = None) -> None:
+    """llm::kernel::moe::permute_align_block, with the flat indices of an expert in ascending order and the
+    padding entries written by the kernel (include/slm_hip.h section 10)."""
+    _require_gpu(topk_ids, sorted_token_idxes, expert_ids, n_padded_tokens, cu_sum)
+    for t in (topk_ids, sorted_token_idxes, expert_ids, n_padded_tokens, cu_sum):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise SlmError("moe_align_block takes contiguous int32 tensors")
+    if cu_sum is not None and cu_sum.numel() < n_experts + 1:
+        raise SlmError("cu_sum needs n_experts + 1 entries")
+    a = _lib.MoeAlignArgs()
+    a.topk_ids, a.sorted_token_idxes = topk_ids.data_ptr(), sorted_token_idxes.data_ptr()
+    a.expert_ids, a.n_padded_tokens = expert_ids.data_ptr(), n_padded_tokens.data_ptr()
+    a.cu_sum = cu_sum.data_ptr() if cu_sum is not None else None
+    a.n_flat = topk_ids.numel()
+    a.sorted_capacity, a.blocks_capacity = sorted_token_idxes.numel(), expert_ids.numel()
+    a.n_experts, a.block_size = n_experts, block_size
+    check(_lib.lib().slm_moe_align_block(C.byref(a), _stream()), "slm_moe_align_block")
+
+
+def moe_sum(inp: torch.Tensor, out: torch.Tensor) -> None:
+    """llm::kernel::moe::sum_out: out [T, dim] = sum over j of inp [T, k, dim], fp32, one rounding."""
+    _require_gpu(inp, out)
+    if inp.dim() != 3 or not inp.is_contiguous() or not out.is_contiguous() or inp.dtype != out.dtype or \
+            tuple(out.shape) != (inp.size(0), inp.size(2)):
+        raise SlmError("moe_sum: input [T, k, dim] and output [T, dim] must be contiguous and of one dtype")
+    check(_lib.lib().slm_moe_sum(out.data_ptr(), inp.data_ptr(), inp.size(0), inp.size(1), inp.size(2),
+                                 _dtype_code(inp), _stream()), "slm_moe_sum")
+
+
+def moe_w4_grouped_gemm(a: torch.Tensor, experts: PackedMoeW4, c: torch.Tensor, sorted_token_idxes: torch.Tensor,
+                        expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor, a_div: int,
+                        row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """C[idx] = epilogue(A[idx // a_div] . dequant(W_e)) for the 32-row blocks moe_align_block(block_size = 32)
+    produced.  a_div = topk when `a` holds one row per token, 1 when it holds one per (token, expert).
+    silu_mul: paired (gate | up) experts, c is [n_flat, N / 2]; row_scale: fp32 [n_flat] routing weights applied
+    to the fp32 accumulator.  The grid covers expert_ids.numel() blocks; the count in use is read on the device."""
+    _require_gpu(a, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    if a.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1:
+        raise SlmError("A and C must be 2-D with contiguous rows")
+    if silu_mul and not experts.paired:
+        raise SlmError("silu_mul=True needs experts packed with paired=True")
+    n_flat = c.size(0)
+    if a.size(1) != experts.K or c.size(1) != (experts.N // 2 if silu_mul else experts.N) or \
+            a_div < 1 or a.size(0) * a_div < n_flat:
+        raise SlmError("grouped GEMM shape mismatch")
+    if a.dtype != experts.dtype or c.dtype != experts.dtype:
+        raise SlmError("activation / output dtype must match the experts' scales dtype")
+    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
+    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
+        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
+                                  row_scale.numel() != n_flat):
+        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
+    g = _lib.MoeGemmArgs()
+    g.a, g.wq, g.sz, g.c = a.data_ptr(), experts.wq.data_ptr(), experts.sz.data_ptr(), c.data_ptr()
+    g.perm, g.bias = None, None
+    g.row_scale = row_scale.data_ptr() if row_scale is not None else None
+    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
+    g.n_padded_tokens = n_padded_tokens.data_ptr()
+    g.wq_expert_stride, g.sz_expert_stride = experts.wq.stride(0) * 4, experts.sz.stride(0) * 4
+    g.n_flat, g.K, g.N = n_flat, experts.K, experts.N
+    g.lda, g.ldc, g.group_size = a.stride(0), c.stride(0), experts.group_size
+    g.a_div, g.n_experts, g.max_blocks = a_div, experts.n_experts, expert_ids.numel()
+    g.dtype = _dtype_code(a)
+    g.format = experts.fmt | (_lib.SLM_W4_PAIRED if experts.paired else 0)
+    g.flags = _lib.SLM_W4_SILU_MUL if silu_mul else 0
+    check(_lib.lib().slm_moe_w4a16_gemm(C.byref(g), _stream()), "slm_moe_w4a16_gemm")

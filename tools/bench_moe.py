@@ -1,0 +1,167 @@
+"""FusedMoE (scalellm_amd/moe.py: routing, align, two grouped int4 GEMMs, sum) at Mixtral-8x7B shapes against
+what the dense path offers: a host loop of per-expert slm_w4a16_gemm calls.
+
+    python tools/bench_moe.py [--out profiles/r09_moe.jsonl] [--tokens 1,32,256] [--iters 200]
+
+hidden 4096, intermediate 14336, E = 8, k = 2, AWQ group 128, bf16 (random weights: 705 MB packed).  One JSON
+line per T:
+  fused_us        FusedMoE.forward captured once in a hipGraph and replayed `iters` times between device events.
+                  Before each replay one of `--pool` different inputs is copied into the static buffer, so the routing
+                  -- and with it the experts streamed -- changes from replay to replay and the weights (beyond the
+                  256 MB MALL as soon as more than two experts are in use) come from HBM.
+  touched_bytes   packed weight + scale bytes of the experts in use (gate_up and down), each counted ONCE, averaged
+                  over the pool; streamed_bytes counts an expert once per 32-row block (what the kernel issues when
+                  nothing is served from cache).  frac_7tbs = touched_bytes / fused_us over the 7.0 TB/s read ceiling
+                  measured in this repository.
+  loop_us         the same inputs through the dense kernels: per expert, torch index_select of its tokens,
+                  gptq_gemm(gate_up, silu_mul), gptq_gemm(down), scale by the routing weight, index_add_ -- eager,
+                  with the routing and the per-expert counts known on the host beforehand (not timed).
+  loop_graph_us   that loop for ONE fixed routing captured in a graph (host-known counts can be captured only for a
+                  routing that never changes): its best case, without launch gaps.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from scalellm_amd import kernels, moe  # noqa: E402
+from scalellm_amd.layers import QuantArgs  # noqa: E402
+
+HID, INTER, NE, TOPK, GS = 4096, 14336, 8, 2, 128
+READ_CEILING = 7.0e12
+
+
+def _layer(max_tokens, dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    sd = {}
+    for e in range(NE):
+        for w, (K, N) in (("w1", (HID, INTER)), ("w3", (HID, INTER)), ("w2", (INTER, HID))):
+            sd[f"experts.{e}.{w}.qweight"] = torch.randint(-2**31, 2**31 - 1, (K, N // 8), device=dev, generator=g,
+                                                           dtype=torch.int64).to(torch.int32)
+            sd[f"experts.{e}.{w}.qzeros"] = torch.randint(-2**31, 2**31 - 1, (K // GS, N // 8), device=dev, generator=g,
+                                                          dtype=torch.int64).to(torch.int32)
+            sd[f"experts.{e}.{w}.scales"] = (torch.rand(K // GS, N, device=dev, generator=g) * 0.015 + 0.005
+                                             ).to(torch.bfloat16)
+    sd["gate.weight"] = (torch.randn(NE, HID, device=dev, generator=g) * 0.05).to(torch.bfloat16)
+    layer = moe.FusedMoE(HID, INTER, NE, TOPK, QuantArgs("awq", 4, GS), scoring="softmax", renormalize=True,
+                         max_tokens=max_tokens, dtype=torch.bfloat16, device=dev)
+    layer.load_state_dict(sd)
+    layer(torch.zeros(1, HID, device=dev, dtype=torch.bfloat16))   # repack + buffers
+    return layer
+
+
+def _routing(layer, x):
+    logits = x.float() @ layer.gate_weight.float().t()
+    w, ids = kernels.moe_topk_softmax(logits, TOPK, True)
+    return w.cpu(), ids.cpu()
+
+
+def _loop_plan(layer, x, dev):
+    """host-known routing -> per expert (token rows, weights), as a dense-kernel host would hold them"""
+    w, ids = _routing(layer, x)
+    plan = []
+    for e in range(NE):
+        t, j = (ids == e).nonzero(as_tuple=True)
+        if t.numel():
+            plan.append((e, t.to(dev), w[t, j].to(dev, torch.bfloat16).unsqueeze(1)))
+    return plan
+
+
+def _loop_forward(layer, x, plan, out):
+    out.zero_()
+    for e, rows, w in plan:
+        xs = x.index_select(0, rows)
+        h = torch.empty(xs.size(0), INTER, dtype=x.dtype, device=x.device)
+        kernels.gptq_gemm(xs, layer.experts.gate_up.expert(e), h, silu_mul=True)
+        d = torch.empty(xs.size(0), HID, dtype=x.dtype, device=x.device)
+        kernels.gptq_gemm(h, layer.experts.down.expert(e), d)
+        out.index_add_(0, rows, d * w)
+    return out
+
+
+def _time(fn, iters):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for i in range(min(10, iters)):
+        fn(i)
+    torch.cuda.synchronize()
+    start.record()
+    for i in range(iters):
+        fn(i)
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--tokens", default="1,32,256")
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--pool", type=int, default=16)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_moe needs a GPU: there is no CPU path to time")
+    dev = torch.device("cuda")
+    tokens = [int(t) for t in args.tokens.split(",")]
+    layer = _layer(max(tokens), dev)
+    per_expert = (layer.experts.gate_up.nbytes() + layer.experts.down.nbytes()) // NE
+    gu_bytes, dn_bytes = layer.experts.gate_up.nbytes() // NE, layer.experts.down.nbytes() // NE
+    lines = []
+    for T in tokens:
+        g = torch.Generator(device=dev).manual_seed(T)
+        pool = [torch.randn(T, HID, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(args.pool)]
+        x_static, out_static = pool[0].clone(), torch.empty(T, HID, device=dev, dtype=torch.bfloat16)
+        eager = layer(pool[1]).clone()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            layer.forward(x_static, out=out_static)
+        x_static.copy_(pool[1])
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out_static, eager), "graph replay differs from the eager forward"
+
+        def fused(i):
+            x_static.copy_(pool[i % len(pool)])
+            graph.replay()
+
+        fused_us = _time(fused, args.iters)
+
+        plans = [_loop_plan(layer, x, dev) for x in pool]
+        out_loop = torch.zeros(T, HID, device=dev, dtype=torch.bfloat16)
+        loop_us = _time(lambda i: _loop_forward(layer, pool[i % len(pool)], plans[i % len(pool)], out_loop), args.iters)
+        # agreement of the two paths on one input (different rounding points: a tolerance, not equality)
+        ref = _loop_forward(layer, pool[1], plans[1], out_loop).float()
+        rel = float((eager.float() - ref).abs().mean() / ref.abs().mean())
+        torch.cuda.synchronize()
+        lg = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(lg):
+            _loop_forward(layer, x_static, plans[0], out_loop)
+        x_static.copy_(pool[0])
+        loop_graph_us = _time(lambda i: lg.replay(), args.iters)
+
+        used = [len(p) for p in plans]
+        blocks = [sum((rows.numel() + 31) // 32 for _, rows, _ in p) for p in plans]
+        touched = per_expert * sum(used) / len(used)
+        streamed = (gu_bytes + dn_bytes) * sum(blocks) / len(blocks)
+        line = dict(bench="moe_mixtral_8x7b_awq_g128_bf16", T=T, topk=TOPK, n_experts=NE,
+                    fused_us=round(fused_us, 2), loop_us=round(loop_us, 2), loop_graph_us=round(loop_graph_us, 2),
+                    experts_in_use=round(sum(used) / len(used), 2), row_blocks=round(sum(blocks) / len(blocks), 2),
+                    touched_bytes=int(touched), streamed_bytes=int(streamed),
+                    frac_7tbs=round(touched / (fused_us * 1e-6) / READ_CEILING, 4),
+                    streamed_frac_7tbs=round(streamed / (fused_us * 1e-6) / READ_CEILING, 4),
+                    fused_vs_loop_rel_err=round(rel, 5), iters=args.iters, pool=args.pool)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
