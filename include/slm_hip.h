@@ -308,6 +308,33 @@ typedef struct slm_w4_gemm_args {
 SLM_API size_t slm_w4a16_gemm_workspace_bytes(const slm_w4_gemm_args* a);
 /* number of partial slabs the call will leave in the workspace (>= 2), or 0 when it writes c as usual */
 SLM_API int32_t slm_w4a16_gemm_deferred_splits(const slm_w4_gemm_args* a);
+/* The launch the plan gives `a`: which kernel, its grid and its kernel-specific parameters.  A pure
+ * function of the argument block and the tuning table (csrc/w4_plan.hip): no HIP call, works without a
+ * GPU; the two queries above are read from the same plan (workspace = part_bytes + aperm_bytes).
+ * variant[] per kernel id, unused entries 0:
+ *   KS      { row tiles 1 / 2, chunks of K per wave, waves per workgroup, column tiles per workgroup }
+ *   GENERAL { row tiles, column tiles per wave, chunks per pass, 1 = post-scaled dequant }
+ *   M128    { weight ring depth, waves per column tile, column tiles per workgroup, 1 = LDS-DMA activations }
+ *   XL_SK   { 128-deep chunks of the work list per workgroup }                                        */
+typedef enum slm_w4_kernel {
+  SLM_W4_KERNEL_GEMV = 0,    /* w4_gemv.hip     dot2 GEMV, M <= 4                                  */
+  SLM_W4_KERNEL_KS = 1,      /* w4_ks.hip       K-sliced stream, one (M <= 32) or two (M <= 64) row tiles */
+  SLM_W4_KERNEL_SMALL = 2,   /* w4_small.hip    lean weight stream, M <= 32                       */
+  SLM_W4_KERNEL_GENERAL = 3, /* w4_general.hip  32 / 64 / 128-row tiles                           */
+  SLM_W4_KERNEL_M128 = 4,    /* w4_m128.hip     65 <= M <= 128, all rows in one workgroup         */
+  SLM_W4_KERNEL_WS = 5,      /* w4_ws.hip       wave-specialised 256 x 128 tiles                  */
+  SLM_W4_KERNEL_XL = 6,      /* w4_xl.hip       256 x 256 tiles                                   */
+  SLM_W4_KERNEL_XL_SK = 7    /* w4_xl.hip       256 x 256 tiles, stream-K                         */
+} slm_w4_kernel;
+typedef struct slm_w4_plan_info {
+  int32_t kernel;            /* slm_w4_kernel                                                      */
+  int32_t row_tiles;         /* 32-row tiles per workgroup the kernel works on (GEMV: 0, it has no row tiles) */
+  int32_t n_mblocks, n_nblocks, split_k, chunks_per_split; /* grid; chunks are 128 deep            */
+  int32_t variant[4];
+  uint64_t lds_bytes;        /* dynamic LDS of the launch (GEMV: without the norm prologue's row)  */
+  uint64_t part_bytes, aperm_bytes; /* workspace: split-K / stream-K partials, then the act-order A copy */
+} slm_w4_plan_info;
+SLM_API int slm_w4a16_gemm_plan(const slm_w4_gemm_args* a, slm_w4_plan_info* out);
 SLM_API int slm_w4a16_gemm(const slm_w4_gemm_args* a, void* stream);
 
 /* The M <= 4 GEMV with the RMSNorm that feeds it computed in its prologue: at batch 1 a decoder

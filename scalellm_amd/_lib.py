@@ -60,6 +60,23 @@ SLM_W4_DEFER_REDUCE = 1
 SLM_W4_SILU_MUL = 2
 SLM_W4_SHARES_CHIP = 4
 
+# enum slm_w4_kernel, in value order
+W4_KERNELS = ("GEMV", "KS", "SMALL", "GENERAL", "M128", "WS", "XL", "XL_SK")
+
+
+class W4PlanInfo(C.Structure):
+    """struct slm_w4_plan_info (include/slm_hip.h)."""
+    _fields_ = [
+        ("kernel", C.c_int32), ("row_tiles", C.c_int32), ("n_mblocks", C.c_int32),
+        ("n_nblocks", C.c_int32), ("split_k", C.c_int32), ("chunks_per_split", C.c_int32),
+        ("variant", C.c_int32 * 4),
+        ("lds_bytes", C.c_uint64), ("part_bytes", C.c_uint64), ("aperm_bytes", C.c_uint64),
+    ]
+
+    @property
+    def kernel_name(self) -> str:
+        return W4_KERNELS[self.kernel]
+
 
 class W4NormPrologue(C.Structure):
     """struct slm_w4_norm_prologue (include/slm_hip.h)."""
@@ -209,6 +226,7 @@ def lib() -> C.CDLL:
         ("slm_w4a16_gemm_workspace_bytes", C.c_size_t, [C.POINTER(W4GemmArgs)]),
         ("slm_w4a16_gemm", C.c_int, [C.POINTER(W4GemmArgs), C.c_void_p]),
         ("slm_w4a16_gemm_deferred_splits", C.c_int32, [C.POINTER(W4GemmArgs)]),
+        ("slm_w4a16_gemm_plan", C.c_int, [C.POINTER(W4GemmArgs), C.POINTER(W4PlanInfo)]),
         ("slm_w4a16_gemv_norm_supported", C.c_int32, [C.POINTER(W4GemmArgs)]),
         ("slm_w4a16_gemv_norm", C.c_int, [C.POINTER(W4GemmArgs), C.POINTER(W4NormPrologue), C.c_void_p]),
         ("slm_rms_norm_splitk", C.c_int,

@@ -254,38 +254,44 @@ __device__ __forceinline__ void store_ct_silu_pair(const GemmKParams& p, const f
 
 constexpr int W4_KC = 128;  // K granularity of the plan (split-K units, LDS chunk of the small-M kernels)
 
+// What each kernel file says about itself: what it can run, how much LDS it takes.  The plan that chooses
+// among them and the launch_* entry points are in w4_plan.h.
+
 // dot2 GEMV for M <= 4 (w4_gemv.hip): no MFMA, activations resident in LDS, K split inside the workgroup
 // norm: with the RMSNorm prologue (one more fp32 row in LDS)
 bool gemv_supported(int64_t M, int64_t K, int64_t group_size, bool norm = false);
-void launch_gemv(const GemmKParams& kp, int dtype, int ng, hipStream_t st);
+size_t gemv_lds_bytes(int64_t M, int64_t K, bool norm);
 // K splits across workgroups (1 = none; > 1 only when the caller takes fp32 partial slabs)
 int gemv_global_splits(int64_t M, int64_t K, int64_t N, bool partials_ok);
+// workgroups per split (runs of column tiles): the grid launch_gemv sizes for itself
+int gemv_workgroups(int64_t K, int64_t N, bool silu);
 
 // lean weight-streaming kernel for M <= 32 (w4_small.hip): BM = 32, BN = 128, 256 threads
-void launch_gemm_small(const GemmKParams& kp, int dtype, int ng, int n_blocks, hipStream_t st);
 constexpr size_t W4_SMALL_LDS_BYTES = 2 * 32 * 256;
 
 // K-sliced weight stream for M <= 32 (mt = 1) and 33 <= M <= 64 (mt = 2: two row tiles per unpacked
 // weight word) (w4_ks.hip): NW waves x CW chunks of K per workgroup, the activations of a wave's K
 // slice live in its registers, partial tiles meet in LDS once per tile
-void launch_gemm_ks(const GemmKParams& kp, int dtype, int ng, int cw, int nw, int n_blocks,
-                    hipStream_t st, int mt = 1);
-bool gemm_ks_config_ok(int ng, int cw, int nw, int mt = 1);
+bool gemm_ks_config_ok(int ng, int cw, int nw, int mt);
 constexpr size_t w4_ks_lds_bytes(int nw) { return (size_t)4 * nw * 4096 + 64; }  // 4 partial slots + counters
+
+// general kernel (w4_general.hip): MT = 1 / 2 / 4 row tiles x NTW column tiles per wave, PC chunks per pass
+// Instantiations of the general kernel that do not fit 256 VGPRs (hipcc spills: measured 4-7x
+// SLOWER than the PRE form of the same tile -- group 32 at 32 < M <= 64, qkv 83 vs 19 us) are neither
+// planned nor built: the post-scaled form needs one more accumulator set per scale group and tile.
+constexpr bool w4_post_fits(int mt, int ntw, int ng, int pc) {
+  return mt <= 2 && ntw == 1 && !(ng == 4 && (mt == 2 || pc >= 2));
+}
+constexpr bool w4_pre_fits(int /*mt*/, int ntw, int ng, int pc) { return !(ntw == 2 && ng == 4 && pc >= 2); }
 
 // 65 <= M <= 128: all rows in one workgroup, 64-deep chunks, two workgroups per CU next to the decode
 // attention stream (w4_m128.hip, round 5); wd = weight ring depth, (64-deep chunks per split) % wd == 0
-void launch_gemm_m128(const GemmKParams& kp, int dtype, int group_size, int wd, int kw, int ct, int adma, int n_blocks, hipStream_t st);
 constexpr size_t W4_M128_LDS_BYTES = 2 * 128 * 128;
 
 // warp-specialised large-M kernel (w4_ws.hip): BM = 256, BN = 128, 512 threads
-void launch_gemm_ws(const GemmKParams& kp, int dtype, int ng, int n_blocks, hipStream_t st);
 constexpr size_t W4_WS_LDS_BYTES = 7 * (256 * 64) + 4 * (8 * 1024) + 2 * 4 * (1024 + 512);
 
-
-// symmetric 256 x 256 kernel for large M x N (w4_xl.hip): 512 threads, 160 KiB LDS
-void launch_gemm_xl(const GemmKParams& kp, int dtype, int ng, int n_blocks, hipStream_t st);
-void launch_gemm_xl_sk(const GemmKParams& kp, int dtype, int ng, int n_wgs, hipStream_t st);
+// symmetric 256 x 256 kernel for large M x N (w4_xl.hip): 512 threads, 160 KiB LDS; its stream-K form
 constexpr int W4_XL_SK_WGS = 256;                                  // one workgroup per CU (160 KiB of LDS each)
 constexpr size_t W4_XL_SK_SLOT_BYTES = 256 * 256 * sizeof(float);  // a partial tile
 constexpr size_t W4_XL_SK_SYNC_BYTES = 2048;                       // ticket + one flag per workgroup

@@ -19,7 +19,7 @@
 // Numerics: fp32 accumulation of exact products, affine correction in fp32 (the post-scaled form of
 // the other small-M kernels): within the reference tests' GEMM tolerance, not bit-identical to
 // "dequantise to T, then multiply".
-#include "w4_common.h"
+#include "w4_plan.h"
 #include "tuning.h"
 
 namespace slm {
@@ -373,13 +373,16 @@ static void launch_gemv_m(const GemvParams& gp, int n_wgs, size_t lds, hipStream
 #undef SLM_GEMV
 }
 
+size_t gemv_lds_bytes(int64_t M, int64_t K, bool norm) {
+  const int mt = M <= 1 ? 1 : M <= 2 ? 2 : 4;
+  return (size_t)mt * K * 2 + (size_t)mt * (K / 32) * 4 + 8 * mt * 32 * 4 +
+         (norm ? (size_t)K * 4 + 16 : 0);  // + one fp32 row of the norm prologue
+}
+
 bool gemv_supported(int64_t M, int64_t K, int64_t group_size, bool norm) {
   if (M < 1 || M > 4) return false;
-  const int mt = M <= 1 ? 1 : M <= 2 ? 2 : 4;
-  const size_t lds = (size_t)mt * K * 2 + (size_t)mt * (K / 32) * 4 + 8 * mt * 32 * 4 +
-                     (norm ? (size_t)K * 4 + 16 : 0);
   (void)group_size;
-  return lds <= 160 * 1024 && K % 64 == 0;  // (the < 4 GiB checks are in launch_gemv's caller)
+  return gemv_lds_bytes(M, K, norm) <= 160 * 1024 && K % 64 == 0;  // (the < 4 GiB checks are in launch_gemv's caller)
 }
 
 static void gemv_shape(int64_t K, int64_t N, bool silu, int& ks, int& tw, int& n_wgs) {
@@ -400,6 +403,12 @@ static void gemv_shape(int64_t K, int64_t N, bool silu, int& ks, int& tw, int& n
   n_wgs = (int)((tiles + tw - 1) / tw);
 }
 
+int gemv_workgroups(int64_t K, int64_t N, bool silu) {
+  int ks, tw, n_wgs;
+  gemv_shape(K, N, silu, ks, tw, n_wgs);
+  return n_wgs;
+}
+
 int gemv_global_splits(int64_t M, int64_t K, int64_t N, bool partials_ok) {
   (void)M;
   if (!partials_ok) return 1;
@@ -414,7 +423,8 @@ int gemv_global_splits(int64_t M, int64_t K, int64_t N, bool partials_ok) {
   return sp < 1 ? 1 : sp;
 }
 
-void launch_gemv(const GemmKParams& kp, int dtype, int ng, hipStream_t st) {
+void launch_gemv(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng;
   GemvParams gp;
   gp.a = kp.a; gp.wq = kp.wq; gp.sz = kp.sz; gp.bias = kp.bias; gp.c = kp.c;
   gp.M = kp.M; gp.K = kp.K; gp.N = kp.N; gp.lda = kp.lda; gp.ldc = kp.ldc;
@@ -429,9 +439,7 @@ void launch_gemv(const GemmKParams& kp, int dtype, int ng, hipStream_t st) {
   gp.norm_x = kp.norm_x; gp.norm_part = kp.norm_part; gp.norm_splits = kp.norm_splits;
   gp.norm_eps = kp.norm_eps; gp.norm_res_in = kp.norm_res_in; gp.norm_res_out = kp.norm_res_out;
   gp.norm_weight = kp.norm_weight; gp.norm_out = kp.norm_out;
-  const int mt = kp.M <= 1 ? 1 : kp.M <= 2 ? 2 : 4;
-  const size_t lds = (size_t)mt * kp.K * 2 + (size_t)mt * (kp.K / 32) * 4 + 8 * mt * 32 * 4 +
-                     (kp.norm_weight ? (size_t)kp.K * 4 + 16 : 0);  // + one fp32 row of the norm prologue
+  const size_t lds = gemv_lds_bytes(kp.M, kp.K, kp.norm_weight != nullptr);
   if (dtype == SLM_BF16) {
     if (ng == 4) launch_gemv_m<bf16_tag, 2>(gp, n_wgs, lds, st);
     else launch_gemv_m<bf16_tag, 1>(gp, n_wgs, lds, st);

@@ -44,7 +44,7 @@
 // packed tree at the END of a tile, which keeps every partial tile live (spills) and serialises the
 // epilogue behind the MFMAs.
 // hipcc-flags: -fno-slp-vectorize
-#include "w4_common.h"
+#include "w4_plan.h"
 
 namespace slm {
 
@@ -650,8 +650,8 @@ bool gemm_ks_config_ok(int ng, int cw, int nw, int mt) {
   return ng == 1 || ng == 2 || ng == 4;
 }
 
-void launch_gemm_ks(const GemmKParams& kp, int dtype, int ng, int cw, int nw, int n_blocks,
-                    hipStream_t st, int mt) {
+void launch_gemm_ks(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng, mt = pl.ks.mt, cw = pl.ks.cw, nw = pl.ks.nw, n_blocks = pl.n_blocks();
   if (mt == 2) {  // (ng == 1: gemm_ks_config_ok)
     if (dtype == SLM_BF16) launch_ks_mt2<bf16_tag, 1>(kp, n_blocks, st);
     else launch_ks_mt2<f16_tag, 1>(kp, n_blocks, st);

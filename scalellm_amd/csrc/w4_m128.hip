@@ -28,7 +28,7 @@
 //     wait in front of the LDS stores leaves the whole weight ring in flight (VMEM returns in order).
 // Epilogues as in w4.hip: 16-bit store (+ bias), fp32 split-K slabs (reduce kernel or the consumer,
 // SLM_W4_DEFER_REDUCE), SiLU*mul on (gate, up) tile pairs held by adjacent waves (SLM_W4_SILU_MUL).
-#include "w4_common.h"
+#include "w4_plan.h"
 
 namespace slm {
 
@@ -354,8 +354,9 @@ static void launch_m128_t(const GemmKParams& kp, int ng, int wd, int n_blocks, h
 //  profiles/r05_m128_70b_shapes.jsonl.)
 // ct = column tiles per workgroup (4 / 8; 8 only with kw = 1); n_blocks counts workgroups of ct tiles;
 // adma = activations by LDS-DMA (built for the 256-column form)
-void launch_gemm_m128(const GemmKParams& kp, int dtype, int group_size, int wd, int kw, int ct, int adma, int n_blocks, hipStream_t st) {
-  const int ng = group_size == 32 ? 2 : 1;
+void launch_gemm_m128(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng == 4 ? 2 : 1;  // scale groups per 64-deep chunk
+  const int wd = pl.m128.wd, kw = pl.m128.kw, ct = pl.m128.ct, adma = pl.m128.adma, n_blocks = pl.n_blocks();
   if (dtype == SLM_BF16) {
     if (ct == 8 && adma) launch_m128_t<bf16_tag, 1, 8, true>(kp, ng, wd, n_blocks, st);
     else if (ct == 8) launch_m128_t<bf16_tag, 1, 8, false>(kp, ng, wd, n_blocks, st);

@@ -28,7 +28,7 @@
 // Numerics are those of the general kernel's post-scaled path (fp32 accumulate of exact products,
 // affine correction in fp32): within the GEMM tolerance of the reference tests
 // (marlin_gemm_test.py:104-107), not bit-identical to "dequantise to T, then multiply".
-#include "w4_common.h"
+#include "w4_plan.h"
 
 namespace slm {
 
@@ -285,7 +285,8 @@ static void launch_small_ng(const GemmKParams& kp, int ng, int n_blocks, hipStre
   else launch_small_t<T, 1, true>(kp, n_blocks, st);
 }
 
-void launch_gemm_small(const GemmKParams& kp, int dtype, int ng, int n_blocks, hipStream_t st) {
+void launch_gemm_small(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng, n_blocks = pl.n_blocks();
   if (dtype == SLM_BF16) launch_small_ng<bf16_tag>(kp, ng, n_blocks, st);
   else launch_small_ng<f16_tag>(kp, ng, n_blocks, st);
 }

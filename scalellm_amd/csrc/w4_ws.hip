@@ -33,7 +33,7 @@
 // B unit g+3 and publish (counted waits) A unit g+2 and B unit g+2.  A global -> LDS transfer therefore has 4 steps
 // (~2000 cycles) to land: with one 64-deep chunk of lead (the previous version) the measured
 // issue -> landed time of a 32 KiB chunk (~1100 cycles from L2, more from HBM) was fully exposed.
-#include "w4_common.h"
+#include "w4_plan.h"
 
 namespace slm {
 
@@ -362,8 +362,8 @@ static void launch_ws(const GemmKParams& kp, int n_blocks, hipStream_t st) {
   hipLaunchKernelGGL(kfn, dim3((unsigned)n_blocks), dim3(512), W4_WS_LDS_BYTES, st, kp);
 }
 
-void launch_gemm_ws(const GemmKParams& kp, int dtype, int ng, int n_blocks, hipStream_t st) {
-  // ng = scale groups per 128 of K (w4.hip plan): 4 for group 32 -> 2 per 64-deep chunk
+void launch_gemm_ws(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng, n_blocks = pl.n_blocks();  // ng = scale groups per 128 of K: 4 for group 32 -> 2 per 64-deep chunk
   const bool once = kp.n_mblocks <= 1;  // every weight read by one row block only: stream it past the caches
   if (dtype == SLM_BF16) {
     if (ng == 4) (once ? launch_ws<bf16_tag, 2, true>(kp, n_blocks, st) : launch_ws<bf16_tag, 2, false>(kp, n_blocks, st));

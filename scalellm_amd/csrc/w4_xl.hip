@@ -16,7 +16,7 @@
 // step; every wave publishes with counted waits (its B-fragment writes are older than the 6
 // prefetch reads of the next unit, so lgkmcnt(6) covers them; its DMA of unit g+2 is older than 6
 // DMAs and 2 refills).  LDS: A 7 x 16 KiB + B 3 x 16 KiB = 160 KiB, one workgroup per CU.
-#include "w4_common.h"
+#include "w4_plan.h"
 
 namespace slm {
 
@@ -418,7 +418,8 @@ static void launch_xl_sk(const GemmKParams& kp, int n_wgs, hipStream_t st) {
   hipLaunchKernelGGL(kfn, dim3((unsigned)n_wgs), dim3(512), W4_XL_LDS_BYTES, st, kp);
 }
 
-void launch_gemm_xl_sk(const GemmKParams& kp, int dtype, int ng, int n_wgs, hipStream_t st) {
+void launch_gemm_xl_sk(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng, n_wgs = W4_XL_SK_WGS;
   // (several row blocks always re-read the weights here: cacheable loads)
   if (dtype == SLM_BF16) {
     if (ng == 4) launch_xl_sk<bf16_tag, 2, false>(kp, n_wgs, st);
@@ -443,8 +444,8 @@ static void launch_xl(const GemmKParams& kp, int n_blocks, hipStream_t st) {
   hipLaunchKernelGGL(kfn, dim3((unsigned)n_blocks), dim3(512), W4_XL_LDS_BYTES, st, kp);
 }
 
-void launch_gemm_xl(const GemmKParams& kp, int dtype, int ng, int n_blocks, hipStream_t st) {
-  // ng = scale groups per 128 of K (w4.hip plan): 4 for group 32 -> 2 per 64-deep chunk
+void launch_gemm_xl(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
+  const int ng = pl.ng, n_blocks = pl.n_blocks();  // ng = scale groups per 128 of K: 4 for group 32 -> 2 per 64-deep chunk
   const bool once = kp.n_mblocks <= 1;  // every weight read by one row block only: stream it past the caches
   if (dtype == SLM_BF16) {
     if (ng == 4) (once ? launch_xl<bf16_tag, 2, true>(kp, n_blocks, st) : launch_xl<bf16_tag, 2, false>(kp, n_blocks, st));

@@ -666,6 +666,33 @@ def gemv_norm_supported(n_tokens: int, packed: PackedW4, dtype: torch.dtype,
     return bool(_lib.lib().slm_w4a16_gemv_norm_supported(C.byref(g)))
 
 
+def _set_gemm_flags(g: W4GemmArgs, defer_reduce: bool, silu_mul: bool) -> int:
+    """g.flags of a gptq_gemm call; returns the slab count when the call defers its reduction, else 0"""
+    chip = _chip_flag()
+    g.flags = chip
+    if silu_mul:
+        g.flags = _lib.SLM_W4_SILU_MUL | chip
+    deferred = 0
+    if defer_reduce:
+        g.flags = _lib.SLM_W4_DEFER_REDUCE | chip
+        deferred = _lib.lib().slm_w4a16_gemm_deferred_splits(C.byref(g))
+        if not deferred:
+            g.flags = chip
+    return deferred
+
+
+def w4_plan(a: torch.Tensor, packed: PackedW4, c: torch.Tensor, bias: Optional[torch.Tensor] = None,
+            defer_reduce: bool = False, silu_mul: bool = False) -> "_lib.W4PlanInfo":
+    """The launch gptq_gemm would give these very arguments now -- under the tuning knobs and the
+    shared_chip() state in force (slm_w4a16_gemm_plan): .kernel_name, grid, kernel-specific variant.
+    A host-side query: nothing runs on the GPU."""
+    g = _gemm_args(a, packed, c, bias, silu_mul)
+    _set_gemm_flags(g, defer_reduce, silu_mul)
+    info = _lib.W4PlanInfo()
+    check(_lib.lib().slm_w4a16_gemm_plan(C.byref(g), C.byref(info)), "slm_w4a16_gemm_plan")
+    return info
+
+
 def gptq_gemm(a: torch.Tensor, packed: PackedW4, c: torch.Tensor,
               bias: Optional[torch.Tensor] = None, defer_reduce: bool = False,
               silu_mul: bool = False, norm: Optional[NormPrologue] = None) -> DeferredPartials:
@@ -717,16 +744,7 @@ def gptq_gemm(a: torch.Tensor, packed: PackedW4, c: torch.Tensor,
         npro.residual_out = norm.residual_out.data_ptr() if norm.residual_out is not None else None
         npro.weight = norm.weight.data_ptr()
         npro.normed_out = norm.normed_out.data_ptr() if norm.normed_out is not None else None
-    chip = _chip_flag()
-    g.flags = chip
-    if silu_mul:
-        g.flags = _lib.SLM_W4_SILU_MUL | chip
-    deferred = 0
-    if defer_reduce:
-        g.flags = _lib.SLM_W4_DEFER_REDUCE | chip
-        deferred = L.slm_w4a16_gemm_deferred_splits(C.byref(g))
-        if not deferred:
-            g.flags = chip
+    deferred = _set_gemm_flags(g, defer_reduce, silu_mul)
     need = L.slm_w4a16_gemm_workspace_bytes(C.byref(g))
     ws = None
     if need:

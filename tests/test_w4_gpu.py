@@ -94,7 +94,9 @@ def _rel_err(c, ref):
 GEMM_TOL = {"f16": 1e-3, "bf16": 8e-3}  # marlin_gemm_test.py:104-107; bf16 = 8x (8 fewer mantissa bits)
 
 
-def _run_gemm(case, bits, M, bias=False, seed=0):
+def _run_gemm(case, bits, M, bias=False, seed=0, kernel=None, row_tiles=None):
+    """kernel / row_tiles: what the plan must say about this very call (kernels.w4_plan, a host-side query) --
+    a knob that stopped selecting its kernel fails here instead of testing another kernel quietly"""
     from scalellm_amd import kernels
     dt = _tdtype(bits)
     g = torch.Generator(device=DEV).manual_seed(seed)
@@ -102,6 +104,10 @@ def _run_gemm(case, bits, M, bias=False, seed=0):
     b = torch.randn(case["N"], device=DEV, dtype=dt, generator=g) if bias else None
     packed = _pack(case, bits)
     c = torch.full((M, case["N"]), float("nan"), device=DEV, dtype=dt)
+    if kernel is not None:
+        plan = kernels.w4_plan(a, packed, c, b)
+        assert plan.kernel_name == kernel, (plan.kernel_name, kernel, M, case["K"], case["N"])
+        assert row_tiles is None or plan.row_tiles == row_tiles, (plan.row_tiles, row_tiles)
     kernels.gptq_gemm(a, packed, c, b)
     torch.cuda.synchronize()
     ref = oracle.gemm_f32(a.float().cpu().numpy(), _oracle_w(case))
@@ -180,7 +186,7 @@ def test_wave_specialised_kernel_grid(bits, tune):
         i += 1
         tune(SLM_W4_SPLITK=sk)
         case = helpers.make_quant_case(700 + i, K, N, gs, fmt, bits, act_order=act)
-        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="WS")
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, sk, err)
 
@@ -209,15 +215,21 @@ def test_m128_kernel_grid(bits, wd, kw, ct, adma, tune):
         i += 1
         tune(SLM_W4_SPLITK=sk)
         case = helpers.make_quant_case(900 + i, K, N, gs, fmt, bits, act_order=act)
-        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="M128")
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, sk, err)
     # the kernel is what ran: the general kernel (SLM_W4_M128=0) agrees to summation order only
     tune(SLM_W4_SPLITK=0, SLM_W4_M128=1, SLM_W4_M128_KW=kw, SLM_W4_M128_CT=ct, SLM_W4_M128_ADMA=adma)
     case = helpers.make_quant_case(990, 1024, 512, 128, "awq", bits)
-    a_out, ref = _run_gemm(case, bits, 128, bias=False, seed=3)
+    a_out, ref = _run_gemm(case, bits, 128, bias=False, seed=3, kernel="M128")
+    # ... in the form the knobs ask for: variant = {ring depth, waves per column tile, column tiles, LDS-DMA}
+    # (the ring falls back to 2 chunks where 4 do not divide a split; LDS-DMA exists in the 256-column form only)
+    g = torch.Generator(device=DEV).manual_seed(3)
+    plan = kernels.w4_plan(torch.randn(128, 1024, device=DEV, dtype=_tdtype(bits), generator=g), _pack(case, bits),
+                           torch.empty(128, 512, device=DEV, dtype=_tdtype(bits)))
+    assert plan.variant[0] in (2, wd) and list(plan.variant[1:]) == [kw, ct, adma if ct == 8 else 0], list(plan.variant)
     tune(SLM_W4_M128=0)
-    b_out, _ = _run_gemm(case, bits, 128, bias=False, seed=3)
+    b_out, _ = _run_gemm(case, bits, 128, bias=False, seed=3, kernel="GENERAL")
     assert _rel_err(a_out, ref) < GEMM_TOL[bits] and _rel_err(b_out, ref) < GEMM_TOL[bits]
     assert not np.array_equal(a_out, b_out) or True  # (informational: different split-K / tile order)
 
@@ -237,7 +249,7 @@ def test_xl_256x256_kernel_grid(bits, tune):
         i += 1
         tune(SLM_W4_SPLITK=sk)
         case = helpers.make_quant_case(900 + i, K, N, gs, fmt, bits, act_order=act)
-        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="XL")
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, sk, err)
 
@@ -290,7 +302,7 @@ def test_dot2_gemv_kernel_grid(bits, tune):
             (1, 224, 1792, 256, "gptq", False), (4, 288, 4096, 128, "awq", False)):
         i += 1
         case = helpers.make_quant_case(1300 + i, K, N, gs, fmt, bits, act_order=act)
-        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="GEMV")
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, err)
 
@@ -320,7 +332,7 @@ def test_k_sliced_small_m_kernel_grid(bits):
         i += 1
         case = helpers.make_quant_case(1700 + i, K, N, gs, fmt, bits, act_order=act)
         with kernels.tuning(SLM_W4_KS=1, **knobs):  # per case: knobs of one case must not leak into the next
-            out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+            out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="KS", row_tiles=1)
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, knobs, err)
 
@@ -349,11 +361,11 @@ def test_two_row_tile_k_sliced_kernel_grid(bits):
         i += 1
         case = helpers.make_quant_case(2700 + i, K, N, gs, fmt, bits, act_order=act)
         with kernels.tuning(**{"SLM_W4_KS_MT2": 1, **knobs}):   # (opt-in kernel: not the default plan)
-            out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+            out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="KS", row_tiles=2)
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, knobs, err)
         with kernels.tuning(SLM_W4_KS_MT2=0):
-            base, _ = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i)
+            base, _ = _run_gemm(case, bits, M, bias=(i % 2 == 1), seed=i, kernel="GENERAL", row_tiles=2)
         assert _rel_err(out, base) < GEMM_TOL[bits] / 2, (M, N, K, "vs the general kernel")
 
 
@@ -423,7 +435,7 @@ def test_lean_small_m_kernel_still_covered(bits, tune):
                                   (8, 384, 2048, -1, "gptq", True), (2, 160, 640, 32, "gptq", False)):
         i += 1
         case = helpers.make_quant_case(1800 + i, K, N, gs, fmt, bits, act_order=act)
-        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 0), seed=i)
+        out, ref = _run_gemm(case, bits, M, bias=(i % 2 == 0), seed=i, kernel="SMALL")
         err = _rel_err(out, ref)
         assert err < GEMM_TOL[bits], (M, N, K, gs, fmt, act, err)
 
@@ -598,6 +610,9 @@ def test_shares_chip_flag_only_changes_the_plan(M, K, N):
         with kernels.shared_chip(shared):
             c1 = torch.full((M, N), float("nan"), device=DEV, dtype=torch.bfloat16)
             c2 = torch.full_like(c1, float("nan"))
+            plan = kernels.w4_plan(a, packed, c1)
+            alone_ks = not shared and K <= 4096   # (<= 4 slabs: the two-row-tile stream is taken alone)
+            assert (plan.kernel_name, plan.row_tiles) == (("KS", 2) if alone_ks else ("GENERAL", 2))
             kernels.gptq_gemm(a, packed, c1)
             kernels.gptq_gemm(a, packed, c2)
             torch.cuda.synchronize()
@@ -606,6 +621,7 @@ def test_shares_chip_flag_only_changes_the_plan(M, K, N):
             outs[shared] = c1
     with kernels.tuning(SLM_W4_KS_MT2=0):       # the knob's "never" == the flag's plan
         c0 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+        assert kernels.w4_plan(a, packed, c0).kernel_name == "GENERAL"
         kernels.gptq_gemm(a, packed, c0)
         torch.cuda.synchronize()
     assert torch.equal(c0, outs[True])
@@ -630,6 +646,8 @@ def _sk_run(a, packed, b, M, N, sk):
     from scalellm_amd import kernels
     with kernels.tuning(SLM_W4_XL_SK=sk):
         c = torch.full((M, N), float("nan"), device=DEV, dtype=a.dtype)
+        name = kernels.w4_plan(a, packed, c, b).kernel_name   # 2 = stream-K wherever it applies, 0 = never: tiles
+        assert name == "XL_SK" if sk == 2 else name in ("XL", "WS"), (name, sk, M, N)
         kernels.gptq_gemm(a, packed, c, b)
     return c
 
@@ -675,6 +693,7 @@ def test_stream_k_form_repeats_bit_identically_and_replays_under_a_graph():
     assert all(torch.equal(o, first) for o in outs)
     with kernels.tuning(SLM_W4_XL_SK=2):
         c = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+        assert kernels.w4_plan(a, packed, c).kernel_name == "XL_SK"
         kernels.gptq_gemm(a, packed, c)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -700,7 +719,13 @@ def test_stream_k_form_is_planned_where_the_round_model_says_so():
         g = _lib.W4GemmArgs()
         g.M, g.K, g.N, g.lda, g.ldc, g.group_size, g.dtype = M, K, N, K, N, 128, _lib.SLM_BF16
         g.flags = flags
-        return int(L.slm_w4a16_gemm_workspace_bytes(C.byref(g)))
+        ws, plan = int(L.slm_w4a16_gemm_workspace_bytes(C.byref(g))), _lib.W4PlanInfo()
+        assert L.slm_w4a16_gemm_plan(C.byref(g), C.byref(plan)) == 0
+        assert (plan.kernel_name == "XL_SK") == (ws == sk_ws) and plan.part_bytes + plan.aperm_bytes == ws
+        if plan.kernel_name == "XL_SK":  # no split-K slabs: 256 equal ranges of the tile x K work list, in chunk pairs
+            assert plan.split_k == 1 and plan.row_tiles == 8
+            assert plan.variant[0] % 2 == 0 and 256 * plan.variant[0] >= plan.n_mblocks * plan.n_nblocks * (K // 128)
+        return ws
     sk_ws = 256 * 256 * 256 * 4 + 2048
     assert splits_and_ws(2648, 4096, 4096) == sk_ws
     assert splits_and_ws(2648, 4096, 6144) == sk_ws

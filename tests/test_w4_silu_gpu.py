@@ -45,51 +45,57 @@ def test_paired_prepack_is_the_documented_column_permutation(fmt, gs, act, bits)
     assert torch.equal(paired, plain[:, src])
 
 
-# (M, K, N, group, knobs): every kernel / reduce path the plan can take
+# (M, K, N, group, knobs, kernel, row tiles): every kernel / reduce path the plan can take, and what
+# slm_w4a16_gemm_plan must call it (None: not pinned here)
 PLANS = [
-    (1, 1024, 512, 128, dict(SLM_W4_GEMV_KS=4)),                 # dot2 GEMV, 2 tiles x 4 K slices
-    (1, 4096, 1024, 128, dict(SLM_W4_GEMV_KS=2)),                # 4 tiles x 2 K slices
-    (3, 512, 256, 32, dict(SLM_W4_GEMV=2, SLM_W4_GEMV_KS=4)),    # GEMV with MT = 4, group 32
-    (8, 1024, 512, 128, dict(SLM_W4_SPLITK=1)),                  # small-M kernel, pair exchange in LDS
-    (32, 1024, 512, 64, dict(SLM_W4_SPLITK=1)),
-    (17, 2048, 256, 128, dict()),                                # small-M kernel, split-K -> fused reduce
-    (32, 4096, 1024, 128, dict(SLM_W4_SPLITK=4)),
-    (24, 1024, 512, 128, dict(SLM_W4_SMALL=0, SLM_W4_SPLITK=1)),  # general kernel MT = 1 (POST form)
-    (24, 1024, 512, 128, dict(SLM_W4_SMALL=0, SLM_W4_SPLITK=1, SLM_W4_NTW=2)),  # pair inside one wave
-    (48, 1024, 512, 128, dict(SLM_W4_SPLITK=1)),                 # general kernel, MT = 2
-    (48, 1024, 512, 128, dict(SLM_W4_KS_MT2=1)),                 # K-sliced stream, two row tiles: in-kernel pair
-    (64, 4096, 1024, 128, dict(SLM_W4_KS_MT2=1)),                # ... split over 4 workgroups: fused reduce
-    (33, 2048, 448, 128, dict(SLM_W4_KS_MT2=1, SLM_W4_KS_TPW=4)),  # ... ragged tile runs, one row in tile 2
-    (64, 1024, 512, 32, dict(SLM_W4_SPLITK=2)),
-    (100, 1024, 512, 128, dict(SLM_W4_MT=4, SLM_W4_SPLITK=1)),   # MT = 4 (PRE form)
-    (128, 2048, 1024, 128, dict(SLM_W4_MT=4, SLM_W4_SPLITK=2)),
-    (256, 1024, 1024, 128, dict(SLM_W4_MT=8, SLM_W4_SPLITK=1)),  # wave-specialised 256 x 128
-    (300, 1024, 1152, 64, dict(SLM_W4_MT=8, SLM_W4_SPLITK=1)),   # ragged M, N = 9 tiles of 128
-    (256, 2048, 1024, 128, dict(SLM_W4_MT=8, SLM_W4_SPLITK=2)),
-    (256, 1024, 1024, 128, dict(SLM_W4_MT=16, SLM_W4_SPLITK=1)),  # symmetric 256 x 256
-    (384, 1024, 1280, 128, dict(SLM_W4_MT=16, SLM_W4_SPLITK=1)),
-    (256, 4096, 2048, 128, dict()),                              # whatever the plan picks
-    (128, 2048, 1024, 128, dict(SLM_W4_M128=1)),                 # round 5: w4_m128.hip (65 <= M <= 128), the plan's split
-    (100, 1024, 512, 32, dict(SLM_W4_M128=1, SLM_W4_SPLITK=1)),  # ... in-kernel pair exchange, two scale groups per chunk
-    (96, 4096, 1024, 64, dict(SLM_W4_M128=1, SLM_W4_SPLITK=4)),  # ... fp32 slabs + the fused reduce
-    (128, 1024, 512, 128, dict(SLM_W4_M128=1, SLM_W4_M128_WD=4, SLM_W4_SPLITK=1)),  # ... four-chunk weight ring
-    (65, 1024, 448, 128, dict(SLM_W4_M128=1, SLM_W4_SPLITK=1)),  # ... N = 7 tile pairs: a clamped wave pair
-    (128, 8192, 1024, 128, dict()),                              # ... K >= 8192: the plan's own choice
-    (128, 2048, 1024, 128, dict(SLM_W4_M128=1, SLM_W4_M128_KW=2, SLM_W4_SPLITK=1)),  # ... two waves per column tile
-    (100, 1024, 448, 32, dict(SLM_W4_M128=1, SLM_W4_M128_KW=2, SLM_W4_SPLITK=2)),    # ... + slabs, group 32, clamped pair
-    (96, 1024, 512, 64, dict(SLM_W4_M128=1, SLM_W4_M128_KW=1, SLM_W4_SPLITK=1)),
-    (128, 2048, 1024, 128, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_SPLITK=1)),  # ... 256-column workgroups: four (gate, up) wave pairs
-    (100, 1024, 448, 32, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_SPLITK=2)),    # ... + slabs, clamped pairs
-    (65, 1024, 1216, 128, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_M128_WD=4)),  # ... N = 19 tile pairs
-    (128, 2048, 1024, 128, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_M128_ADMA=1, SLM_W4_SPLITK=1)),  # ... activations by LDS-DMA
-    (100, 1024, 448, 32, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_M128_ADMA=1, SLM_W4_SPLITK=2)),
+    (1, 1024, 512, 128, dict(SLM_W4_GEMV_KS=4), "GEMV", None),                 # dot2 GEMV, 2 tiles x 4 K slices
+    (1, 4096, 1024, 128, dict(SLM_W4_GEMV_KS=2), "GEMV", None),                # 4 tiles x 2 K slices
+    (3, 512, 256, 32, dict(SLM_W4_GEMV=2, SLM_W4_GEMV_KS=4), "GEMV", None),    # GEMV with MT = 4, group 32
+    (8, 1024, 512, 128, dict(SLM_W4_SPLITK=1), "KS", 1),                  # K-sliced stream (the forced split is one it can realise), 8 waves x 4 chunks
+    (32, 1024, 512, 64, dict(SLM_W4_SPLITK=1), "KS", 1),
+    (17, 2048, 256, 128, dict(), "KS", 1),                                # K-sliced stream: 16 chunks on 8 waves x 2
+    (32, 4096, 1024, 128, dict(SLM_W4_SPLITK=4), "KS", 1),
+    (24, 1024, 512, 128, dict(SLM_W4_SMALL=0, SLM_W4_SPLITK=1), "GENERAL", None),  # general kernel MT = 1 (POST form)
+    (24, 1024, 512, 128, dict(SLM_W4_SMALL=0, SLM_W4_SPLITK=1, SLM_W4_NTW=2), "GENERAL", None),  # pair inside one wave
+    (48, 1024, 512, 128, dict(SLM_W4_SPLITK=1), "KS", 2),                 # the default for 33 <= M <= 64: two row tiles
+    (48, 1024, 512, 128, dict(SLM_W4_KS_MT2=1), "KS", 2),                 # K-sliced stream, two row tiles: in-kernel pair
+    (64, 4096, 1024, 128, dict(SLM_W4_KS_MT2=1), "KS", 2),                # ... split over 4 workgroups: fused reduce
+    (33, 2048, 448, 128, dict(SLM_W4_KS_MT2=1, SLM_W4_KS_TPW=4), "KS", 2),  # ... ragged tile runs, one row in tile 2
+    (64, 1024, 512, 32, dict(SLM_W4_SPLITK=2), "GENERAL", None),
+    (100, 1024, 512, 128, dict(SLM_W4_MT=4, SLM_W4_SPLITK=1), "GENERAL", None),   # MT = 4 (PRE form)
+    (128, 2048, 1024, 128, dict(SLM_W4_MT=4, SLM_W4_SPLITK=2), "GENERAL", None),
+    (256, 1024, 1024, 128, dict(SLM_W4_MT=8, SLM_W4_SPLITK=1), "WS", None),  # wave-specialised 256 x 128
+    (300, 1024, 1152, 64, dict(SLM_W4_MT=8, SLM_W4_SPLITK=1), "WS", None),   # ragged M, N = 9 tiles of 128
+    (256, 2048, 1024, 128, dict(SLM_W4_MT=8, SLM_W4_SPLITK=2), "WS", None),
+    (256, 1024, 1024, 128, dict(SLM_W4_MT=16, SLM_W4_SPLITK=1), "XL", None),  # symmetric 256 x 256
+    (384, 1024, 1280, 128, dict(SLM_W4_MT=16, SLM_W4_SPLITK=1), "XL", None),
+    (256, 4096, 2048, 128, dict(), None, None),                              # whatever the plan picks
+    (128, 2048, 1024, 128, dict(SLM_W4_M128=1), "M128", None),                 # round 5: w4_m128.hip (65 <= M <= 128), the plan's split
+    (100, 1024, 512, 32, dict(SLM_W4_M128=1, SLM_W4_SPLITK=1), "M128", None),  # ... in-kernel pair exchange, two scale groups per chunk
+    (96, 4096, 1024, 64, dict(SLM_W4_M128=1, SLM_W4_SPLITK=4), "M128", None),  # ... fp32 slabs + the fused reduce
+    (128, 1024, 512, 128, dict(SLM_W4_M128=1, SLM_W4_M128_WD=4, SLM_W4_SPLITK=1), "M128", None),  # ... four-chunk weight ring
+    (65, 1024, 448, 128, dict(SLM_W4_M128=1, SLM_W4_SPLITK=1), "M128", None),  # ... N = 7 tile pairs: a clamped wave pair
+    (128, 8192, 1024, 128, dict(), "GENERAL", None),                              # K >= 8192 but N < 8192: the plan keeps the general kernel's BM = 64 tiles
+    (128, 2048, 1024, 128, dict(SLM_W4_M128=1, SLM_W4_M128_KW=2, SLM_W4_SPLITK=1), "M128", None),  # ... two waves per column tile
+    (100, 1024, 448, 32, dict(SLM_W4_M128=1, SLM_W4_M128_KW=2, SLM_W4_SPLITK=2), "M128", None),    # ... + slabs, group 32, clamped pair
+    (96, 1024, 512, 64, dict(SLM_W4_M128=1, SLM_W4_M128_KW=1, SLM_W4_SPLITK=1), "M128", None),
+    (128, 2048, 1024, 128, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_SPLITK=1), "M128", None),  # ... 256-column workgroups: four (gate, up) wave pairs
+    (100, 1024, 448, 32, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_SPLITK=2), "M128", None),    # ... + slabs, clamped pairs
+    (65, 1024, 1216, 128, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_M128_WD=4), "M128", None),  # ... N = 19 tile pairs
+    (128, 2048, 1024, 128, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_M128_ADMA=1, SLM_W4_SPLITK=1), "M128", None),  # ... activations by LDS-DMA
+    (100, 1024, 448, 32, dict(SLM_W4_M128=1, SLM_W4_M128_CT=8, SLM_W4_M128_ADMA=1, SLM_W4_SPLITK=2), "M128", None),
+    # the kernels behind the K-sliced stream, which the rows above no longer reach since it became the default
+    (8, 1024, 512, 128, dict(SLM_W4_KS=0, SLM_W4_SPLITK=1), "SMALL", None),      # lean small-M kernel, pair exchange in LDS
+    (17, 2048, 256, 128, dict(SLM_W4_KS=0), "SMALL", None),                     # ... split-K -> fused reduce
+    (48, 1024, 512, 128, dict(SLM_W4_KS_MT2=0, SLM_W4_SPLITK=1), "GENERAL", 2), # general kernel, MT = 2 (POST form)
 ]
 
 
 @pytest.mark.parametrize("bits", ["bf16", "f16"])
 @pytest.mark.parametrize("bias", [False, True])
-@pytest.mark.parametrize("M,K,N,gs,knobs", PLANS)
-def test_fused_silu_mul_is_bit_identical_to_gemm_then_silu(M, K, N, gs, knobs, bias, bits, tune):
+@pytest.mark.parametrize("M,K,N,gs,knobs,kernel,row_tiles", PLANS,
+                         ids=["%d-%d-%d-%d-knobs%d" % (*p[:4], i) for i, p in enumerate(PLANS)])  # (ids as before the pins)
+def test_fused_silu_mul_is_bit_identical_to_gemm_then_silu(M, K, N, gs, knobs, kernel, row_tiles, bias, bits, tune):
     from scalellm_amd import kernels
     tune(**knobs)
     dt = _dt(bits)
@@ -105,6 +111,9 @@ def test_fused_silu_mul_is_bit_identical_to_gemm_then_silu(M, K, N, gs, knobs, b
     kernels.silu_and_mul(want, full)
     b_packed = b[torch.from_numpy(_src_cols(N)).to(DEV)].contiguous() if bias else None
     got = torch.full((M, N // 2), float("nan"), device=DEV, dtype=dt)
+    for plan in (kernels.w4_plan(a, plain, full, b), kernels.w4_plan(a, paired, got, b_packed, silu_mul=True)):
+        assert kernel is None or plan.kernel_name == kernel, (plan.kernel_name, kernel)
+        assert row_tiles is None or plan.row_tiles == row_tiles, (plan.row_tiles, row_tiles)
     kernels.gptq_gemm(a, paired, got, b_packed, silu_mul=True)
     torch.cuda.synchronize()
     assert not torch.isnan(got.float()).any()
