@@ -916,6 +916,83 @@ typedef struct slm_moe_gemm_args {
 } slm_moe_gemm_args;
 SLM_API int slm_moe_w4a16_gemm(const slm_moe_gemm_args* a, void* stream);
 
+/* ========================================================================== */
+/* 11. Multi-head latent attention (MLA) over a paged latent KV cache         */
+/*    mirrors   the reference's MLA kernel family                             */
+/*              src/kernels/attention/mla_params.h (MLAPagedKVParams),        */
+/*              device/sm80_mla_dispatch.cuh; semantics tests/mla_ref.h:      */
+/*      S[q,k]     = sm_scale (q[q,h,:] . kv[k,:] + q_rope[q,h,:] . k_rope[k,:]) */
+/*      S[q,k]     = -inf where k > q + (kv_len_b - q_len_b)                  */
+/*      out[q,h,:] = softmax_k(S[q,:]) . kv[:, :]   (V IS the latent row)     */
+/*    ONE latent row and one RoPE key per token, shared by all heads; both    */
+/*    caches paged exactly as in section 1 (same block table for both).       */
+/*    One entry point for decode, prefill, chunked prefill and verify.        */
+/*    f16 / bf16; head_dim 128, 256 or 512; rope_head_dim 64; any n_heads >=  */
+/*    1; block_size any power of two.  No soft-cap, alibi or sliding window   */
+/*    (the reference's MLA has none).  Hints as in section 1: max_q_len       */
+/*    bounds the query rows per sequence and sizes the grid; max_kv_len only  */
+/*    sizes the KV splits -- results are correct for any value.  Lengths and  */
+/*    tables are read on the device only, so a captured graph replays over    */
+/*    changed ones.  A pure-decode call may carry more rows than              */
+/*    q_cu_lens[batch] (graph padding): they are left untouched.              */
+/*    Split-KV goes through the caller's workspace (fp32 partials, merged in  */
+/*    split order by a combine pass: no atomics, repeats are bit-identical).  */
+/*    Checked before any launch: null pointer / block_size not a power of two */
+/*    -> SLM_ERR_INVALID_ARG; other head_dim / rope_head_dim / dtype ->       */
+/*    SLM_ERR_UNSUPPORTED; a base or stride that is not 16-byte aligned ->    */
+/*    SLM_ERR_ALIGNMENT; workspace missing or short -> SLM_ERR_WORKSPACE.     */
+/*    batch_size == 0 or n_tokens == 0: SLM_OK without a launch.              */
+/* ========================================================================== */
+typedef struct slm_mla_args {
+  void* out;                 /* [n_tokens, n_heads, head_dim]                  */
+  const void* q;             /* [n_tokens, n_heads, head_dim]                  */
+  const void* q_rope;        /* [n_tokens, n_heads, rope_head_dim]             */
+  const void* kv_cache;      /* [n_slots, head_dim]                            */
+  const void* k_rope_cache;  /* [n_slots, rope_head_dim]                       */
+  int64_t o_stride[2];       /* {token stride, head stride} in elements        */
+  int64_t q_stride[2];
+  int64_t q_rope_stride[2];
+  int64_t kv_stride;         /* slot stride of kv_cache in elements            */
+  int64_t k_rope_stride;     /* slot stride of k_rope_cache                    */
+  const int32_t* q_cu_lens;      /* [batch+1]                                  */
+  const int32_t* kv_cu_lens;     /* [batch+1]                                  */
+  const int32_t* block_table;    /* [sum_b ceil(kv_len_b / block_size)]        */
+  const int32_t* block_cu_lens;  /* [batch+1]                                  */
+  int32_t dtype;             /* slm_dtype of out / q / q_rope / caches         */
+  int32_t batch_size;
+  int32_t n_tokens;          /* rows of out / q / q_rope (>= q_cu_lens[batch]) */
+  int32_t n_heads;
+  int32_t head_dim;          /* width of the latent row: 128, 256 or 512       */
+  int32_t rope_head_dim;     /* 64                                             */
+  int32_t block_size;        /* power of two                                   */
+  int32_t max_q_len;         /* scheduling hint, as in section 1               */
+  int32_t max_kv_len;        /* scheduling hint: sizes the KV splits only      */
+  float sm_scale;
+  void* workspace;           /* split-KV scratch, may be NULL if bytes == 0    */
+  size_t workspace_bytes;
+  int32_t num_splits;        /* 0 = auto (heuristic); > 0 forces the split count */
+  int32_t reserved;
+} slm_mla_args;
+
+/* Scratch needed for `a` (host-side sizes only; 0 without a KV split).  Pass num_splits to query a
+ * forced split count. */
+SLM_API size_t slm_mla_paged_kv_workspace_bytes(const slm_mla_args* a);
+/* Split count the heuristic picks for `a` (host-side sizes only): 1 once the batch alone gives every
+ * CU a workgroup. */
+SLM_API int32_t slm_mla_paged_kv_auto_splits(const slm_mla_args* a);
+SLM_API int slm_mla_paged_kv(const slm_mla_args* a, void* stream);
+
+/* Latent cache append: kv_cache[slot_ids[t], :] = kv[t, :] and k_rope_cache[slot_ids[t], :] = k_rope[t, :]
+ * in one launch (bit-exact copy; strides in elements, all 16-byte aligned; head_dim and rope_head_dim
+ * multiples of 8).  A row whose slot id is negative (graph padding) is skipped; every other id must be a
+ * valid slot of both caches. */
+SLM_API int slm_mla_set_kv_cache(const int32_t* slot_ids /* [n_tokens] */, const void* kv /* [n_tokens, head_dim] */,
+                                 const void* k_rope /* [n_tokens, rope_head_dim] */, int64_t kv_token_stride,
+                                 int64_t k_rope_token_stride, void* kv_cache /* [n_slots, head_dim] */,
+                                 void* k_rope_cache /* [n_slots, rope_head_dim] */, int64_t kv_slot_stride,
+                                 int64_t k_rope_slot_stride, int64_t n_tokens, int32_t head_dim,
+                                 int32_t rope_head_dim, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,23 @@ class MoeGemmArgs(C.Structure):
     ]
 
 
+class MlaArgs(C.Structure):
+    """struct slm_mla_args (include/slm_hip.h section 11)."""
+    _fields_ = [
+        ("out", C.c_void_p), ("q", C.c_void_p), ("q_rope", C.c_void_p), ("kv_cache", C.c_void_p),
+        ("k_rope_cache", C.c_void_p),
+        ("o_stride", C.c_int64 * 2), ("q_stride", C.c_int64 * 2), ("q_rope_stride", C.c_int64 * 2),
+        ("kv_stride", C.c_int64), ("k_rope_stride", C.c_int64),
+        ("q_cu_lens", C.c_void_p), ("kv_cu_lens", C.c_void_p), ("block_table", C.c_void_p),
+        ("block_cu_lens", C.c_void_p),
+        ("dtype", C.c_int32), ("batch_size", C.c_int32), ("n_tokens", C.c_int32), ("n_heads", C.c_int32),
+        ("head_dim", C.c_int32), ("rope_head_dim", C.c_int32), ("block_size", C.c_int32),
+        ("max_q_len", C.c_int32), ("max_kv_len", C.c_int32), ("sm_scale", C.c_float),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("num_splits", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 SLM_MOE_GEMM_BLOCK = 32  # rows per block of the grouped GEMM: the align step's block_size
 
 
@@ -287,6 +304,12 @@ def lib() -> C.CDLL:
         ("slm_moe_align_block", C.c_int, [C.POINTER(MoeAlignArgs), C.c_void_p]),
         ("slm_moe_sum", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
         ("slm_moe_w4a16_gemm", C.c_int, [C.POINTER(MoeGemmArgs), C.c_void_p]),
+        ("slm_mla_paged_kv_workspace_bytes", C.c_size_t, [C.POINTER(MlaArgs)]),
+        ("slm_mla_paged_kv_auto_splits", C.c_int32, [C.POINTER(MlaArgs)]),
+        ("slm_mla_paged_kv", C.c_int, [C.POINTER(MlaArgs), C.c_void_p]),
+        ("slm_mla_set_kv_cache", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+          C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ]:
         fn = getattr(L, name)  # AttributeError here = library/header mismatch: fail loudly
         fn.restype = restype

@@ -1,0 +1,145 @@
+// slm_mla_hip.cpp -- see slm_mla_hip.h.  Host code only: tensors are unpacked into slm_mla_args and handed to the
+// slm_mla_* entry points on torch's current HIP stream.
+#include "slm_mla_hip.h"
+
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+#include <c10/hip/HIPGraphsC10Utils.h>
+
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "slm_hip.h"
+
+namespace {
+
+void check(int rc, const char* what) {
+  TORCH_CHECK(rc == SLM_OK, what, " failed: ", slm_status_string(rc), " (", rc, ")",
+              rc == SLM_ERR_LAUNCH ? slm_last_hip_error() : "");
+}
+
+void* stream_of(const torch::Tensor& t) {
+  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
+}
+
+void check_i32(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt && t.is_contiguous(), "slm mla: ", what,
+              " must be a contiguous int32 GPU tensor");
+}
+
+int dtype_code(const torch::Tensor& t) {
+  if (t.scalar_type() == torch::kBFloat16) return SLM_BF16;
+  if (t.scalar_type() == torch::kHalf) return SLM_F16;
+  TORCH_CHECK(false, "slm mla: fp16 / bf16 only, got ", t.scalar_type());
+  return -1;
+}
+
+// split-KV scratch per device.  A buffer that was handed to a kernel is never released (graphs captured earlier
+// replay against its address); growth happens outside capture only.
+std::mutex g_ws_mu;
+std::map<int, torch::Tensor> g_ws;
+std::vector<torch::Tensor> g_ws_retired;
+
+torch::Tensor workspace(size_t need, const torch::Tensor& like) {
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  const int dev = like.device().index();
+  auto it = g_ws.find(dev);
+  if (it != g_ws.end() && static_cast<size_t>(it->second.numel()) >= need) return it->second;
+  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None,
+              "slm mla: the split-KV workspace (", need, " bytes) must exist before graph capture: run the call once first");
+  size_t size = need > (size_t{1} << 20) ? need : (size_t{1} << 20);
+  if (it != g_ws.end()) {
+    g_ws_retired.push_back(it->second);
+    if (size < 2 * static_cast<size_t>(it->second.numel())) size = 2 * static_cast<size_t>(it->second.numel());
+  }
+  torch::Tensor ws = torch::empty({static_cast<int64_t>(size)}, torch::dtype(torch::kUInt8).device(like.device()));
+  g_ws[dev] = ws;
+  return ws;
+}
+
+}  // namespace
+
+namespace slm {
+
+void mla_paged_kv(torch::Tensor& out, const torch::Tensor& q, const torch::Tensor& kv_cache, const torch::Tensor& q_rope,
+                  const torch::Tensor& k_rope_cache, const torch::Tensor& q_cu_lens, const torch::Tensor& kv_cu_lens,
+                  const torch::Tensor& block_table, const torch::Tensor& block_cu_lens, int block_size, int max_q_len,
+                  int max_kv_len, float sm_scale) {
+  TORCH_CHECK(out.is_cuda() && q.is_cuda() && q_rope.is_cuda() && kv_cache.is_cuda() && k_rope_cache.is_cuda(),
+              "slm mla: GPU tensors only");
+  TORCH_CHECK(out.dim() == 3 && q.dim() == 3 && q_rope.dim() == 3 && kv_cache.dim() == 2 && k_rope_cache.dim() == 2,
+              "slm mla: out / q / q_rope are [n_tokens, n_heads, dim], the caches [n_slots, dim]");
+  TORCH_CHECK(out.stride(-1) == 1 && q.stride(-1) == 1 && q_rope.stride(-1) == 1 && kv_cache.stride(-1) == 1 &&
+                  k_rope_cache.stride(-1) == 1,
+              "slm mla: last dimension must be contiguous");
+  TORCH_CHECK(out.scalar_type() == q.scalar_type() && q_rope.scalar_type() == q.scalar_type() &&
+                  kv_cache.scalar_type() == q.scalar_type() && k_rope_cache.scalar_type() == q.scalar_type(),
+              "slm mla: dtypes must match");
+  TORCH_CHECK(out.sizes() == q.sizes() && q_rope.size(0) == q.size(0) && q_rope.size(1) == q.size(1) &&
+                  kv_cache.size(1) == q.size(2) && k_rope_cache.size(1) == q_rope.size(2) &&
+                  kv_cache.size(0) == k_rope_cache.size(0),
+              "slm mla: shape mismatch between out / q / q_rope / caches");
+  check_i32(q_cu_lens, "q_cu_lens");
+  check_i32(kv_cu_lens, "kv_cu_lens");
+  check_i32(block_table, "block_table");
+  check_i32(block_cu_lens, "block_cu_lens");
+  slm_mla_args a{};
+  a.out = out.data_ptr();
+  a.q = q.data_ptr();
+  a.q_rope = q_rope.data_ptr();
+  a.kv_cache = kv_cache.data_ptr();
+  a.k_rope_cache = k_rope_cache.data_ptr();
+  a.o_stride[0] = out.stride(0);
+  a.o_stride[1] = out.stride(1);
+  a.q_stride[0] = q.stride(0);
+  a.q_stride[1] = q.stride(1);
+  a.q_rope_stride[0] = q_rope.stride(0);
+  a.q_rope_stride[1] = q_rope.stride(1);
+  a.kv_stride = kv_cache.stride(0);
+  a.k_rope_stride = k_rope_cache.stride(0);
+  a.q_cu_lens = q_cu_lens.const_data_ptr<int32_t>();
+  a.kv_cu_lens = kv_cu_lens.const_data_ptr<int32_t>();
+  a.block_table = block_table.const_data_ptr<int32_t>();
+  a.block_cu_lens = block_cu_lens.const_data_ptr<int32_t>();
+  a.dtype = dtype_code(q);
+  a.batch_size = static_cast<int32_t>(q_cu_lens.numel() - 1);
+  a.n_tokens = static_cast<int32_t>(q.size(0));
+  a.n_heads = static_cast<int32_t>(q.size(1));
+  a.head_dim = static_cast<int32_t>(q.size(2));
+  a.rope_head_dim = static_cast<int32_t>(q_rope.size(2));
+  a.block_size = block_size;
+  a.max_q_len = max_q_len;
+  a.max_kv_len = max_kv_len;
+  a.sm_scale = sm_scale;
+  if (a.n_tokens == 0 || a.batch_size == 0) return;
+  torch::Tensor ws;
+  const size_t need = slm_mla_paged_kv_workspace_bytes(&a);
+  if (need > 0) {
+    ws = workspace(need, q);
+    a.workspace = ws.data_ptr();
+    a.workspace_bytes = static_cast<size_t>(ws.numel());
+  }
+  check(slm_mla_paged_kv(&a, stream_of(q)), "slm_mla_paged_kv");
+}
+
+void mla_set_kv_cache(const torch::Tensor& slot_ids, const torch::Tensor& kv, const torch::Tensor& k_rope,
+                      torch::Tensor& kv_cache, torch::Tensor& k_rope_cache) {
+  check_i32(slot_ids, "slot_ids");
+  TORCH_CHECK(kv.is_cuda() && k_rope.is_cuda() && kv_cache.is_cuda() && k_rope_cache.is_cuda() && kv.dim() == 2 &&
+                  k_rope.dim() == 2 && kv_cache.dim() == 2 && k_rope_cache.dim() == 2 && kv.stride(1) == 1 &&
+                  k_rope.stride(1) == 1 && kv_cache.stride(1) == 1 && k_rope_cache.stride(1) == 1,
+              "slm mla: set_kv_cache takes 2-D GPU tensors with contiguous rows");
+  TORCH_CHECK(k_rope.scalar_type() == kv.scalar_type() && kv_cache.scalar_type() == kv.scalar_type() &&
+                  k_rope_cache.scalar_type() == kv.scalar_type(),
+              "slm mla: dtypes must match");
+  TORCH_CHECK(kv.size(0) == slot_ids.numel() && k_rope.size(0) == slot_ids.numel() && kv.size(1) == kv_cache.size(1) &&
+                  k_rope.size(1) == k_rope_cache.size(1),
+              "slm mla: set_kv_cache shape mismatch");
+  check(slm_mla_set_kv_cache(slot_ids.const_data_ptr<int32_t>(), kv.data_ptr(), k_rope.data_ptr(), kv.stride(0),
+                             k_rope.stride(0), kv_cache.data_ptr(), k_rope_cache.data_ptr(), kv_cache.stride(0),
+                             k_rope_cache.stride(0), kv.size(0), static_cast<int32_t>(kv.size(1)),
+                             static_cast<int32_t>(k_rope.size(1)), dtype_code(kv), stream_of(kv)),
+        "slm_mla_set_kv_cache");
+}
+
+}  // namespace slm

@@ -9,6 +9,7 @@
 
 #include "slm_attn_handler_hip.h"
 #include "slm_llama_hip.h"
+#include "slm_mla_hip.h"
 #include "slm_moe_hip.h"
 #include "slm_qlinear_hip.h"
 #include "slm_rejection_sampler_hip.h"
@@ -211,6 +212,21 @@ PYBIND11_MODULE(_slm_shim, m) {
         }, py::arg("a"), py::arg("wq"), py::arg("sz"), py::arg("c"), py::arg("sorted_token_idxes"),
         py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("K"), py::arg("N"), py::arg("group_size"),
         py::arg("a_div"), py::arg("format"), py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
+  // multi-head latent attention (slm_mla_hip.h)
+  m.def("mla_paged_kv",
+        [](torch::Tensor out, const torch::Tensor& q, const torch::Tensor& kv_cache, const torch::Tensor& q_rope,
+           const torch::Tensor& k_rope_cache, const torch::Tensor& q_cu_lens, const torch::Tensor& kv_cu_lens,
+           const torch::Tensor& block_table, const torch::Tensor& block_cu_lens, int block_size, int max_q_len,
+           int max_kv_len, float sm_scale) {
+          slm::mla_paged_kv(out, q, kv_cache, q_rope, k_rope_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens,
+                            block_size, max_q_len, max_kv_len, sm_scale);
+        }, py::arg("out"), py::arg("q"), py::arg("kv_cache"), py::arg("q_rope"), py::arg("k_rope_cache"),
+        py::arg("q_cu_lens"), py::arg("kv_cu_lens"), py::arg("block_table"), py::arg("block_cu_lens"),
+        py::arg("block_size"), py::arg("max_q_len"), py::arg("max_kv_len"), py::arg("sm_scale"));
+  m.def("mla_set_kv_cache", [](const torch::Tensor& slot_ids, const torch::Tensor& kv, const torch::Tensor& k_rope,
+                               torch::Tensor kv_cache, torch::Tensor k_rope_cache) {
+          slm::mla_set_kv_cache(slot_ids, kv, k_rope, kv_cache, k_rope_cache);
+        }, py::arg("slot_ids"), py::arg("kv"), py::arg("k_rope"), py::arg("kv_cache"), py::arg("k_rope_cache"));
   py::class_<slm::InputParameters>(m, "InputParameters")
       .def(py::init<>())
       .def_readwrite("num_sequences", &slm::InputParameters::num_sequences)

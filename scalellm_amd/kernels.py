@@ -1347,3 +1347,101 @@ def moe_w4_grouped_gemm(a: torch.Tensor, experts: PackedMoeW4, c: torch.Tensor, 
     g.format = experts.fmt | (_lib.SLM_W4_PAIRED if experts.paired else 0)
     g.flags = _lib.SLM_W4_SILU_MUL if silu_mul else 0
     check(_lib.lib().slm_moe_w4a16_gemm(C.byref(g), _stream()), "slm_moe_w4a16_gemm")
+
+
+# ---------------------------------------------------------------------------------------
+# multi-head latent attention (slm_hip.h section 11; csrc/mla.hip)
+# ---------------------------------------------------------------------------------------
+def _mla_args(out, q, q_rope, kv_cache, k_rope_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens,
+              block_size, max_q_len, max_kv_len, sm_scale, num_splits) -> "_lib.MlaArgs":
+    _require_gpu(out, q, q_rope, kv_cache, k_rope_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens)
+    if out.dim() != 3 or q.dim() != 3 or q_rope.dim() != 3 or kv_cache.dim() != 2 or k_rope_cache.dim() != 2:
+        raise SlmError("mla: out/q [n_tokens, n_heads, head_dim], q_rope [n_tokens, n_heads, rope_head_dim]; "
+                       "caches [n_slots, head_dim] and [n_slots, rope_head_dim]")
+    for t in (out, q, q_rope, kv_cache, k_rope_cache):
+        if t.stride(-1) != 1:
+            raise SlmError("mla: last dimension must be contiguous")
+        if t.dtype != q.dtype:
+            raise SlmError("mla: out/q/q_rope/kv_cache/k_rope_cache dtypes must match")
+    for t in (q_cu_lens, kv_cu_lens, block_table, block_cu_lens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("index tensors must be contiguous int32")
+    if out.shape != q.shape or q_rope.shape[:2] != q.shape[:2] or kv_cache.size(1) != q.size(2) or \
+            k_rope_cache.size(1) != q_rope.size(2) or kv_cache.size(0) != k_rope_cache.size(0):
+        raise SlmError("mla: shape mismatch between out / q / q_rope / caches")
+    a = _lib.MlaArgs()
+    a.out, a.q, a.q_rope = out.data_ptr(), q.data_ptr(), q_rope.data_ptr()
+    a.kv_cache, a.k_rope_cache = kv_cache.data_ptr(), k_rope_cache.data_ptr()
+    a.o_stride[0], a.o_stride[1] = out.stride(0), out.stride(1)
+    a.q_stride[0], a.q_stride[1] = q.stride(0), q.stride(1)
+    a.q_rope_stride[0], a.q_rope_stride[1] = q_rope.stride(0), q_rope.stride(1)
+    a.kv_stride, a.k_rope_stride = kv_cache.stride(0), k_rope_cache.stride(0)
+    a.q_cu_lens, a.kv_cu_lens = q_cu_lens.data_ptr(), kv_cu_lens.data_ptr()
+    a.block_table, a.block_cu_lens = block_table.data_ptr(), block_cu_lens.data_ptr()
+    a.dtype = _dtype_code(q)
+    a.batch_size, a.n_tokens = q_cu_lens.numel() - 1, q.size(0)
+    a.n_heads, a.head_dim, a.rope_head_dim = q.size(1), q.size(2), q_rope.size(2)
+    a.block_size, a.max_q_len, a.max_kv_len = int(block_size), int(max_q_len), int(max_kv_len)
+    a.sm_scale, a.num_splits = float(sm_scale), int(num_splits)
+    a.workspace, a.workspace_bytes = None, 0
+    return a
+
+
+def mla_paged_kv(
+    out: torch.Tensor,            # [n_tokens, n_heads, head_dim]
+    q: torch.Tensor,              # [n_tokens, n_heads, head_dim]
+    q_rope: torch.Tensor,         # [n_tokens, n_heads, rope_head_dim]
+    kv_cache: torch.Tensor,       # [n_slots, head_dim]: the latent rows (K and V)
+    k_rope_cache: torch.Tensor,   # [n_slots, rope_head_dim]
+    q_cu_lens: torch.Tensor,      # [batch + 1] int32
+    kv_cu_lens: torch.Tensor,     # [batch + 1] int32
+    block_table: torch.Tensor,    # flattened first-slot ids, int32
+    block_cu_lens: torch.Tensor,  # [batch + 1] int32
+    block_size: int,
+    max_q_len: int,
+    max_kv_len: int,
+    sm_scale: float,
+    num_splits: int = 0,          # 0 = heuristic, > 0 forces the split-KV count
+) -> None:
+    """Multi-head latent attention over the paged latent cache (slm_mla_paged_kv; semantics of the reference's
+    tests/mla_ref.h): writes `out` in place, async on the current stream."""
+    L = _lib.lib()
+    a = _mla_args(out, q, q_rope, kv_cache, k_rope_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens,
+                  block_size, max_q_len, max_kv_len, sm_scale, num_splits)
+    if a.n_tokens == 0 or a.batch_size == 0:
+        return
+    need = L.slm_mla_paged_kv_workspace_bytes(C.byref(a))
+    if need:
+        ws = reserve_workspace(need, q.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(L.slm_mla_paged_kv(C.byref(a), _stream()), "slm_mla_paged_kv")
+
+
+def mla_paged_kv_auto_splits(n_tokens: int, batch_size: int, n_heads: int, head_dim: int, max_q_len: int,
+                             max_kv_len: int, dtype=torch.bfloat16) -> int:
+    """Split-KV count the library's heuristic picks for these sizes (host-side only)."""
+    a = _lib.MlaArgs()
+    a.dtype = _lib.SLM_BF16 if dtype == torch.bfloat16 else _lib.SLM_F16
+    a.batch_size, a.n_tokens, a.n_heads = int(batch_size), int(n_tokens), int(n_heads)
+    a.head_dim, a.rope_head_dim = int(head_dim), 64
+    a.max_q_len, a.max_kv_len = int(max_q_len), int(max_kv_len)
+    return int(_lib.lib().slm_mla_paged_kv_auto_splits(C.byref(a)))
+
+
+def mla_set_kv_cache(slot_ids: torch.Tensor, kv: torch.Tensor, k_rope: torch.Tensor, kv_cache: torch.Tensor,
+                     k_rope_cache: torch.Tensor) -> None:
+    """kv_cache[slot_ids[t]] = kv[t] and k_rope_cache[slot_ids[t]] = k_rope[t] in one launch (bit-exact; the
+    sources may have any 16-byte aligned token stride)."""
+    _require_gpu(slot_ids, kv, k_rope, kv_cache, k_rope_cache)
+    if slot_ids.dtype != torch.int32 or not slot_ids.is_contiguous():
+        raise SlmError("slot_ids must be contiguous int32")
+    for t in (kv, k_rope, kv_cache, k_rope_cache):
+        if t.dim() != 2 or t.stride(1) != 1 or t.dtype != kv.dtype:
+            raise SlmError("mla_set_kv_cache: 2-D tensors of one dtype with contiguous rows")
+    if kv.size(0) != slot_ids.numel() or k_rope.size(0) != slot_ids.numel() or kv.size(1) != kv_cache.size(1) or \
+            k_rope.size(1) != k_rope_cache.size(1):
+        raise SlmError("mla_set_kv_cache: shape mismatch")
+    check(_lib.lib().slm_mla_set_kv_cache(slot_ids.data_ptr(), kv.data_ptr(), k_rope.data_ptr(), kv.stride(0),
+                                          k_rope.stride(0), kv_cache.data_ptr(), k_rope_cache.data_ptr(),
+                                          kv_cache.stride(0), k_rope_cache.stride(0), kv.size(0), kv.size(1),
+                                          k_rope.size(1), _dtype_code(kv), _stream()), "slm_mla_set_kv_cache")
