@@ -31,23 +31,6 @@
 
 namespace slm {
 
-template <typename T>
-struct TileMfma;
-template <>
-struct TileMfma<bf16_tag> {
-  typedef bf16x8_t frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct TileMfma<f16_tag> {
-  typedef f16x8_t frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 // (s_setprio 1 around the two MFMA clusters was measured on this form: chunked 8 x 256 over 4 k +1 %,
 // causal 1 x 2048 -13 % -- the long query tile's co-resident partner starves it; not used)
 // KV rows per tile: 32 (one S^T block per wave and tile) or 64 (two: KVT template parameter)
@@ -112,7 +95,7 @@ typedef __attribute__((address_space(3))) tr_v4s tr_lds_v4s;
 template <typename T, int HD, int NW, bool PF, bool PLAIN, int KVT = 32, bool DB = false, bool DMA = false, bool PIPE = false,
           bool KV2 = false>
 __global__ void __launch_bounds__(64 * NW * (KV2 ? 2 : 1)) __attribute__((amdgpu_waves_per_eu(2))) attn_tile_kernel(const AttnKParams p, int tiles_per_seq) {
-  typedef typename TileMfma<T>::frag frag_t;
+  typedef typename Mfma<T>::frag frag_t;
   static_assert(KVT == 32 || KVT == 64, "KV tile rows");
   static_assert(!DB || PF, "the double-buffered form prefetches through registers");
   static_assert(!DMA || DB, "LDS-DMA staging is built on the double-buffered form");
@@ -408,7 +391,7 @@ __global__ void __launch_bounds__(64 * NW * (KV2 ? 2 : 1)) __attribute__((amdgpu
         const int kr = 32 * h + l31;
         const u32x4 kv4 = *reinterpret_cast<const u32x4*>(k_lds + kbuf * K_BYTES + kr * (HD * 2) +
                                                           (((2 * s + hh) ^ (kr & (NSLOT - 1))) << 4));
-        sc[P][h] = TileMfma<T>::run(__builtin_bit_cast(frag_t, kv4), qf[s], sc[P][h]);
+        sc[P][h] = Mfma<T>::run(__builtin_bit_cast(frag_t, kv4), qf[s], sc[P][h]);
       }
     };
     auto zero = [&](auto pc) __attribute__((always_inline)) {
@@ -500,7 +483,7 @@ __global__ void __launch_bounds__(64 * NW * (KV2 ? 2 : 1)) __attribute__((amdgpu
           const tr_v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_lds_v4s*)(va0 + 8 * 32));
           const u32x2 v0 = __builtin_bit_cast(u32x2, t0), v1 = __builtin_bit_cast(u32x2, t1);
           const u32x4 va = {v0.x, v0.y, v1.x, v1.y};
-          oacc[d] = TileMfma<T>::run(__builtin_bit_cast(frag_t, va), pfrag, oacc[d]);
+          oacc[d] = Mfma<T>::run(__builtin_bit_cast(frag_t, va), pfrag, oacc[d]);
         }
       }
     };
@@ -665,7 +648,7 @@ __global__ void __launch_bounds__(64 * NW * (KV2 ? 2 : 1)) __attribute__((amdgpu
       for (int h = 0; h < NH; ++h) {
         const int kr = 32 * h + l31;
         const u32x4 kv4 = *reinterpret_cast<const u32x4*>(kb + kr * (HD * 2) + ((sl ^ (kr & (NSLOT - 1))) << 4));
-        sacc[h] = TileMfma<T>::run(__builtin_bit_cast(frag_t, kv4), qf[s], sacc[h]);
+        sacc[h] = Mfma<T>::run(__builtin_bit_cast(frag_t, kv4), qf[s], sacc[h]);
       }
     }
 
@@ -779,7 +762,7 @@ __global__ void __launch_bounds__(64 * NW * (KV2 ? 2 : 1)) __attribute__((amdgpu
         const tr_v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_lds_v4s*)(va0 + 8 * 32));
         const u32x2 v0 = __builtin_bit_cast(u32x2, t0), v1 = __builtin_bit_cast(u32x2, t1);
         const u32x4 va = {v0.x, v0.y, v1.x, v1.y};
-        oacc[d] = TileMfma<T>::run(__builtin_bit_cast(frag_t, va), pfrag, oacc[d]);
+        oacc[d] = Mfma<T>::run(__builtin_bit_cast(frag_t, va), pfrag, oacc[d]);
       }
     }
     if constexpr (DMA) {

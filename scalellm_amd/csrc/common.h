@@ -77,6 +77,24 @@ __device__ __forceinline__ float dot2<f16_tag>(uint32_t a, uint32_t b, float acc
                                 acc, false);
 }
 
+// D = A . B + C on the matrix pipe: v_mfma_f32_32x32x16_{bf16,f16}, 8 k-values per lane and operand
+template <typename T>
+struct Mfma;
+template <>
+struct Mfma<bf16_tag> {
+  typedef bf16x8_t frag;
+  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  }
+};
+template <>
+struct Mfma<f16_tag> {
+  typedef f16x8_t frag;
+  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  }
+};
+
 // ---- cross-lane (wave64) --------------------------------------------------------
 // DPP lane exchange inside a row of 16 lanes; full-rate VALU, no LDS traffic.
 template <int CTRL>

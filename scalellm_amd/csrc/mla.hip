@@ -37,23 +37,6 @@ namespace slm {
 
 namespace {
 
-template <typename T>
-struct MlaMfma;
-template <>
-struct MlaMfma<bf16_tag> {
-  typedef bf16x8_t frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct MlaMfma<f16_tag> {
-  typedef f16x8_t frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 struct MlaKParams {
   void* out;
   const void* q;
@@ -90,7 +73,7 @@ typedef __attribute__((address_space(3))) tr_v4s tr_lds_v4s;
 // NQ: 32-row query blocks per workgroup (1: up to 32 rows -- decode with few heads; 2: 64 rows).
 template <typename T, int HD, int NQ>
 __global__ void __launch_bounds__(64 * MLA_WAVES) __attribute__((amdgpu_waves_per_eu(HD * NQ >= 1024 ? 1 : 2))) mla_kernel(const MlaKParams p) {
-  typedef typename MlaMfma<T>::frag frag_t;
+  typedef typename Mfma<T>::frag frag_t;
   constexpr int NSUB = (HD + MLA_ROPE) / 16;     // sub-tiles = k-steps of the score product
   constexpr int NSUB_KV = HD / 16;               // ... of which the latent's
   constexpr int KS = NSUB / MLA_WAVES;           // k-steps per wave
@@ -247,7 +230,7 @@ __global__ void __launch_bounds__(64 * MLA_WAVES) __attribute__((amdgpu_waves_pe
           const int s = wave * KS + j;
           const u32x4 kv4 = *reinterpret_cast<const u32x4*>(kv_lds + mla_sub_base(s) + k_lane);
 #pragma unroll
-          for (int n = 0; n < NQ; ++n) sp[n] = MlaMfma<T>::run(__builtin_bit_cast(frag_t, kv4), qf[n][j], sp[n]);
+          for (int n = 0; n < NQ; ++n) sp[n] = Mfma<T>::run(__builtin_bit_cast(frag_t, kv4), qf[n][j], sp[n]);
         }
 #pragma unroll
         for (int n = 0; n < NQ; ++n)
@@ -322,7 +305,7 @@ __global__ void __launch_bounds__(64 * MLA_WAVES) __attribute__((amdgpu_waves_pe
           const u32x4 va = {v0.x, v0.y, v1.x, v1.y};
 #pragma unroll
           for (int n = 0; n < NQ; ++n)
-            oacc[n][d] = MlaMfma<T>::run(__builtin_bit_cast(frag_t, va), __builtin_bit_cast(frag_t, pb[n][s2]), oacc[n][d]);
+            oacc[n][d] = Mfma<T>::run(__builtin_bit_cast(frag_t, va), __builtin_bit_cast(frag_t, pb[n][s2]), oacc[n][d]);
         }
       }
       if (more) {

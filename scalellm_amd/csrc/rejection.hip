@@ -18,8 +18,6 @@
 // Arithmetic is IEEE fp32 without contraction, division correctly rounded; every argmax is a max over
 // the 64-bit composite (order-preserving key << 32 | ~index), so ties go to the lower index and the
 // result does not depend on the reduction order.  No float atomics: bit-identical across repeats.
-#include <math.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -27,39 +25,12 @@
 #pragma clang fp contract(off)
 
 #include "philox.h"
+#include "vocab_row.h"  // keys, loads, reductions, radix_select, gather_sort_top (shared with sampling.hip)
 
 namespace slm {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxVocab = 1 << 22;
-
-// order-preserving key: larger key = larger value; -0 and +0 share one key (-0 + 0 = +0)
-__device__ __forceinline__ uint32_t f2key(float x) {
-  const uint32_t u = __float_as_uint(x + 0.0f);
-  return u ^ ((u & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-__device__ __forceinline__ u64 composite(float x, int i) {
-  return ((u64)f2key(x) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
-}
-__device__ __forceinline__ int composite_index(u64 c) { return (int)(0xFFFFFFFFu - (uint32_t)c); }
-
-template <int DT>
-constexpr int elem_bytes() { return DT == SLM_F32 ? 4 : 2; }
-
-template <int DT>
-__device__ __forceinline__ float ld(const void* row, int i) {
-  if constexpr (DT == SLM_F16) return (float)reinterpret_cast<const _Float16*>(row)[i];
-  else if constexpr (DT == SLM_BF16)
-    return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(row)[i] << 16);
-  else return reinterpret_cast<const float*>(row)[i];
-}
+using namespace vocab_row;
 
 // G consecutive values from id i0 (ids >= V read nothing and give -inf); one 8- or 16-byte load when
 // the row is aligned and the group is whole
@@ -102,148 +73,15 @@ struct Rec {  // one row of one sequence, written by launch 1
   int32_t acc;  // accepted (rows < k)
 };
 
-struct Smem {
-  u64 red64[kWaves];
-  float redf[kWaves];
-  uint32_t hist[256];
-  uint32_t sel_bin, sel_t, sel_h;
-  uint32_t top_key[SLM_SAMPLE_MAX_TOP];
-  int32_t top_idx[SLM_SAMPLE_MAX_TOP];
-  int32_t top_cnt;
-};
-
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    const u64 w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// block max of a 64-bit composite (every thread gets it)
-__device__ u64 block_max_u64(u64 v, Smem& sm) {
-  v = wave_max_u64(v);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) sm.red64[tid >> 6] = v;
-  __syncthreads();
-  u64 r = sm.red64[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) r = sm.red64[w] > r ? sm.red64[w] : r;
-  __syncthreads();
-  return r;
-}
-// block sum in a fixed order: wave butterfly, waves in order (every thread gets it)
-__device__ float block_sum_f(float v, Smem& sm) {
-  v = wave_sum_f(v);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) sm.redf[tid >> 6] = v;
-  __syncthreads();
-  float r = sm.redf[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) r += sm.redf[w];
-  __syncthreads();
-  return r;
-}
-
-// wave 0: the bin b (scanning 255 -> 0) with before(b) <= t < before(b) + hist[b]
-__device__ void scan_bins(Smem& sm, uint32_t t) {
-  const int lane = threadIdx.x;
-  uint32_t h[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { h[j] = sm.hist[255 - 4 * lane - j]; s += h[j]; }
-  uint32_t inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t n = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += n;
-  }
-  uint32_t before = inc - s;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (before <= t && t < before + h[j]) {
-      sm.sel_bin = 255 - 4 * lane - j;
-      sm.sel_t = t - before;
-      sm.sel_h = h[j];
-    }
-    before += h[j];
-  }
-}
+typedef RowSmem<uint32_t> Smem;  // 32-bit bins: the only select here counts
 
 // top-n of a row (n <= 20) in the order (value desc, index asc), into sm.top_key / top_idx (sorted).
-// Radix select over the 8-bit digits of the key; a cut inside a run of equal keys is resolved
-// lowest-index-first by a radix select over the index.  Each pass re-reads the row (L2 / MALL).
+// Each pass of the select re-reads the row (L2 / MALL).
 template <int DT>
 __device__ void top_n(const void* row, int V, int n, Smem& sm) {
-  const int tid = threadIdx.x;
-  uint32_t prefix = 0, pmask = 0, t = (uint32_t)(n - 1), heq = 0;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (tid < 256) sm.hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < V; i += kThreads) {
-      const uint32_t k = f2key(ld<DT>(row, i));
-      if ((k & pmask) == prefix) atomicAdd(&sm.hist[(k >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) scan_bins(sm, t);
-    __syncthreads();
-    prefix |= sm.sel_bin << shift;
-    pmask |= 255u << shift;
-    t = sm.sel_t;
-    heq = sm.sel_h;
-    __syncthreads();  // sel_* are rewritten by the next pass
-  }
-  int32_t imax = 0x7FFFFFFF;  // kept: key > prefix, or key == prefix and index <= imax
-  if (t + 1 < heq) {          // only the (t + 1) lowest indices among key == prefix: select on IM - i
-    int nb = 1;
-    while ((1 << nb) < V) ++nb;
-    const uint32_t IM = (1u << nb) - 1u;
-    uint32_t ip = 0, im = 0;
-    for (int shift = ((nb - 1) / 8) * 8; shift >= 0; shift -= 8) {
-      if (tid < 256) sm.hist[tid] = 0;
-      __syncthreads();
-      for (int i = tid; i < V; i += kThreads) {
-        const uint32_t inv = IM - (uint32_t)i;
-        if (f2key(ld<DT>(row, i)) == prefix && (inv & im) == ip) atomicAdd(&sm.hist[(inv >> shift) & 255u], 1u);
-      }
-      __syncthreads();
-      if (tid < 64) scan_bins(sm, t);
-      __syncthreads();
-      ip |= sm.sel_bin << shift;
-      im |= 255u << shift;
-      t = sm.sel_t;
-      __syncthreads();
-    }
-    imax = (int32_t)(IM - ip);
-  }
-  if (tid == 0) sm.top_cnt = 0;
-  __syncthreads();
-  for (int i = tid; i < V; i += kThreads) {
-    const uint32_t k = f2key(ld<DT>(row, i));
-    if (k > prefix || (k == prefix && i <= imax)) {
-      const int slot = atomicAdd(&sm.top_cnt, 1);
-      if (slot < SLM_SAMPLE_MAX_TOP) { sm.top_key[slot] = k; sm.top_idx[slot] = i; }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int a = 1; a < n; ++a) {  // insertion sort: key desc, index asc
-      const uint32_t k = sm.top_key[a];
-      const int32_t ix = sm.top_idx[a];
-      int b = a - 1;
-      while (b >= 0 && (sm.top_key[b] < k || (sm.top_key[b] == k && sm.top_idx[b] > ix))) {
-        sm.top_key[b + 1] = sm.top_key[b];
-        sm.top_idx[b + 1] = sm.top_idx[b];
-        --b;
-      }
-      sm.top_key[b + 1] = k;
-      sm.top_idx[b + 1] = ix;
-    }
-  }
+  auto e = [&](int i, uint32_t& k, uint32_t& w) { k = f2key(ld<DT>(row, i)); w = 1; return true; };
+  const Filter fn = radix_select<false>(e, V, (uint32_t)(n - 1), -1.f, 0.f, sm);
+  gather_sort_top(e, V, n, fn, sm);
   __syncthreads();
 }
 

@@ -24,107 +24,24 @@
 //   write   probs, then processed logits (last: `processed` may alias `logits`)
 // The processing arithmetic is plain IEEE fp32 without contraction (step 1 is a multiply and two
 // subtractions, not an FMA) and with correctly rounded division, so numpy float32 reproduces it.
-#include <math.h>
-
 #include "common.h"
 
 #pragma clang fp contract(off)
 
-#include "philox.h"  // philox_word, exp_draw (shared with rejection.hip)
+#include "philox.h"     // philox_word, exp_draw (shared with rejection.hip)
+#include "vocab_row.h"  // keys, loads, reductions, radix_select, gather_sort_top (shared with rejection.hip)
 
 namespace slm {
 namespace {
 
-typedef unsigned long long u64;
+using namespace vocab_row;
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kKeyNegInf = 0x007FFFFFu;  // f2key(-inf)
-constexpr int kMaxVocab = 1 << 22;            // 2^22 tokens * 2^40 mass units < 2^64
 constexpr int kMaxPenVocab = 1 << 19;         // bitmap + prefix of 2^14 words each: 128 KiB of LDS
 
-// order-preserving key: larger key = larger value; -0 and +0 share one key (-0 + 0 = +0)
-__device__ __forceinline__ uint32_t f2key(float x) {
-  const uint32_t u = __float_as_uint(x + 0.0f);
-  return u ^ ((u & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-// softmax numerator and its fixed-point form in 2^-40 units (the top element weighs 2^40)
-__device__ __forceinline__ float expm(float x, float m) { return expf(x - m); }
-__device__ __forceinline__ u64 mass_q(float x, float m) {
-  const float e = expm(x, m) * 1099511627776.0f;  // exact scaling by 2^40
-  return e > 0.f ? (u64)e : 0ull;
-}
-
-template <int DT>
-__device__ __forceinline__ float ld(const void* row, int i) {
-  if constexpr (DT == SLM_F16) return (float)reinterpret_cast<const _Float16*>(row)[i];
-  else if constexpr (DT == SLM_BF16)
-    return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(row)[i] << 16);
-  else return reinterpret_cast<const float*>(row)[i];
-}
-template <int DT>
-__device__ __forceinline__ void st(void* row, int i, float x) {
-  if constexpr (DT == SLM_F16) reinterpret_cast<_Float16*>(row)[i] = (_Float16)x;
-  else if constexpr (DT == SLM_BF16) reinterpret_cast<uint16_t*>(row)[i] = pack1<bf16_tag>(x);
-  else reinterpret_cast<float*>(row)[i] = x;
-}
-template <int DT>
-constexpr int elem_bytes() { return DT == SLM_F32 ? 4 : 2; }
-
-struct Smem {
-  u64 hist[256];
-  u64 red64[kWaves];
-  float redf[kWaves];
+struct Smem : RowSmem<u64> {  // 64-bit bins: top-p sums fixed-point masses
   uint32_t scan32[kWaves];
-  u64 sel_t, sel_h;
-  uint32_t sel_bin;
-  uint32_t top_key[SLM_SAMPLE_MAX_TOP];
-  int32_t top_idx[SLM_SAMPLE_MAX_TOP];
-  int32_t top_cnt;
 };
 
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    const u64 w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block max of a 64-bit composite (every thread gets it)
-__device__ u64 block_max_u64(u64 v, Smem& sm) {
-  v = wave_max_u64(v);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) sm.red64[tid >> 6] = v;
-  __syncthreads();
-  u64 r = sm.red64[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) r = sm.red64[w] > r ? sm.red64[w] : r;
-  __syncthreads();
-  return r;
-}
-// block sum in a fixed order: thread-sequential, wave butterfly, waves in order
-__device__ float block_sum_f(float v, Smem& sm) {
-  v = wave_sum_f(v);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) sm.redf[tid >> 6] = v;
-  __syncthreads();
-  float r = sm.redf[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) r += sm.redf[w];
-  __syncthreads();
-  return r;
-}
 // exclusive prefix sum of one uint32 per thread, in thread order
 __device__ uint32_t block_excl_scan(uint32_t v, Smem& sm) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -140,102 +57,6 @@ __device__ uint32_t block_excl_scan(uint32_t v, Smem& sm) {
   for (int w = 0; w < (tid >> 6); ++w) base += sm.scan32[w];
   __syncthreads();
   return base + inc - v;
-}
-
-// wave 0: find the bin b (scanning 255 -> 0) with before(b) <= t < before(b) + hist[b].
-// frac >= 0: t = floor(frac * total) (the top-p target, known once the first histogram is in).
-__device__ void scan_bins(Smem& sm, u64 t, float frac) {
-  const int lane = threadIdx.x;
-  u64 h[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { h[j] = sm.hist[255 - 4 * lane - j]; s += h[j]; }
-  u64 inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 n = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += n;
-  }
-  if (frac >= 0.f) {
-    const u64 total = __shfl(inc, 63, 64);
-    t = (u64)((double)frac * (double)total);
-    if (t >= total) t = total - 1;
-  }
-  u64 before = inc - s;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (before <= t && t < before + h[j]) {
-      sm.sel_bin = 255 - 4 * lane - j;
-      sm.sel_t = t - before;
-      sm.sel_h = h[j];
-    }
-    before += h[j];
-  }
-}
-
-struct Filter {
-  uint32_t key;  // kept: key > this.key, or key == this.key and index <= imax
-  int32_t imax;
-  __device__ __forceinline__ bool keep(uint32_t k, int i) const { return k > key || (k == key && i <= imax); }
-};
-
-// Radix select over the order (key desc, index asc) of the eligible elements: the filter that keeps
-// the element e with W(before e) <= t < W(before e) + w(e), and everything before it.
-// elem(i, key, w) -> eligible; w = 1 (count) or the fixed-point mass (MASS: t = floor(frac * total)).
-template <bool MASS, class ElemF>
-__device__ Filter radix_select(const ElemF& elem, int V, u64 t, float frac, float m, Smem& sm) {
-  const int tid = threadIdx.x;
-  uint32_t prefix = 0, pmask = 0;
-  u64 heq = 0;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (tid < 256) sm.hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < V; i += kThreads) {
-      uint32_t k;
-      u64 w;
-      if (elem(i, k, w) && w && (k & pmask) == prefix) atomicAdd(&sm.hist[(k >> shift) & 255u], w);
-    }
-    __syncthreads();
-    if (tid < 64) scan_bins(sm, t, (MASS && shift == 24) ? frac : -1.f);
-    __syncthreads();
-    prefix |= sm.sel_bin << shift;
-    pmask |= 255u << shift;
-    t = sm.sel_t;
-    heq = sm.sel_h;
-    __syncthreads();  // sel_* are rewritten by the next pass
-  }
-  Filter f{prefix, 0x7FFFFFFF};
-  u64 j = t, cnt = heq;  // position among the equal keys, their number
-  if constexpr (MASS) {  // equal keys weigh the same: heq = cnt * q, the crossing is the j-th
-    const u64 q = mass_q(key2f(prefix), m);
-    if (q == 0) return f;  // a row without mass (non-finite logits): nothing to split
-    cnt = heq / q;
-    j = t / q;
-  }
-  if (j + 1 >= cnt) return f;
-  // the (j + 1) lowest indices among the elements with key == prefix: select on inv = IM - i
-  int nb = 1;
-  while ((1 << nb) < V) ++nb;
-  const uint32_t IM = (1u << nb) - 1u;
-  uint32_t ip = 0, im = 0;
-  for (int shift = ((nb - 1) / 8) * 8; shift >= 0; shift -= 8) {
-    if (tid < 256) sm.hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < V; i += kThreads) {
-      uint32_t k;
-      u64 w;
-      const uint32_t inv = IM - (uint32_t)i;
-      if (elem(i, k, w) && w && k == prefix && (inv & im) == ip) atomicAdd(&sm.hist[(inv >> shift) & 255u], 1ull);
-    }
-    __syncthreads();
-    if (tid < 64) scan_bins(sm, j, -1.f);
-    __syncthreads();
-    ip |= sm.sel_bin << shift;
-    im |= 255u << shift;
-    j = sm.sel_t;
-    __syncthreads();
-  }
-  f.imax = (int32_t)(IM - ip);
-  return f;
 }
 
 struct Params {
@@ -347,12 +168,12 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(const Params p) {
   // ---- max: greedy token and softmax shift ---------------------------------------------------
   u64 best = 0;
   for (int i = tid; i < V; i += kThreads) {
-    const u64 c = ((u64)f2key(proc(i)) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+    const u64 c = composite(proc(i), i);
     best = c > best ? c : best;
   }
   best = block_max_u64(best, sm);
   const float m = key2f((uint32_t)(best >> 32));
-  const int top_i = (int)(0xFFFFFFFFu - (uint32_t)best);
+  const int top_i = composite_index(best);
 
   // ---- top-k, then top-p over the top-k survivors ---------------------------------------------
   Filter f{0u, 0x7FFFFFFF};
@@ -369,7 +190,7 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(const Params p) {
       w = mass_q(x, m);
       return true;
     };
-    f = radix_select<true>(e, V, 0, tp > 0.f ? tp : 0.f, m, sm);
+    f = radix_select<true>(e, V, 0ull, tp > 0.f ? tp : 0.f, m, sm);
     // the top-p boundary is a position among the top-k survivors: when it falls in the run of equal
     // keys that top-k cut, the tokens top-k dropped from that run stay dropped
     if (f.key == fk.key && fk.imax < f.imax) f.imax = fk.imax;
@@ -389,13 +210,13 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(const Params p) {
       s += e;
       if (sample_row) {  // argmax(probs / E) = argmax(exp(x - m) / E): the common 1 / sum drops out
         const float sc = e / exp_draw(philox_word(seed, pos, 0u, (uint32_t)i));
-        const u64 c = ((u64)f2key(sc) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+        const u64 c = composite(sc, i);
         race = c > race ? c : race;
       }
     }
     s = block_sum_f(s, sm);
     const float lse = logf(s);
-    if (sample_row) token = (int)(0xFFFFFFFFu - (uint32_t)block_max_u64(race, sm));
+    if (sample_row) token = composite_index(block_max_u64(race, sm));
     if (p.logprobs && tid == 0) p.logprobs[r] = (proc(token) - m) - lse;
 
     // ---- top-n of log_softmax(processed) ------------------------------------------------------
@@ -407,32 +228,9 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(const Params p) {
         return true;
       };
       const Filter fn = radix_select<false>(e, V, (u64)(p.n_top - 1), -1.f, m, sm);
-      if (tid == 0) sm.top_cnt = 0;
-      __syncthreads();
-      for (int i = tid; i < V; i += kThreads) {
-        uint32_t k;
-        u64 w;
-        e(i, k, w);
-        if (fn.keep(k, i)) {
-          const int slot = atomicAdd(&sm.top_cnt, 1);
-          if (slot < SLM_SAMPLE_MAX_TOP) { sm.top_key[slot] = k; sm.top_idx[slot] = i; }
-        }
-      }
-      __syncthreads();
+      gather_sort_top(e, V, p.n_top, fn, sm);
       if (tid == 0) {
         const int n = p.n_top;
-        for (int a = 1; a < n; ++a) {  // insertion sort: key desc, index asc
-          const uint32_t k = sm.top_key[a];
-          const int32_t ix = sm.top_idx[a];
-          int b = a - 1;
-          while (b >= 0 && (sm.top_key[b] < k || (sm.top_key[b] == k && sm.top_idx[b] > ix))) {
-            sm.top_key[b + 1] = sm.top_key[b];
-            sm.top_idx[b + 1] = sm.top_idx[b];
-            --b;
-          }
-          sm.top_key[b + 1] = k;
-          sm.top_idx[b + 1] = ix;
-        }
         for (int a = 0; a < n; ++a) {
           const float x = key2f(sm.top_key[a]);
           p.top_lp[r * n + a] = x == -INFINITY ? -INFINITY : (x - m) - lse;

@@ -193,10 +193,7 @@ __global__ void __launch_bounds__(256) w4_splitk_reduce_silu_kernel(
 using namespace slm;
 
 static bool w4_format_ok(int32_t format, int64_t N) {
-  const int32_t base = format & SLM_W4_FORMAT_MASK;
-  if (format & ~(SLM_W4_FORMAT_MASK | SLM_W4_PAIRED)) return false;
-  if (base != SLM_W4_GPTQ && base != SLM_W4_AWQ) return false;
-  return !(format & SLM_W4_PAIRED) || N % 64 == 0;
+  return w4_format_valid(format) && (!(format & SLM_W4_PAIRED) || N % 64 == 0);
 }
 
 extern "C" {

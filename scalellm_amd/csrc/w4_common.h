@@ -1,5 +1,6 @@
-// w4_common.h -- shared pieces of the int4-weight GEMM kernels (w4.hip, w4_ws.hip): the dequant
-// helpers (one code path for the GEMMs and the debug dequant kernel), MFMA wrappers, kernel params.
+// w4_common.h -- shared pieces of the int4-weight GEMM kernels: the dequant helpers (one code path for the
+// GEMMs and the debug dequant kernel), the all-ones fragment word, kernel params, what each kernel file says
+// about itself, and the host checks of the format word and the group size (Mfma<T> is in common.h).
 #pragma once
 #include "common.h"
 
@@ -156,6 +157,18 @@ struct W4Magic<f16_tag> {
   }
 };
 
+// 1.0 twice, packed in T: against it a dot2 or an MFMA sums the activations (X in the formula above)
+template <typename T>
+struct W4Ones;
+template <>
+struct W4Ones<bf16_tag> {
+  static constexpr uint32_t bits = 0x3F803F80u;
+};
+template <>
+struct W4Ones<f16_tag> {
+  static constexpr uint32_t bits = 0x3C003C00u;
+};
+
 struct GemmKParams {
   const void* a;
   const uint32_t* wq;
@@ -189,23 +202,6 @@ struct GemmKParams {
   void* norm_res_out;          // [M, K] T
   const void* norm_weight;     // [K] T
   void* norm_out;              // optional [M, K] T copy of the normalised activations
-};
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<bf16_tag> {
-  typedef bf16x8_t frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct Mfma<f16_tag> {
-  typedef f16x8_t frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
 };
 
 // SLM_W4_SILU_MUL epilogue of the C^T-accumulator kernels (w4_ws.hip, w4_xl.hip; split_k == 1):
@@ -250,6 +246,17 @@ __device__ __forceinline__ void store_ct_silu_pair(const GemmKParams& p, const f
       }
     }
   }
+}
+
+// What every int4 entry point accepts, said once (host).  A format word is GPTQ or AWQ, optionally
+// | SLM_W4_PAIRED; a group size is 32, 64, a power of two from 128 up, or K (per-channel), and divides K.
+inline bool w4_format_bits_ok(int32_t format) { return !(format & ~(SLM_W4_FORMAT_MASK | SLM_W4_PAIRED)); }
+inline bool w4_format_valid(int32_t format) {
+  const int32_t base = format & SLM_W4_FORMAT_MASK;
+  return w4_format_bits_ok(format) && (base == SLM_W4_GPTQ || base == SLM_W4_AWQ);
+}
+inline bool w4_group_size_valid(int64_t gs, int64_t K) {
+  return (gs == 32 || gs == 64 || (gs >= 128 && is_pow2(gs)) || gs == K) && K % gs == 0;
 }
 
 constexpr int W4_KC = 128;  // K granularity of the plan (split-K units, LDS chunk of the small-M kernels)

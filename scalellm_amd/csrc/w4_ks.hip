@@ -48,17 +48,6 @@
 
 namespace slm {
 
-template <typename T>
-struct KsOnes;
-template <>
-struct KsOnes<bf16_tag> {
-  static constexpr uint32_t bits = 0x3F803F80u;
-};
-template <>
-struct KsOnes<f16_tag> {
-  static constexpr uint32_t bits = 0x3C003C00u;
-};
-
 // raw buffer resources: SGPR base + 32-bit offsets (no 64-bit VALU address math per load), and
 // out-of-range stores are dropped by the hardware -- rows >= M and tiles past the run need no branch,
 // so the loop body is straight-line code and hipcc's vmcnt waits stay exact
@@ -219,10 +208,10 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
 #pragma unroll
         for (int jj = 0; jj < WPG; ++jj) {
           const u32x4 f = __builtin_bit_cast(u32x4, act[mt][c][g * WPG + jj]);
-          xs0 = dot2<T>(f.x, KsOnes<T>::bits, xs0);
-          xs1 = dot2<T>(f.y, KsOnes<T>::bits, xs1);
-          xs0 = dot2<T>(f.z, KsOnes<T>::bits, xs0);
-          xs1 = dot2<T>(f.w, KsOnes<T>::bits, xs1);
+          xs0 = dot2<T>(f.x, W4Ones<T>::bits, xs0);
+          xs1 = dot2<T>(f.y, W4Ones<T>::bits, xs1);
+          xs0 = dot2<T>(f.z, W4Ones<T>::bits, xs0);
+          xs1 = dot2<T>(f.w, W4Ones<T>::bits, xs1);
         }
         const float xs = xs0 + xs1;
         xg[mt][c * NG + g] = xs + __shfl_xor(xs, 32, 64);

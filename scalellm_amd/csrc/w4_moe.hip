@@ -5,9 +5,8 @@
 // For every 32-row block b of the aligned token list (slm_moe_align_block with block_size 32):
 //     C[idx, :] = epilogue( A[idx / a_div, :] . dequant(W_e) ),  e = expert_ids[b], idx = sorted[b * 32 + r]
 // At decode an expert sees a handful of rows, so the call is a stream of the packed weights of the experts in
-// use: this is w4_small.hip's kernel -- 32 x 128 tiles, 4-chunk weight ring, post-scaled dequant through the
-// matrix pipe, SiLU*mul epilogue; read its header and comments for why the loads are issued in this order and
-// pinned with sched_barriers -- with three changes:
+// use: the 32-row weight stream of w4_stream32.h (32 x 128 tiles, 4-chunk weight ring, post-scaled dequant
+// through the matrix pipe), which w4_small.hip runs over dense rows.  What differs here:
 //   * the expert, and with it the base of the weights and of the scale table, is chosen per row tile;
 //   * the rows of A are gathered: each thread's two A pointers come from the sorted index list (the issue
 //     order and the 32-bit per-chunk offsets are unchanged);
@@ -15,7 +14,7 @@
 // No split-K (parallelism = blocks x N / 128), hence no workspace.  Workgroups whose block lies beyond the
 // device-side n_padded return at once: the grid is sized for the worst case so that a captured graph replays
 // for any routing.
-#include "w4_common.h"
+#include "w4_stream32.h"
 
 namespace slm {
 
@@ -39,29 +38,11 @@ struct MoeGemmKParams {
   int silu;
 };
 
-constexpr int MOE_STAGES = 2;
-constexpr int MOE_STAGE_BYTES = 32 * 256;
-constexpr int MOE_RING = 4;
-
-template <typename T>
-struct MoeOnes;
-template <>
-struct MoeOnes<bf16_tag> {
-  static constexpr uint32_t bits = 0x3F803F80u;
-};
-template <>
-struct MoeOnes<f16_tag> {
-  static constexpr uint32_t bits = 0x3C003C00u;
-};
-
-// NG / SPAN: as in w4_small.hip (scale groups per 128-deep chunk; groups wider than a chunk)
+// NG / SPAN: w4_stream32.h (scale groups per 128-deep chunk; groups wider than a chunk)
 template <typename T, int NG, bool SPAN>
 __global__ void __launch_bounds__(256, 2) w4a16_moe_gemm_kernel(const MoeGemmKParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_idx[32];  // the block's flat indices, for the scatter in the epilogue
-  typedef typename Mfma<T>::frag frag_t;
-  constexpr int WPG = 8 / NG;
-
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -75,11 +56,7 @@ __global__ void __launch_bounds__(256, 2) w4a16_moe_gemm_kernel(const MoeGemmKPa
   const bool nvalid = nt < n_tiles;
   if (!nvalid) nt = n_tiles - 1;  // clamped duplicate work, never stored
 
-  const int nC = p.n_chunks;  // >= 1
-  const int last = nC - 1;
-  auto clampc = [&](int c) { return c < last ? c : last; };
-
-  // ---- A staging: thread -> (row, 16-B slot) x 2 per chunk; the row comes from the sorted list ----
+  // ---- A: this thread's two (row, 16-B slot) sources of a chunk; the row comes from the sorted list ----
   const int32_t* blk = p.sorted + (int64_t)mb * 32;
   if (tid < 32) s_idx[tid] = blk[tid];
   const char* abase = reinterpret_cast<const char*>(p.a);
@@ -92,131 +69,17 @@ __global__ void __launch_bounds__(256, 2) w4a16_moe_gemm_kernel(const MoeGemmKPa
     const int fi = blk[row];
     const int64_t ar = (unsigned)fi < (unsigned)p.n_flat ? fi / p.a_div : 0;  // padding: a clamped row
     a_src[i] = abase + 2 * (ar * p.lda + slot * 8);
-    a_dst[i] = row * 256 + ((slot ^ (row & 15)) << 4);
+    a_dst[i] = s32_a_dst(row, slot);
   }
-  u32x4 areg[MOE_RING][2];
-  auto a_load = [&](int c, u32x4 (&dst)[2]) {
-    const uint32_t off = (uint32_t)clampc(c) * 256u;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) dst[i] = *reinterpret_cast<const u32x4*>(a_src[i] + off);
-  };
-  auto a_store = [&](int stage, const u32x4 (&src)[2]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      *reinterpret_cast<u32x4*>(smem + stage * MOE_STAGE_BYTES + a_dst[i]) = src[i];
-  };
 
-  // ---- weight / scale rings: the expert base is a 64-bit pointer, offsets inside an expert 32-bit ----
-  u32x4 wreg[MOE_RING][2];
-  uint32_t szreg[MOE_RING][NG];
+  // the expert base is a 64-bit pointer, offsets inside an expert 32-bit
   const char* wlane = p.wq + (int64_t)e * p.wq_stride + (nt * 64 + lane) * 16;
   const char* szlane = p.sz + (int64_t)e * p.sz_stride + (nt * 32 + (lane & 31)) * 4;
   const uint32_t wstride = (uint32_t)(n_tiles * 1024);  // bytes per 64-deep half chunk
   const uint32_t szstride = (uint32_t)(p.N * 4);        // bytes per scale group
   const int cpg_shift = p.gs_shift >= 30 ? 30 : (p.gs_shift > 7 ? p.gs_shift - 7 : 0);
-  auto w_load = [&](int c, u32x4 (&w)[2], uint32_t (&sz)[NG]) {
-    const uint32_t cc = (uint32_t)clampc(c);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-      w[h] = __builtin_nontemporal_load(
-          reinterpret_cast<const u32x4*>(wlane + (cc * 2 + h) * wstride));
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const uint32_t grp = NG > 1 ? cc * NG + g : (cc >> cpg_shift);
-      sz[g] = *reinterpret_cast<const uint32_t*>(szlane + grp * szstride);
-    }
-  };
-
-  // prologue in the order the steady-state iterations issue (w4_small.hip)
-  a_load(0, areg[0]);
-  w_load(0, wreg[0], szreg[0]);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int d = 1; d < MOE_RING; ++d) {
-    a_load(d, areg[d]);
-    __builtin_amdgcn_sched_barrier(0);
-    w_load(d, wreg[d], szreg[d]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  a_store(0, areg[0]);
-
-  f32x16 acc, tmp, tmpx;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = tmp[r] = tmpx[r] = 0.f;
-  const u32x4 ones4 = {MoeOnes<T>::bits, MoeOnes<T>::bits, MoeOnes<T>::bits, MoeOnes<T>::bits};
-  const frag_t ones = __builtin_bit_cast(frag_t, ones4);
-  uint32_t magic_v = W4Magic<T>::bits;
-  asm volatile("" : "+v"(magic_v));
-  uint32_t mask_s = 0x000F000Fu;
-  asm volatile("" : "+s"(mask_s));
-  const int mrow = lane & 31, kh = lane >> 5;
-  const int a_row = mrow * 256;
-  const int a_swz = mrow & 15;
-
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-
-  bool group_open = false;
-  int stage = 0;
-  const int n_iter = (nC + MOE_RING - 1) / MOE_RING * MOE_RING;
-  for (int base = 0; base < n_iter; base += MOE_RING) {
-#pragma unroll
-    for (int u = 0; u < MOE_RING; ++u) {
-      const int i = base + u;
-      a_load(i + MOE_RING, areg[u]);
-      __builtin_amdgcn_sched_barrier(0);
-      if (i < nC) {
-        const char* sbase = smem + stage * MOE_STAGE_BYTES + a_row;
-        const bool grp_ends = !SPAN || i == nC - 1 || ((i + 1) >> cpg_shift) != (i >> cpg_shift);
-        frag_t af = __builtin_bit_cast(
-            frag_t, *reinterpret_cast<const u32x4*>(sbase + (((0 * 2 + kh) ^ a_swz) << 4)));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          frag_t af_n = af;
-          if (j < 7)
-            af_n = __builtin_bit_cast(
-                frag_t, *reinterpret_cast<const u32x4*>(sbase + ((((j + 1) * 2 + kh) ^ a_swz) << 4)));
-          const u32x4 wv = wreg[u][j >> 2];
-          const uint32_t word = (j & 3) == 0 ? wv.x : (j & 3) == 1 ? wv.y : (j & 3) == 2 ? wv.z : wv.w;
-          uint32_t o[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            // a plain expression, not inline asm (w4_small.hip: hazards behind an asm statement)
-            const uint32_t x = q == 0 ? word : word >> (4 * q);
-            o[q] = (x & mask_s) | magic_v;
-          }
-          const u32x4 packed = {o[0], o[1], o[2], o[3]};
-          const frag_t bf = __builtin_bit_cast(frag_t, packed);
-          const bool g_first = (j % WPG) == 0 && !(SPAN && group_open);
-          if (g_first) {
-            f32x16 z;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            tmp = Mfma<T>::run(af, bf, z);
-            tmpx = Mfma<T>::run(af, ones, z);
-          } else {
-            tmp = Mfma<T>::run(af, bf, tmp);
-            tmpx = Mfma<T>::run(af, ones, tmpx);
-          }
-          const bool g_last = (j % WPG) == WPG - 1;
-          if (g_last && (!SPAN || grp_ends)) {
-            float sc, zm;
-            W4Magic<T>::decode(szreg[u][j / WPG], sc, zm);
-            const float nzs = -zm * sc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = fmaf(sc, tmp[r], fmaf(nzs, tmpx[r], acc[r]));
-          }
-          af = af_n;
-        }
-        if constexpr (SPAN) group_open = !grp_ends;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      w_load(i + MOE_RING, wreg[u], szreg[u]);
-      __builtin_amdgcn_sched_barrier(0);
-      a_store(stage ^ 1, areg[(u + 1) % MOE_RING]);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      stage ^= 1;
-    }
-  }
+  const f32x16 acc = w4_stream32<T, NG, SPAN>(smem, a_src, a_dst, wlane, szlane, wstride, szstride, cpg_shift, 0,
+                                              p.n_chunks, lane & 31, lane >> 5);
 
   // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5);
   // the row goes to C[idx]; s_idx was written before the first barrier
@@ -257,7 +120,7 @@ __global__ void __launch_bounds__(256, 2) w4a16_moe_gemm_kernel(const MoeGemmKPa
 template <typename T, int NG, bool SPAN>
 static void launch_moe_t(const MoeGemmKParams& kp, unsigned n_blocks, hipStream_t st) {
   hipLaunchKernelGGL((w4a16_moe_gemm_kernel<T, NG, SPAN>), dim3(n_blocks), dim3(256),
-                     MOE_STAGES * MOE_STAGE_BYTES, st, kp);
+                     S32_LDS_BYTES, st, kp);
 }
 
 template <typename T>
@@ -278,17 +141,15 @@ SLM_API int slm_moe_w4a16_gemm(const slm_moe_gemm_args* a, void* stream) {
   if (a->n_flat < 0 || a->K <= 0 || a->N <= 0 || a->a_div < 1 || a->n_experts < 1 || a->max_blocks < 0)
     return SLM_ERR_INVALID_ARG;
   if (a->dtype != SLM_F16 && a->dtype != SLM_BF16) return SLM_ERR_UNSUPPORTED;
-  const int base = a->format & SLM_W4_FORMAT_MASK;
-  if (a->format & ~(SLM_W4_FORMAT_MASK | SLM_W4_PAIRED)) return SLM_ERR_INVALID_ARG;
-  if (base != SLM_W4_GPTQ && base != SLM_W4_AWQ) return SLM_ERR_UNSUPPORTED;  // 8-bit planes need the column gather
+  if (!w4_format_bits_ok(a->format)) return SLM_ERR_INVALID_ARG;
+  if (!w4_format_valid(a->format)) return SLM_ERR_UNSUPPORTED;  // 8-bit planes need the column gather
   if (a->perm || a->bias) return SLM_ERR_UNSUPPORTED;
   if (a->K % W4_KC || a->N % 64) return SLM_ERR_UNSUPPORTED;
   if (a->flags & ~SLM_W4_SILU_MUL) return SLM_ERR_INVALID_ARG;
   const bool silu = (a->flags & SLM_W4_SILU_MUL) != 0;
   if (silu && (!(a->format & SLM_W4_PAIRED) || a->row_scale)) return SLM_ERR_INVALID_ARG;
   const int64_t gs = a->group_size;
-  if (!(gs == 32 || gs == 64 || (gs >= 128 && is_pow2(gs)) || gs == a->K)) return SLM_ERR_UNSUPPORTED;
-  if (a->K % gs) return SLM_ERR_UNSUPPORTED;
+  if (!w4_group_size_valid(gs, a->K)) return SLM_ERR_UNSUPPORTED;
   // 32-bit offsets inside one expert (w4_small.hip's rules, per expert); flat indices are int32
   if (a->K * a->N / 2 >= ((int64_t)1 << 32) || (a->K / gs) * a->N * 4 >= ((int64_t)1 << 32) ||
       a->n_flat >= ((int64_t)1 << 31) - 256)

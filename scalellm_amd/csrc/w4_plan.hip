@@ -20,10 +20,7 @@ static int validate(const slm_w4_gemm_args* a) {
     if (a->flags & SLM_W4_DEFER_REDUCE) return SLM_ERR_INVALID_ARG;
     if (a->N % 64) return SLM_ERR_UNSUPPORTED;
   }
-  const int64_t gs = a->group_size;
-  if (!(gs == 32 || gs == 64 || (gs >= 128 && gs % 128 == 0 && is_pow2(gs)) || gs == a->K))
-    return SLM_ERR_UNSUPPORTED;
-  if (a->K % gs) return SLM_ERR_UNSUPPORTED;
+  if (!w4_group_size_valid(a->group_size, a->K)) return SLM_ERR_UNSUPPORTED;
   return SLM_OK;
 }
 

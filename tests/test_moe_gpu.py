@@ -315,6 +315,54 @@ def test_grouped_gemm_row_scale(bits):
         assert _rel_err(o, want) < GEMM_TOL[bits]
 
 
+# The grouped kernel and the dense lean kernel (w4_small.hip) run one main loop (csrc/w4_stream32.h): the same
+# arithmetic in the same order, so they agree bit for bit.  (rows of expert 0, rows of expert 1, K, N, group, silu);
+# every expert has >= 2 rows: M = 1 plans the GEMV.
+STREAM_CASES = [
+    (17, 5, 256, 192, 128, False),    # two chunks < the ring of four; the last workgroup: two valid, two clamped waves
+    (32, 2, 640, 64, 32, False),      # five chunks, four scale groups per chunk
+    (9, 31, 640, 128, 64, False),     # two scale groups per chunk
+    (3, 20, 1024, 64, 256, False),    # groups spanning chunks
+    (6, 11, 384, 64, 384, False),     # per-channel, K no power of two
+    (8, 12, 256, 128, 128, True),     # paired experts, SiLU*mul epilogue on both sides
+]
+
+
+@pytest.mark.parametrize("bits", ["bf16", "f16"])
+@pytest.mark.parametrize("n", range(len(STREAM_CASES)))
+def test_grouped_gemm_is_bit_identical_to_the_dense_lean_kernel(n, bits):
+    from scalellm_amd import _lib, kernels
+    r0, r1, K, N, gs, silu = STREAM_CASES[n]
+    fmt = ("awq", "gptq")[(n + (bits == "f16")) % 2]                 # alternating; each case sees both over the dtypes
+    dt, T = _dt(bits), r0 + r1
+    packed = [helpers.pack_case(helpers.make_quant_case(7000 + 10 * n + e, K, N, gs, fmt, bits), bits, paired=silu)
+              for e in range(2)]
+    experts = kernels.moe_stack_experts(packed, _lib.SLM_W4_AWQ if fmt == "awq" else _lib.SLM_W4_GPTQ)
+    # top-1 routing by hand: expert 1 takes r1 tokens spread over the batch, so both experts gather
+    assert np.gcd(7, T) == 1
+    ids = np.array([0] * r0 + [1] * r1, np.int32)[(np.arange(T) * 7) % T]
+    cap, blocks = kernels.moe_align_capacity(T, 2, 32)
+    srt = torch.empty(cap, dtype=torch.int32, device=DEV)
+    eid = torch.empty(blocks, dtype=torch.int32, device=DEV)
+    npad = torch.empty(1, dtype=torch.int32, device=DEV)
+    kernels.moe_align_block(torch.from_numpy(ids).to(DEV), 2, 32, srt, eid, npad)
+    g = torch.Generator(device=DEV).manual_seed(n)
+    a = torch.randn(T, K, device=DEV, dtype=dt, generator=g)
+    n_out = N // 2 if silu else N
+    out = torch.full((T, n_out), float("nan"), device=DEV, dtype=dt)
+    kernels.moe_w4_grouped_gemm(a, experts, out, srt, eid, npad, 1, silu_mul=silu)
+    for e, rows in enumerate((r0, r1)):
+        idx = torch.from_numpy(np.nonzero(ids == e)[0]).to(DEV)
+        assert idx.numel() == rows
+        a_e = a[idx].contiguous()
+        want = torch.full((rows, n_out), float("nan"), device=DEV, dtype=dt)
+        with kernels.tuning(SLM_W4_KS=0, SLM_W4_SPLITK=1):
+            assert kernels.w4_plan(a_e, experts.expert(e), want, silu_mul=silu).kernel_name == "SMALL"
+            kernels.gptq_gemm(a_e, experts.expert(e), want, silu_mul=silu)
+        assert not bool(torch.isnan(want).any())
+        assert torch.equal(out[idx], want), (STREAM_CASES[n], fmt, e)
+
+
 # ---- FusedMoE end to end -----------------------------------------------------------------------------
 HID, INTER, NE, TOPK = 256, 384, 8, 2
 
