@@ -264,3 +264,133 @@ def dense_weight8(case) -> np.ndarray:
     K, gs = case["K"], case["group_size"]
     gi = case["g_idx"] if case["g_idx"] is not None else np.arange(K) // gs
     return case["scales"][gi] * (case["q"] - case["z_eff"][gi]).astype(np.float32)
+
+
+# ---- inputs on which the int4 GEMM is exact (tests/test_w4_exact_*.py) ----------------------------
+# Small-integer activations, power-of-two scales and a bias that is a multiple of the smallest scale: every
+# product and every partial sum is then representable in fp32, so the result does not depend on the order of
+# summation, on split-K / stream-K pieces or on the dequant form, and every kernel owes RNE_T(exact sum + bias)
+# in every element, bit for bit.  assert_exact_budget() checks that a case really is inside that regime.
+EXACT_MAGIC = {"bf16": 128, "f16": 1024}       # the magic number of the post-scaled form (csrc/w4_common.h)
+EXACT_MANT = {"bf16": 8, "f16": 11}            # significant bits of T
+EXACT_SCALE_EXPS = {"bf16": (-2, -1, 0), "f16": (-1, 0)}
+EXACT_XMAX = {"bf16": 2, "f16": 1}
+
+
+def _t_bits(x: np.ndarray, dtype_bits: str) -> np.ndarray:
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    return f32_to_bf16_bits(x) if dtype_bits == "bf16" else x.astype(np.float16).view(np.uint16)
+
+
+def _from_t_bits(u16: np.ndarray, dtype_bits: str) -> np.ndarray:
+    return bf16_bits_to_f32(u16) if dtype_bits == "bf16" else f16_bits_to_f32(u16)
+
+
+def _pow2_scales(rng, shape, scale_exps, dtype_bits):
+    s = np.exp2(rng.choice(np.asarray(scale_exps, np.int64), size=shape)).astype(np.float32)
+    return s, _t_bits(s, dtype_bits)
+
+
+def make_exact_quant_case(seed, K, N, group_size, fmt, dtype_bits="bf16", act_order=False, scale_exps=None):
+    """make_quant_case() with power-of-two scales drawn per (group, column) from 2 ** scale_exps; nibbles and zero
+    points stay fully random (GPTQ: stored zeros of 15 give z = 16).  Same dict, plus dtype_bits."""
+    d = make_quant_case(seed, K, N, group_size, fmt, dtype_bits, act_order=act_order)
+    rng = np.random.default_rng([seed, 0x5CA1E])
+    exps = EXACT_SCALE_EXPS[dtype_bits] if scale_exps is None else scale_exps
+    s, s_bits = _pow2_scales(rng, d["scales"].shape, exps, dtype_bits)
+    d.update(scales=s, scales_bits=s_bits, dtype_bits=dtype_bits)
+    return d
+
+
+def make_exact_quant8_case(seed, K, N, group_size, fmt, dtype_bits="bf16", act_order=False, sym=False,
+                           scale_exps=(0,)):
+    """make_quant8_case() with power-of-two scales (one value per case by default: the two planes already cost a
+    factor of 32 of the exactness budget)."""
+    d = make_quant8_case(seed, K, N, group_size, fmt, dtype_bits, act_order=act_order, sym=sym)
+    rng = np.random.default_rng([seed, 0x5CA1E])
+    s, s_bits = _pow2_scales(rng, d["scales"].shape, scale_exps, dtype_bits)
+    d.update(scales=s, scales_bits=s_bits, dtype_bits=dtype_bits)
+    return d
+
+
+def exact_activations(seed, M, K, xmax, nonzero=None):
+    """[M, K] fp32 integers in [-xmax, xmax]; every aligned run of 16 along K of every row holds a non-zero, so a
+    dropped k-step cannot hide behind zeros.  nonzero: share of non-zero entries (default: uniform integers)."""
+    rng = np.random.default_rng([seed, 0xAC7])
+    a = rng.integers(-xmax, xmax + 1, size=(M, K)).astype(np.float32)
+    if nonzero is not None:
+        a *= rng.random((M, K)) < nonzero
+    runs = a.reshape(M, K // 16, 16)
+    r, c = np.nonzero(~runs.any(axis=2))
+    runs[r, c, rng.integers(0, 16, size=r.size)] = rng.choice([-1.0, 1.0], size=r.size)
+    return a
+
+
+def exact_bias(seed, N, case, big=False):
+    """[N] fp32: integer multiples of the smallest scale, representable in T.  big: magnitudes of
+    (2^(p-1) ... 2^p - 1) * 2 * s_min (p = significant bits of T), which push the sums past T's precision."""
+    rng = np.random.default_rng([seed, 0xB1A5])
+    s_min, p = float(case["scales"].min()), EXACT_MANT[case["dtype_bits"]]
+    if big:
+        m = rng.integers(1 << (p - 1), 1 << p, size=N) * 2 * rng.choice([-1, 1], size=N)
+    else:
+        m = rng.integers(-8, 9, size=N)
+    return (m * s_min).astype(np.float32)
+
+
+def _exact_weight(case) -> np.ndarray:
+    K, gs = case["K"], case["group_size"]
+    gi = case["g_idx"] if case["g_idx"] is not None else np.arange(K) // gs
+    return (case["q"] - case["z_eff"][gi]).astype(np.float64) * case["scales"][gi].astype(np.float64)
+
+
+def exact_truth(a, case, bias=None):
+    """float64 a @ ((q - z[g]) * s[g]) + bias (exact: integers times powers of two, sums far below 2^53), and the
+    share of its elements that are not representable in T, i.e. that the kernel has to round."""
+    truth = np.asarray(a, np.float64) @ _exact_weight(case)
+    if bias is not None:
+        truth = truth + np.asarray(bias, np.float64)[None, :]
+    t32 = truth.astype(np.float32)
+    assert np.array_equal(t32.astype(np.float64), truth)
+    bits = _t_bits(t32, case["dtype_bits"])
+    return truth, float((_from_t_bits(bits, case["dtype_bits"]) != t32).mean())
+
+
+def assert_exact_budget(a, case, bias=None, bits=22):
+    """For every activation row: (sum_k |x_k| (magic + 16) s_max + |bias|_max) / s_min < 2^bits (x 32 for the two
+    planes of an 8-bit layer, whose high plane carries 16 s) -- two spare bits below fp32's 24 -- and the density
+    rule of exact_activations()."""
+    a = np.asarray(a)
+    assert np.array_equal(a, np.rint(a)) and a.shape[1] == case["K"] and case["K"] % 16 == 0
+    assert a.reshape(a.shape[0], -1, 16).any(axis=2).all(), "an aligned run of 16 activations is all zero"
+    s = case["scales"]
+    assert np.array_equal(np.exp2(np.rint(np.log2(s))), s), "scales must be powers of two"
+    s_min, s_max = float(s.min()), float(s.max())
+    planes = 32 if case.get("bits") == 8 else 1
+    b_max = float(np.abs(bias).max()) if bias is not None else 0.0
+    if bias is not None:
+        m = np.asarray(bias, np.float64) / s_min
+        assert np.array_equal(m, np.rint(m)), "bias must be a multiple of the smallest scale"
+        assert np.array_equal(_from_t_bits(_t_bits(bias, case["dtype_bits"]), case["dtype_bits"]),
+                              np.asarray(bias, np.float32)), "bias must be representable in T"
+    worst = float(np.abs(a).sum(axis=1).max()) * (EXACT_MAGIC[case["dtype_bits"]] + 16) * s_max * planes
+    assert (worst + b_max) / s_min < 2.0 ** bits, ((worst + b_max) / s_min, 2.0 ** bits)
+
+
+def assert_bits_equal(out, truth, T, what=""):
+    """Every element of `out` (a torch tensor of dtype T, any device) against RNE_T(truth) as 16-bit patterns.  The
+    failure message gives the number of wrong elements, the bounding box of their rows and columns and the first
+    few (row, column, got, want): a tile edge, a K slice and a scattered row look different there."""
+    import torch
+    want = torch.from_numpy(np.ascontiguousarray(truth)).to(T)
+    assert out.dtype == T and tuple(out.shape) == tuple(want.shape), (what, out.dtype, tuple(out.shape), tuple(want.shape))
+    got = out.detach().cpu().contiguous()
+    bad = (got.view(torch.int16) != want.view(torch.int16)).numpy()
+    if not bad.any():
+        return
+    r, c = np.nonzero(bad)
+    first = [(int(i), int(j), float(got[i, j]), float(want[i, j])) for i, j in zip(r[:6], c[:6])]
+    raise AssertionError(
+        f"{what}: {r.size} of {bad.size} elements differ from RNE(exact); rows [{r.min()}, {r.max()}] "
+        f"({np.unique(r).size} distinct), columns [{c.min()}, {c.max()}] ({np.unique(c).size} distinct); "
+        f"first (row, column, got, want): {first}")

@@ -7,6 +7,10 @@ Structure follows the reference's tests:
   * tests/kernels/marlin_repack_test.py:16-84 (repack bit-exact) -- the Marlin byte layout is an
     NVIDIA artefact, so bit-exactness is asserted on our layout through the dequant round trip
   * src/layers/quantization/qlinear_impl_test.cpp:10-98 (GPTQ fixture; linear vs dequant+matmul)
+What the mean metric does NOT see: a localized error -- a ragged last row or column tile, one workgroup's K
+slice, one stream-K piece, a bias missing on a clamped tile -- moves a mean over the whole output by less than
+the bound (tests/test_w4_exact_cpu.py asserts it on injected faults).  tests/test_w4_exact_gpu.py closes that
+gap: the same kernels on exactly representable inputs, every element compared bit for bit.
 The reference never tested zero points (marlin_gemm_test.py:97 "TODO: test with zero point");
 we do (AWQ asymmetric, GPTQ arbitrary stored zeros).
 """
