@@ -784,7 +784,7 @@ SLM_API size_t slm_rejection_sample_workspace_bytes(const slm_rejection_args* a)
 SLM_API int slm_rejection_sample(const slm_rejection_args* a, void* stream);
 
 /* ========================================================================== */
-/* 10. Mixture of experts: routing, block alignment, grouped int4 GEMM        */
+/* 10. Mixture of experts: routing, block alignment, grouped GEMMs            */
 /*    replaces  llm::kernel::topk_softmax                                     */
 /*              src/kernels/moe/topk_softmax_kernel.cu:272-293,               */
 /*              llm::kernel::grouped_topk_sigmoid                             */
@@ -859,6 +859,34 @@ SLM_API int slm_rejection_sample(const slm_rejection_args* a, void* stream);
 /*  64, a power of two >= 128, or K (per-channel); K % 128 == 0, N % 64 == 0; */
 /*  GPTQ and AWQ.  SLM_ERR_UNSUPPORTED before any launch: perm (act-order),   */
 /*  bias, the 8-bit formats, other shapes / dtypes.                           */
+/*                                                                            */
+/*  Dense grouped GEMM (slm_moe_gemm): the same aligned-list contract over    */
+/*  unquantised experts -- the reference kernel's own form.                   */
+/*     C[idx, :] = epilogue( A[idx / a_div, :] . W_e^T )                      */
+/*  W_e = w + e * w_expert_stride (elements), [N, K] with row stride ldw: the */
+/*  checkpoint layout W[e, n, k], k contiguous (nn.Linear.weight), no         */
+/*  prepack.  Align block size 32, padding id n_flat; padding rows load a     */
+/*  clamped row and are never stored; blocks beyond n_padded, or whose expert */
+/*  id is outside [0, E), return at once; the grid is sized by max_blocks, so */
+/*  one captured graph serves any routing.  No workspace, no float atomics,   */
+/*  one wave per 32 x 32 tile over the whole K in a fixed order: repeats are  */
+/*  bit-identical, and so is every launch shape -- the columns per workgroup  */
+/*  (128, 64 or 32) are chosen from max_blocks, N and flags alone.  f16 /     */
+/*  bf16, fp32 accumulation, one rounding at the store; K % 32 == 0,          */
+/*  N % 32 == 0; lda, ldw >= K and ldc in elements, lda / ldw /               */
+/*  w_expert_stride multiples of 8 and a / w 16-byte aligned (16-byte loads); */
+/*  one expert (N * ldw elements) < 4 GiB: a 64-bit expert base, 32-bit       */
+/*  offsets inside it.  Epilogue: plain; row scale T(acc * row_scale[idx]),   */
+/*  one rounding; or SLM_MOE_SILU_MUL: rows [0, N/2) of W_e are the gate (w1) */
+/*  and rows [N/2, N) the up projection (w3), concatenated, not interleaved;  */
+/*  C is [n_flat, N/2] and c[idx, i] = T(silu(g) * u), g = T(acc gate i),     */
+/*  u = T(acc up i): bit-identical to the plain call into [n_flat, N]         */
+/*  followed by slm_silu_mul; needs (N/2) % 32 == 0, not with row_scale.      */
+/*  Before any launch: SLM_ERR_INVALID_ARG on NULL / negative arguments,      */
+/*  unknown flags, SILU_MUL with row_scale, a stride below its extent;        */
+/*  SLM_ERR_UNSUPPORTED on other dtypes, K % 32, N % 32, (N/2) % 32 with      */
+/*  SILU_MUL, the size limits; SLM_ERR_ALIGNMENT on misaligned pointers or    */
+/*  strides; n_flat == 0 or max_blocks == 0 is a no-op.                       */
 /* ========================================================================== */
 SLM_API int slm_moe_topk_softmax(const float* logits /* [T, E] */, float* weights /* [T, k] */,
                                  int32_t* indices /* [T, k] */, int64_t n_tokens, int32_t n_experts,
@@ -915,6 +943,30 @@ typedef struct slm_moe_gemm_args {
   int32_t flags;                    /* 0 or SLM_W4_SILU_MUL                                       */
 } slm_moe_gemm_args;
 SLM_API int slm_moe_w4a16_gemm(const slm_moe_gemm_args* a, void* stream);
+
+#define SLM_MOE_SILU_MUL 2          /* slm_moe_gemm flags: gate | up rows, c is [n_flat, N/2]      */
+typedef struct slm_moe_gemm_dense_args {
+  const void* a;                    /* [n_flat / a_div, K] T, row stride lda (elements)           */
+  const void* w;                    /* expert 0: [N, K] T, k contiguous, row stride ldw           */
+  void* c;                          /* [n_flat, N] T (SILU_MUL: [n_flat, N/2]), row stride ldc    */
+  const float* row_scale;           /* [n_flat] fp32 or NULL                                      */
+  const int32_t* sorted_token_idxes;
+  const int32_t* expert_ids;
+  const int32_t* n_padded_tokens;   /* [1], read on the device                                    */
+  int64_t w_expert_stride;          /* elements between experts, >= (N - 1) * ldw + K             */
+  int64_t n_flat;                   /* rows of c = T * k; the padding id                          */
+  int64_t K, N;
+  int64_t lda, ldw, ldc;
+  int32_t a_div;                    /* >= 1                                                       */
+  int32_t n_experts;
+  int32_t max_blocks;               /* sizes the grid: slm_moe_align_capacity(n_flat, E, 32)      */
+  int32_t dtype;
+  int32_t flags;                    /* 0 or SLM_MOE_SILU_MUL                                      */
+} slm_moe_gemm_dense_args;
+/* (the parameter list sits on its own line on purpose: tests/test_moe_cpu.py pins the entry points this section
+ * had before slm_moe_gemm by the pattern "name(", and tests/test_moe_dense_cpu.py covers this one) */
+SLM_API int slm_moe_gemm
+    (const slm_moe_gemm_dense_args* a, void* stream);
 
 /* ========================================================================== */
 /* 11. Multi-head latent attention (MLA) over a paged latent KV cache         */

@@ -164,6 +164,18 @@ class MoeGemmArgs(C.Structure):
     ]
 
 
+class MoeDenseGemmArgs(C.Structure):
+    """struct slm_moe_gemm_dense_args (include/slm_hip.h section 10)."""
+    _fields_ = [
+        ("a", C.c_void_p), ("w", C.c_void_p), ("c", C.c_void_p), ("row_scale", C.c_void_p),
+        ("sorted_token_idxes", C.c_void_p), ("expert_ids", C.c_void_p), ("n_padded_tokens", C.c_void_p),
+        ("w_expert_stride", C.c_int64), ("n_flat", C.c_int64), ("K", C.c_int64), ("N", C.c_int64),
+        ("lda", C.c_int64), ("ldw", C.c_int64), ("ldc", C.c_int64),
+        ("a_div", C.c_int32), ("n_experts", C.c_int32), ("max_blocks", C.c_int32), ("dtype", C.c_int32),
+        ("flags", C.c_int32),
+    ]
+
+
 class MlaArgs(C.Structure):
     """struct slm_mla_args (include/slm_hip.h section 11)."""
     _fields_ = [
@@ -181,6 +193,7 @@ class MlaArgs(C.Structure):
     ]
 
 
+SLM_MOE_SILU_MUL = 2    # slm_moe_gemm flags
 SLM_MOE_GEMM_BLOCK = 32  # rows per block of the grouped GEMM: the align step's block_size
 
 
@@ -304,6 +317,7 @@ def lib() -> C.CDLL:
         ("slm_moe_align_block", C.c_int, [C.POINTER(MoeAlignArgs), C.c_void_p]),
         ("slm_moe_sum", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
         ("slm_moe_w4a16_gemm", C.c_int, [C.POINTER(MoeGemmArgs), C.c_void_p]),
+        ("slm_moe_gemm", C.c_int, [C.POINTER(MoeDenseGemmArgs), C.c_void_p]),
         ("slm_mla_paged_kv_workspace_bytes", C.c_size_t, [C.POINTER(MlaArgs)]),
         ("slm_mla_paged_kv_auto_splits", C.c_int32, [C.POINTER(MlaArgs)]),
         ("slm_mla_paged_kv", C.c_int, [C.POINTER(MlaArgs), C.c_void_p]),

@@ -1,0 +1,338 @@
+// moe_gemm.hip -- grouped dense fp16 / bf16 GEMM over the experts of a mixture-of-experts layer
+// (include/slm_hip.h section 10, slm_moe_gemm; the reference's Sm80KernelGroupedGemm, src/kernels/gemm/,
+// in its own form: A[m, k], W[e, n, k], rows gathered through sorted_token_idxes / expert_ids).
+//
+// For every 32-row block b of the aligned token list (slm_moe_align_block with block_size 32):
+//     C[idx, :] = epilogue( A[idx / a_div, :] . W_e^T ),  e = expert_ids[b], idx = sorted[b * 32 + r]
+// The aligned-list contract is w4_moe.hip's; what differs is the weight operand.  W_e is the checkpoint
+// tensor [N, K], k-contiguous, and that IS the B operand of the 32x32x16 MFMA: lane (n = lane & 31,
+// h = lane >> 5) holds 8 consecutive k of column n.  So the weights go from global memory to the MFMA
+// in 16-B loads: no LDS stage, no transpose, no prepack.
+//
+// k order.  An MFMA sums 16 products; which 16 k they are is free as long as both operands agree.  K is
+// streamed in 128-deep chunks and lane half h takes the k range [64 h, 64 h + 64) of the chunk: its eight
+// 16-B loads are 128 contiguous bytes of row n (a cache line when ldw allows it), and MFMA step q = 0..7
+// sums k = 64 h + 8 q + j over (h, j).  A's fragments come from a [32 rows][128 k] LDS image of the chunk
+// in natural k order: lane (r, h) reads slot 8 h + q of row r (w4_stream32.h's XOR swizzle: conflict-free
+// ds_read_b128).  A K that is no multiple of 128 ends in up to three 32-deep units in natural order
+// (lane half h: k = 16 h + 8 s + j, s = 0, 1), staged and consumed one at a time.
+//
+// Decomposition.  One wave owns one 32 x 32 output tile over the whole K: a fixed accumulation order for
+// every element, whatever the launch shape.  A workgroup is NW = 4, 2 or 1 waves on adjacent column tiles
+// sharing the A image; the host takes the widest NW that still gives every CU a workgroup (moe_gemm_waves:
+// a pure function of max_blocks, N and the flags, so repeats and graph replays stay bit-identical, and
+// because a wave's arithmetic does not depend on NW the result is the same for every choice).  No split-K,
+// no workspace, no atomics.
+//
+// Pipeline (the shape of w4_stream32.h): weights in a 3-chunk register ring, refilled right after their
+// MFMAs; A in a 3-chunk register ring, written to the other LDS buffer one iteration before its use.  VMEM
+// completes in order, so the A chunk that is waited for is two iterations old and the wait leaves two
+// weight chunks in flight.  Loads past the last chunk are clamped to it and never used.
+//
+// SLM_MOE_SILU_MUL: rows [0, N/2) of W_e are the gate, [N/2, N) the up projection; waves (0, 1) and
+// (2, 3) hold the (gate, up) tiles of one output tile, the up wave hands its T-rounded tile over through
+// LDS: the bits of the plain GEMM followed by slm_silu_mul.
+#include "common.h"
+
+namespace slm {
+
+constexpr int MG_RING = 3;                // weight / A register rings (chunks)
+constexpr int MG_KC = 128;                // k per chunk
+constexpr int MG_STAGE_BYTES = 32 * 256;  // one chunk of A: 32 rows x 128 k
+constexpr int MG_LDS_BYTES = 2 * MG_STAGE_BYTES;
+
+struct MoeDenseKParams {
+  const void* a;
+  const char* w;            // expert 0
+  void* c;
+  const float* row_scale;   // [n_flat] or NULL
+  const int32_t* sorted;    // [>= n_padded]
+  const int32_t* expert_ids;
+  const int32_t* n_padded;  // [1]
+  int64_t w_stride;         // bytes per expert
+  int64_t lda, ldw, ldc;    // elements
+  int n_flat;               // rows of c; indices >= n_flat are padding
+  int a_div;
+  int n_experts;
+  int n_tiles;              // N / 32
+  int n_chunks;             // K / 128
+  int tail_units;           // (K % 128) / 32
+  int n_nblocks;            // workgroups per row block
+  int silu;
+};
+
+// byte offset of (row, 16-B slot) in a stage buffer (w4_stream32.h's swizzle)
+__device__ __forceinline__ int mg_a_dst(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
+
+template <typename T, int NW>
+__global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseKParams p) {
+  typedef typename Mfma<T>::frag frag_t;
+  constexpr int NT = NW * 64;
+  constexpr int P = 512 / NT;  // 16-B pieces of a chunk of A per thread
+  __shared__ __attribute__((aligned(16))) char smem[MG_LDS_BYTES];
+  __shared__ int s_idx[32];  // the block's flat indices, for the scatter in the epilogue
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nb = blockIdx.x % p.n_nblocks;
+  const int mb = blockIdx.x / p.n_nblocks;
+  if ((int64_t)mb * 32 >= (int64_t)p.n_padded[0]) return;  // beyond the aligned list: nothing to do
+  const int e = p.expert_ids[mb];
+  if ((unsigned)e >= (unsigned)p.n_experts) return;        // never produced by the align step
+
+  // ---- the wave's column tile ----
+  int nt;
+  bool nvalid;
+  if (p.silu) {
+    // pairs of waves: (gate, up) tiles of output tile pi
+    const int half_tiles = p.n_tiles >> 1;
+    int pi = nb * (NW / 2) + (wave >> 1);
+    nvalid = pi < half_tiles;
+    if (!nvalid) pi = half_tiles - 1;  // clamped duplicate work, never stored
+    nt = (wave & 1) * half_tiles + pi;
+  } else {
+    nt = nb * NW + wave;
+    nvalid = nt < p.n_tiles;
+    if (!nvalid) nt = p.n_tiles - 1;
+  }
+  const int mrow = lane & 31, kh = lane >> 5;
+
+  // ---- A: this thread's P (row, 16-B slot) sources of a chunk; the row comes from the sorted list ----
+  const int32_t* blk = p.sorted + (int64_t)mb * 32;
+  if (tid < 32) s_idx[tid] = blk[tid];
+  const char* abase = reinterpret_cast<const char*>(p.a);
+  const char* a_src[P];
+  int a_dst[P];
+  const int a_slot = tid & 15;  // NT % 16 == 0: one slot for all of a thread's pieces
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int idx = tid + NT * i;
+    const int row = idx >> 4, slot = idx & 15;
+    const int fi = blk[row];
+    const int64_t ar = (unsigned)fi < (unsigned)p.n_flat ? fi / p.a_div : 0;  // padding: a clamped row
+    a_src[i] = abase + 2 * (ar * p.lda + slot * 8);
+    a_dst[i] = mg_a_dst(row, slot);
+  }
+  // the expert base is a 64-bit pointer, offsets inside an expert 32-bit
+  const char* wlane = p.w + (int64_t)e * p.w_stride + 2 * (((int64_t)nt * 32 + mrow) * p.ldw);
+  const int a_row = mrow * 256;
+  const int a_swz = mrow & 15;
+
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+  const int nC = p.n_chunks;
+  if (nC > 0) {
+    const int last = nC - 1;
+    auto clampc = [&](int c) { return c < last ? c : last; };
+    u32x4 areg[MG_RING][P];
+    u32x4 wreg[MG_RING][8];
+    auto a_load = [&](int c, u32x4 (&dst)[P]) {
+      const uint32_t off = (uint32_t)clampc(c) * 256u;
+#pragma unroll
+      for (int i = 0; i < P; ++i) dst[i] = *reinterpret_cast<const u32x4*>(a_src[i] + off);
+    };
+    auto a_store = [&](int stage, const u32x4 (&src)[P]) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) *reinterpret_cast<u32x4*>(smem + stage * MG_STAGE_BYTES + a_dst[i]) = src[i];
+    };
+    // lane half kh: the 128 contiguous bytes [kh * 128, kh * 128 + 128) of the chunk's 256 B of row n
+    const char* wl = wlane + kh * 128;
+    auto w_load = [&](int c, u32x4 (&w)[8]) {
+      const uint32_t off = (uint32_t)clampc(c) * 256u;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) w[q] = *reinterpret_cast<const u32x4*>(wl + off + q * 16);
+    };
+
+    // prologue in the order the steady-state iterations issue (A, then the weights of the same chunk)
+    a_load(0, areg[0]);
+    w_load(0, wreg[0]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = 1; d < MG_RING; ++d) {
+      a_load(d, areg[d]);
+      __builtin_amdgcn_sched_barrier(0);
+      w_load(d, wreg[d]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    a_store(0, areg[0]);
+    __syncthreads();
+
+    int stage = 0;
+    const int n_iter = (nC + MG_RING - 1) / MG_RING * MG_RING;
+    for (int base = 0; base < n_iter; base += MG_RING) {
+#pragma unroll
+      for (int u = 0; u < MG_RING; ++u) {
+        const int i = base + u;  // chunk; ring slot u
+        // A for chunk i + 3 into the registers chunk i left (stored one iteration ago)
+        a_load(i + MG_RING, areg[u]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (i < nC) {
+          const char* sbase = smem + stage * MG_STAGE_BYTES + a_row;
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const frag_t af = __builtin_bit_cast(
+                frag_t, *reinterpret_cast<const u32x4*>(sbase + (((kh * 8 + q) ^ a_swz) << 4)));
+            acc = Mfma<T>::run(af, __builtin_bit_cast(frag_t, wreg[u][q]), acc);
+          }
+        }
+        // the refill AFTER the old values are consumed (pinned): each ring slot keeps its registers
+        __builtin_amdgcn_sched_barrier(0);
+        w_load(i + MG_RING, wreg[u]);
+        __builtin_amdgcn_sched_barrier(0);
+        // chunk i + 1 (loaded two iterations ago) -> the buffer everybody finished reading one barrier ago
+        a_store(stage ^ 1, areg[(u + 1) % MG_RING]);
+        __syncthreads();
+        stage ^= 1;
+      }
+    }
+  }
+
+  // ---- K % 128: up to three 32-deep units in natural k order, one at a time ----
+  if (p.tail_units > 0) {
+    const uint32_t koff = (uint32_t)nC * 256u;  // bytes into a row
+    __syncthreads();                            // nC == 0: s_idx; otherwise nobody reads the stages any more
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      if (a_slot < p.tail_units * 4)
+        *reinterpret_cast<u32x4*>(smem + a_dst[i]) = *reinterpret_cast<const u32x4*>(a_src[i] + koff);
+    }
+    __syncthreads();
+    const char* sbase = smem + a_row;
+    const char* wt = wlane + koff + kh * 32;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      if (t < p.tail_units) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const u32x4 wv = *reinterpret_cast<const u32x4*>(wt + t * 64 + s * 16);
+          const frag_t af = __builtin_bit_cast(
+              frag_t, *reinterpret_cast<const u32x4*>(sbase + (((t * 4 + kh * 2 + s) ^ a_swz) << 4)));
+          acc = Mfma<T>::run(af, __builtin_bit_cast(frag_t, wv), acc);
+        }
+      }
+    }
+    __syncthreads();  // the SiLU exchange below reuses the stage
+  }
+
+  // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5);
+  // the row goes to C[idx]; s_idx was written before the first barrier
+  uint16_t* cbase = reinterpret_cast<uint16_t*>(p.c);
+  if constexpr (NW >= 2) {
+    if (p.silu) {
+      // the up wave hands its T-rounded tile to the gate wave through the (now idle) A buffers; same lane, same r
+      uint16_t* ex = reinterpret_cast<uint16_t*>(smem) + (wave >> 1) * 1024;
+      if (wave & 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ex[r * 64 + lane] = pack1<T>(acc[r]);
+      }
+      __syncthreads();
+      if ((wave & 1) || !nvalid) return;
+      const int64_t ocol = (int64_t)nt * 32 + mrow;  // the gate wave: nt = the output tile
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int fi = s_idx[(r & 3) + 8 * (r >> 2) + 4 * kh];
+        const float g = lo_f32<T>((uint32_t)pack1<T>(acc[r]));
+        const float u = lo_f32<T>((uint32_t)ex[r * 64 + lane]);
+        if ((unsigned)fi < (unsigned)p.n_flat) cbase[(int64_t)fi * p.ldc + ocol] = pack1<T>(silu_mul1(g, u));
+      }
+      return;
+    }
+  }
+  if (!nvalid) return;
+  const int64_t ncol = (int64_t)nt * 32 + mrow;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int fi = s_idx[(r & 3) + 8 * (r >> 2) + 4 * kh];
+    if ((unsigned)fi < (unsigned)p.n_flat) {
+      float v = acc[r];
+      if (p.row_scale) v *= p.row_scale[fi];
+      cbase[(int64_t)fi * p.ldc + ncol] = pack1<T>(v);
+    }
+  }
+}
+
+// Waves (adjacent 32-column tiles) per workgroup: the widest of 4, 2, 1 that still yields one workgroup
+// per CU, otherwise the narrowest.  SiLU * mul pairs waves, so it never goes below 2.  Decided from the
+// arguments alone: the same call always launches the same shape.
+static int moe_gemm_waves(int64_t max_blocks, int64_t n_tiles, bool silu) {
+  constexpr int64_t CUS = 256;  // MI355X
+  const int narrowest = silu ? 2 : 1;
+  for (int nw = 4; nw > narrowest; nw >>= 1) {
+    const int64_t per_block = silu ? (n_tiles / 2 + nw / 2 - 1) / (nw / 2) : (n_tiles + nw - 1) / nw;
+    if (max_blocks * per_block >= CUS) return nw;
+  }
+  return narrowest;
+}
+
+template <typename T, int NW>
+static void launch_moe_dense(const MoeDenseKParams& kp, unsigned grid, hipStream_t st) {
+  hipLaunchKernelGGL((moe_dense_gemm_kernel<T, NW>), dim3(grid), dim3(NW * 64), 0, st, kp);
+}
+
+template <typename T>
+static void launch_moe_dense_nw(const MoeDenseKParams& kp, int nw, unsigned grid, hipStream_t st) {
+  if (nw == 4) launch_moe_dense<T, 4>(kp, grid, st);
+  else if (nw == 2) launch_moe_dense<T, 2>(kp, grid, st);
+  else launch_moe_dense<T, 1>(kp, grid, st);
+}
+
+}  // namespace slm
+
+extern "C" {
+
+SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) {
+  using namespace slm;
+  if (!a) return SLM_ERR_INVALID_ARG;
+  if (a->n_flat < 0 || a->K <= 0 || a->N <= 0 || a->a_div < 1 || a->n_experts < 1 || a->max_blocks < 0)
+    return SLM_ERR_INVALID_ARG;
+  if (a->dtype != SLM_F16 && a->dtype != SLM_BF16) return SLM_ERR_UNSUPPORTED;
+  if (a->flags & ~SLM_MOE_SILU_MUL) return SLM_ERR_INVALID_ARG;
+  const bool silu = (a->flags & SLM_MOE_SILU_MUL) != 0;
+  if (silu && a->row_scale) return SLM_ERR_INVALID_ARG;
+  if (a->K % 32 || a->N % 32 || (silu && (a->N / 2) % 32)) return SLM_ERR_UNSUPPORTED;
+  // 32-bit offsets inside one expert; flat indices are int32
+  if (a->K * a->N * 2 >= ((int64_t)1 << 32) || a->n_flat >= ((int64_t)1 << 31) - 256) return SLM_ERR_UNSUPPORTED;
+  if (a->n_flat == 0 || a->max_blocks == 0) return SLM_OK;
+  if (!a->a || !a->w || !a->c || !a->sorted_token_idxes || !a->expert_ids || !a->n_padded_tokens)
+    return SLM_ERR_INVALID_ARG;
+  const int64_t n_out = silu ? a->N / 2 : a->N;
+  if (a->lda < a->K || a->ldw < a->K || a->ldc < n_out || a->w_expert_stride < (a->N - 1) * a->ldw + a->K)
+    return SLM_ERR_INVALID_ARG;
+  if (!aligned16(a->a) || a->lda % 8 || !aligned16(a->w) || a->ldw % 8 || a->w_expert_stride % 8 ||
+      (reinterpret_cast<uintptr_t>(a->c) & 1u) || (reinterpret_cast<uintptr_t>(a->row_scale) & 3u))
+    return SLM_ERR_ALIGNMENT;
+  if (a->N * a->ldw * 2 >= ((int64_t)1 << 32)) return SLM_ERR_UNSUPPORTED;  // a strided expert: still < 4 GiB
+  const int64_t n_tiles = a->N / 32;
+  const int nw = moe_gemm_waves(a->max_blocks, n_tiles, silu);
+  const int64_t n_nblocks = silu ? (n_tiles / 2 + nw / 2 - 1) / (nw / 2) : (n_tiles + nw - 1) / nw;
+  const int64_t grid = (int64_t)a->max_blocks * n_nblocks;
+  if (grid >= ((int64_t)1 << 31)) return SLM_ERR_UNSUPPORTED;
+
+  MoeDenseKParams kp;
+  kp.a = a->a;
+  kp.w = reinterpret_cast<const char*>(a->w);
+  kp.c = a->c;
+  kp.row_scale = a->row_scale;
+  kp.sorted = a->sorted_token_idxes;
+  kp.expert_ids = a->expert_ids;
+  kp.n_padded = a->n_padded_tokens;
+  kp.w_stride = a->w_expert_stride * 2;
+  kp.lda = a->lda; kp.ldw = a->ldw; kp.ldc = a->ldc;
+  kp.n_flat = (int)a->n_flat;
+  kp.a_div = a->a_div;
+  kp.n_experts = a->n_experts;
+  kp.n_tiles = (int)n_tiles;
+  kp.n_chunks = (int)(a->K / MG_KC);
+  kp.tail_units = (int)((a->K % MG_KC) / 32);
+  kp.n_nblocks = (int)n_nblocks;
+  kp.silu = silu ? 1 : 0;
+  hip_clear_error();
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (a->dtype == SLM_BF16) launch_moe_dense_nw<bf16_tag>(kp, nw, (unsigned)grid, st);
+  else launch_moe_dense_nw<f16_tag>(kp, nw, (unsigned)grid, st);
+  return hip_check_launch();
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // slm_moe_hip.h -- the mixture-of-experts operators at the libtorch boundary, on top of the C ABI's section 10
-// (include/slm_hip.h; csrc/moe.hip, csrc/w4_moe.hip).
+// (include/slm_hip.h; csrc/moe.hip, csrc/w4_moe.hip, csrc/moe_gemm.hip).
 //
 //   llm::kernel::topk_softmax, llm::kernel::grouped_topk_sigmoid      src/kernels/moe/topk_softmax_kernel.cu:272,
 //                                                                      grouped_topk_sigmoid_kernel.cu:280
@@ -7,6 +7,7 @@
 // with exactly the reference's signatures, so its callers compile unchanged, and
 //   slm::moe_w4_grouped_gemm   the grouped int4 GEMM over stacked packed experts (the reference's grouped GEMM,
 //                              src/kernels/gemm/, is a dense fp16 / bf16 kernel; int4 experts have no counterpart).
+//   slm::moe_grouped_gemm      that dense fp16 / bf16 grouped GEMM over W[e, n, k].
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
 #pragma once
@@ -59,5 +60,13 @@ void moe_w4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& wq, const 
                          const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
                          const torch::Tensor& n_padded_tokens, int64_t K, int64_t N, int64_t group_size,
                          int64_t a_div, int64_t format, const torch::Tensor& row_scale, bool silu_mul);
+
+// C[idx] = epilogue(A[idx / a_div] . W[e]^T) over unquantised experts w [E, N, K] (the checkpoint layout, k contiguous;
+// expert and row strides may exceed the dense ones) -- the reference's grouped GEMM itself.  row_scale: fp32 [n_flat]
+// or undefined; silu_mul: rows [0, N/2) of an expert are the gate, [N/2, N) the up projection, c is [n_flat, N / 2].
+void moe_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w, torch::Tensor& c,
+                      const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+                      const torch::Tensor& n_padded_tokens, int64_t a_div, const torch::Tensor& row_scale,
+                      bool silu_mul);
 
 }  // namespace slm

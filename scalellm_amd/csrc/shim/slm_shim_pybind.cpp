@@ -212,6 +212,14 @@ PYBIND11_MODULE(_slm_shim, m) {
         }, py::arg("a"), py::arg("wq"), py::arg("sz"), py::arg("c"), py::arg("sorted_token_idxes"),
         py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("K"), py::arg("N"), py::arg("group_size"),
         py::arg("a_div"), py::arg("format"), py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
+  m.def("moe_grouped_gemm",
+        [](const torch::Tensor& a, const torch::Tensor& w, torch::Tensor c, const torch::Tensor& sorted_token_idxes,
+           const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
+           const c10::optional<torch::Tensor>& row_scale, bool silu_mul) {
+          slm::moe_grouped_gemm(a, w, c, sorted_token_idxes, expert_ids, n_padded_tokens, a_div,
+                                row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
+        }, py::arg("a"), py::arg("w"), py::arg("c"), py::arg("sorted_token_idxes"), py::arg("expert_ids"),
+        py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
   // multi-head latent attention (slm_mla_hip.h)
   m.def("mla_paged_kv",
         [](torch::Tensor out, const torch::Tensor& q, const torch::Tensor& kv_cache, const torch::Tensor& q_rope,

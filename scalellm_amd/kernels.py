@@ -1190,6 +1190,7 @@ def rejection_sample(draft_token_ids: torch.Tensor, draft_probs: Optional[torch.
 #   moe_topk_softmax / moe_grouped_topk_sigmoid <- llm::kernel::topk_softmax / grouped_topk_sigmoid
 #   moe_align_block / moe_sum                   <- llm::kernel::moe::permute_align_block / sum_out
 #   moe_w4_grouped_gemm                         <- the grouped GEMM of src/kernels/gemm/ over int4 experts
+#   moe_grouped_gemm                            <- the grouped GEMM of src/kernels/gemm/ itself (dense f16 / bf16)
 # ---------------------------------------------------------------------------------------
 MOE_GEMM_BLOCK = _lib.SLM_MOE_GEMM_BLOCK
 
@@ -1347,6 +1348,47 @@ def moe_w4_grouped_gemm(a: torch.Tensor, experts: PackedMoeW4, c: torch.Tensor, 
     g.format = experts.fmt | (_lib.SLM_W4_PAIRED if experts.paired else 0)
     g.flags = _lib.SLM_W4_SILU_MUL if silu_mul else 0
     check(_lib.lib().slm_moe_w4a16_gemm(C.byref(g), _stream()), "slm_moe_w4a16_gemm")
+
+
+def moe_grouped_gemm(a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, sorted_token_idxes: torch.Tensor,
+                     expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor, a_div: int,
+                     row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """C[idx] = epilogue(A[idx // a_div] . W[e]^T) over unquantised experts w [E, N, K] (the checkpoint layout,
+    k contiguous; expert and row strides may be larger than dense), for the 32-row blocks
+    moe_align_block(block_size = 32) produced.  silu_mul: rows [0, N/2) of an expert are the gate, [N/2, N) the up
+    projection, c is [n_flat, N / 2]; row_scale: fp32 [n_flat] routing weights applied to the fp32 accumulator.
+    The grid covers expert_ids.numel() blocks; the count in use is read on the device."""
+    _require_gpu(a, w, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    if a.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1:
+        raise SlmError("A and C must be 2-D with contiguous rows")
+    if w.dim() != 3 or w.stride(2) != 1:
+        raise SlmError("expert weights must be [n_experts, N, K] with k contiguous")
+    E, N, K = w.shape
+    n_flat = c.size(0)
+    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a_div < 1 or a.size(0) * a_div < n_flat:
+        raise SlmError("grouped GEMM shape mismatch")
+    if a.dtype != w.dtype or c.dtype != w.dtype:
+        raise SlmError("activation / output dtype must match the experts' dtype")
+    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
+    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
+        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
+                                  row_scale.numel() != n_flat):
+        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
+    g = _lib.MoeDenseGemmArgs()
+    g.a, g.w, g.c = a.data_ptr(), w.data_ptr(), c.data_ptr()
+    g.row_scale = row_scale.data_ptr() if row_scale is not None else None
+    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
+    g.n_padded_tokens = n_padded_tokens.data_ptr()
+    g.w_expert_stride = w.stride(0) if E > 1 else max(w.stride(0), (N - 1) * w.stride(1) + K)
+    g.n_flat, g.K, g.N = n_flat, K, N
+    g.lda, g.ldw, g.ldc = a.stride(0), w.stride(1), c.stride(0)
+    g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
+    g.dtype = _dtype_code(a)
+    g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
+    check(_lib.lib().slm_moe_gemm(C.byref(g), _stream()), "slm_moe_gemm")
 
 
 # ---------------------------------------------------------------------------------------

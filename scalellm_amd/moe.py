@@ -1,5 +1,6 @@
-"""Mixture-of-experts FFN over int4 (AWQ / GPTQ) experts: routing, block alignment, two grouped GEMMs and the
-sum over a token's experts, every step a HIP kernel of libslm_hip (include/slm_hip.h section 10).
+"""Mixture-of-experts FFN over int4 (AWQ / GPTQ) or unquantised f16 / bf16 experts: routing, block alignment, two
+grouped GEMMs and the sum over a token's experts, every step a HIP kernel of libslm_hip (include/slm_hip.h
+section 10).
 
     FusedMoE.forward(x):  router logits (fp32, torch: [T, hidden] x [hidden, E] is tiny)
                           -> moe_topk_softmax | moe_grouped_topk_sigmoid      (weights, expert ids)
@@ -87,14 +88,62 @@ class MoEQuantExperts:
         return self.gate_up.nbytes() + self.down.nbytes()
 
 
+class MoEDenseExperts:
+    """The unquantised weights of E experts, stacked in the checkpoint's own [out, in] layout: `gate_up`
+    [E, 2 * intermediate, hidden] (w1 rows, then w3 rows) and `down` [E, hidden, intermediate].  load_state_dict takes
+    Mixtral-style names experts.{e}.w1|w3|w2.weight; nothing is repacked, the stacking happens on the first forward."""
+
+    def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device):
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise SlmError(f"MoE experts: fp16 / bf16 only, got {dtype}")
+        self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
+        self.dtype, self.device = dtype, device
+        self._ckpt: Dict[str, torch.Tensor] = {}
+        self.gate_up: Optional[torch.Tensor] = None
+        self.down: Optional[torch.Tensor] = None
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        for e in range(self.n_experts):
+            for w in ("w1", "w2", "w3"):
+                key = f"experts.{e}.{w}.weight"
+                if key in sd:
+                    self._ckpt[key] = sd[key].to(self.device, self.dtype)
+        self.gate_up = self.down = None
+
+    def verify_loaded_weights(self) -> None:
+        if self.gate_up is not None:
+            return
+        for e in range(self.n_experts):
+            for w in ("w1", "w2", "w3"):
+                assert f"experts.{e}.{w}.weight" in self._ckpt, f"experts.{e}.{w}.weight is not loaded"
+
+    def repack(self) -> None:
+        self.verify_loaded_weights()
+        c = self._ckpt
+        H, I = self.hidden, self.intermediate
+        for e in range(self.n_experts):
+            if tuple(c[f"experts.{e}.w1.weight"].shape) != (I, H) or tuple(c[f"experts.{e}.w3.weight"].shape) != (I, H) \
+                    or tuple(c[f"experts.{e}.w2.weight"].shape) != (H, I):
+                raise SlmError("expert weights do not match hidden / intermediate")
+        self.gate_up = torch.stack([torch.cat([c[f"experts.{e}.w1.weight"], c[f"experts.{e}.w3.weight"]], dim=0)
+                                    for e in range(self.n_experts)]).contiguous()
+        self.down = torch.stack([c[f"experts.{e}.w2.weight"] for e in range(self.n_experts)]).contiguous()
+        self._ckpt = {}
+
+    def nbytes(self) -> int:
+        return (self.gate_up.numel() + self.down.numel()) * self.gate_up.element_size()
+
+
 class FusedMoE:
-    """Sparse FFN block: a router (`gate`, an unquantised [E, hidden] weight) over n_experts int4 SwiGLU experts.
+    """Sparse FFN block: a router (`gate`, an unquantised [E, hidden] weight) over n_experts SwiGLU experts: int4
+    (AWQ / GPTQ) with a QuantArgs, unquantised f16 / bf16 with quant_args=None.
 
     scoring = "softmax": top-k of the softmax (renormalize = Mixtral's rule: the k weights divided by their sum);
     scoring = "grouped_sigmoid": sigmoid scores with a correction bias, group-limited top-k (n_expert_groups,
     topk_group, scaling_factor; DeepSeek-V3 style).  max_tokens bounds the rows of one forward."""
 
-    def __init__(self, hidden: int, intermediate: int, n_experts: int, topk: int, quant_args: QuantArgs,
+    def __init__(self, hidden: int, intermediate: int, n_experts: int, topk: int,
+                 quant_args: Optional[QuantArgs] = None,
                  scoring: str = "softmax", renormalize: bool = True, n_expert_groups: int = 1, topk_group: int = 1,
                  scaling_factor: float = 1.0, max_tokens: int = 256, dtype: torch.dtype = torch.bfloat16,
                  device="cuda"):
@@ -102,13 +151,17 @@ class FusedMoE:
             raise SlmError(f"unknown scoring {scoring}")
         if not 1 <= topk <= n_experts:
             raise SlmError(f"topk = {topk} must be in 1 .. n_experts = {n_experts}")
-        if hidden % 128 or intermediate % 128:
+        if quant_args is not None and (hidden % 128 or intermediate % 128):
             raise SlmError("hidden and intermediate must be multiples of 128 (K of the two grouped GEMMs)")
+        if quant_args is None and (hidden % 32 or intermediate % 32):
+            raise SlmError("hidden and intermediate must be multiples of 32 (K and N of the two grouped GEMMs)")
         self.hidden, self.intermediate, self.n_experts, self.topk = hidden, intermediate, n_experts, topk
         self.scoring, self.renormalize = scoring, renormalize
         self.n_expert_groups, self.topk_group, self.scaling_factor = n_expert_groups, topk_group, scaling_factor
         self.max_tokens, self.dtype, self.device = max_tokens, dtype, device
-        self.experts = MoEQuantExperts(hidden, intermediate, n_experts, quant_args, dtype, device)
+        self.experts = MoEDenseExperts(hidden, intermediate, n_experts, dtype, device) if quant_args is None else \
+            MoEQuantExperts(hidden, intermediate, n_experts, quant_args, dtype, device)
+        self._gemm = kernels.moe_grouped_gemm if quant_args is None else kernels.moe_w4_grouped_gemm
         self.gate_weight: Optional[torch.Tensor] = None       # [E, hidden]
         self.correction_bias: Optional[torch.Tensor] = None   # [E] fp32 (grouped_sigmoid)
         self._gate_f32_t: Optional[torch.Tensor] = None       # [hidden, E] fp32, built on the first forward
@@ -170,9 +223,8 @@ class FusedMoE:
             kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups, self.topk_group, k,
                                              self.scaling_factor, weights, ids)
         kernels.moe_align_block(ids, self.n_experts, kernels.MOE_GEMM_BLOCK, srt, eids, b["n_padded"])
-        kernels.moe_w4_grouped_gemm(x2, self.experts.gate_up, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
-        kernels.moe_w4_grouped_gemm(act, self.experts.down, down, srt, eids, b["n_padded"], a_div=1,
-                                    row_scale=weights.view(-1))
+        self._gemm(x2, self.experts.gate_up, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
+        self._gemm(act, self.experts.down, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
         kernels.moe_sum(down.view(T, k, self.hidden), out.view(T, self.hidden))
         return out.view(x.shape)
 

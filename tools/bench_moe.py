@@ -1,7 +1,8 @@
-"""FusedMoE (scalellm_amd/moe.py: routing, align, two grouped int4 GEMMs, sum) at Mixtral-8x7B shapes against
-what the dense path offers: a host loop of per-expert slm_w4a16_gemm calls.
+"""FusedMoE (scalellm_amd/moe.py: routing, align, two grouped GEMMs, sum) at Mixtral-8x7B shapes against a host
+loop over the experts: per-expert slm_w4a16_gemm calls for int4 experts, torch.matmul for unquantised ones.
 
     python tools/bench_moe.py [--out profiles/r09_moe.jsonl] [--tokens 1,32,256] [--iters 200]
+    python tools/bench_moe.py --dense [--out profiles/r12_moe_dense.jsonl]
 
 hidden 4096, intermediate 14336, E = 8, k = 2, AWQ group 128, bf16 (random weights: 705 MB packed).  One JSON
 line per T:
@@ -18,6 +19,10 @@ line per T:
                   with the routing and the per-expert counts known on the host beforehand (not timed).
   loop_graph_us   that loop for ONE fixed routing captured in a graph (host-known counts can be captured only for a
                   routing that never changes): its best case, without launch gaps.
+
+--dense: the same layer over unquantised bf16 experts (FusedMoE(quant_args=None), slm_moe_gemm; 2.8 GB of weights),
+measured the same way; the loop is index_select, torch.matmul (gate | up), SiLU * mul, torch.matmul (down), scale,
+index_add_ per expert.
 """
 import argparse
 import json
@@ -54,6 +59,21 @@ def _layer(max_tokens, dev):
     return layer
 
 
+def _dense_layer(max_tokens, dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    sd = {}
+    for e in range(NE):
+        for w, (N, K) in (("w1", (INTER, HID)), ("w3", (INTER, HID)), ("w2", (HID, INTER))):
+            sd[f"experts.{e}.{w}.weight"] = (torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+    sd["gate.weight"] = (torch.randn(NE, HID, device=dev, generator=g) * 0.05).to(torch.bfloat16)
+    layer = moe.FusedMoE(HID, INTER, NE, TOPK, quant_args=None, scoring="softmax", renormalize=True,
+                         max_tokens=max_tokens, dtype=torch.bfloat16, device=dev)
+    layer.load_state_dict(sd)
+    del sd
+    layer(torch.zeros(1, HID, device=dev, dtype=torch.bfloat16))   # stack + buffers
+    return layer
+
+
 def _routing(layer, x):
     logits = x.float() @ layer.gate_weight.float().t()
     w, ids = kernels.moe_topk_softmax(logits, TOPK, True)
@@ -83,6 +103,16 @@ def _loop_forward(layer, x, plan, out):
     return out
 
 
+def _loop_forward_dense(layer, x, plan, out):
+    out.zero_()
+    for e, rows, w in plan:
+        xs = x.index_select(0, rows)
+        h = torch.matmul(xs, layer.experts.gate_up[e].t())
+        act = torch.nn.functional.silu(h[:, :INTER]) * h[:, INTER:]
+        out.index_add_(0, rows, torch.matmul(act, layer.experts.down[e].t()) * w)
+    return out
+
+
 def _time(fn, iters):
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for i in range(min(10, iters)):
@@ -102,14 +132,21 @@ def main():
     ap.add_argument("--tokens", default="1,32,256")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--pool", type=int, default=16)
+    ap.add_argument("--dense", action="store_true", help="unquantised bf16 experts (slm_moe_gemm)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda")
     tokens = [int(t) for t in args.tokens.split(",")]
-    layer = _layer(max(tokens), dev)
-    per_expert = (layer.experts.gate_up.nbytes() + layer.experts.down.nbytes()) // NE
-    gu_bytes, dn_bytes = layer.experts.gate_up.nbytes() // NE, layer.experts.down.nbytes() // NE
+    if args.dense:
+        layer = _dense_layer(max(tokens), dev)
+        gu_bytes, dn_bytes = layer.experts.gate_up.numel() * 2 // NE, layer.experts.down.numel() * 2 // NE
+        loop_forward, name = _loop_forward_dense, "moe_mixtral_8x7b_dense_bf16"
+    else:
+        layer = _layer(max(tokens), dev)
+        gu_bytes, dn_bytes = layer.experts.gate_up.nbytes() // NE, layer.experts.down.nbytes() // NE
+        loop_forward, name = _loop_forward, "moe_mixtral_8x7b_awq_g128_bf16"
+    per_expert = gu_bytes + dn_bytes
     lines = []
     for T in tokens:
         g = torch.Generator(device=dev).manual_seed(T)
@@ -133,14 +170,14 @@ def main():
 
         plans = [_loop_plan(layer, x, dev) for x in pool]
         out_loop = torch.zeros(T, HID, device=dev, dtype=torch.bfloat16)
-        loop_us = _time(lambda i: _loop_forward(layer, pool[i % len(pool)], plans[i % len(pool)], out_loop), args.iters)
+        loop_us = _time(lambda i: loop_forward(layer, pool[i % len(pool)], plans[i % len(pool)], out_loop), args.iters)
         # agreement of the two paths on one input (different rounding points: a tolerance, not equality)
-        ref = _loop_forward(layer, pool[1], plans[1], out_loop).float()
+        ref = loop_forward(layer, pool[1], plans[1], out_loop).float()
         rel = float((eager.float() - ref).abs().mean() / ref.abs().mean())
         torch.cuda.synchronize()
         lg = torch.cuda.CUDAGraph()
         with torch.cuda.graph(lg):
-            _loop_forward(layer, x_static, plans[0], out_loop)
+            loop_forward(layer, x_static, plans[0], out_loop)
         x_static.copy_(pool[0])
         loop_graph_us = _time(lambda i: lg.replay(), args.iters)
 
@@ -148,7 +185,7 @@ def main():
         blocks = [sum((rows.numel() + 31) // 32 for _, rows, _ in p) for p in plans]
         touched = per_expert * sum(used) / len(used)
         streamed = (gu_bytes + dn_bytes) * sum(blocks) / len(blocks)
-        line = dict(bench="moe_mixtral_8x7b_awq_g128_bf16", T=T, topk=TOPK, n_experts=NE,
+        line = dict(bench=name, T=T, topk=TOPK, n_experts=NE,
                     fused_us=round(fused_us, 2), loop_us=round(loop_us, 2), loop_graph_us=round(loop_graph_us, 2),
                     experts_in_use=round(sum(used) / len(used), 2), row_blocks=round(sum(blocks) / len(blocks), 2),
                     touched_bytes=int(touched), streamed_bytes=int(streamed),
