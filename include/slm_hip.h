@@ -406,7 +406,10 @@ SLM_API int slm_gelu(void* out, const void* x, int64_t n_tokens, int64_t d, int3
  * (src/layers/attention/attention.cpp:36-42).  cos_sin row = [cos(rot/2) | sin(rot/2)] per
  * position (the reference cache layout, pos_embedding_kernels.cu:41: [max_pos, 2, rot/2]), either
  * in the activation dtype (as RotaryEmbeddingKernel builds it, pos_embedding.cpp:195-196) or
- * fp32.  cos_sin == NULL skips the rotation (alibi models); slot_ids == NULL skips the append. */
+ * fp32.  cos_sin == NULL skips the rotation (alibi models); slot_ids == NULL skips the append.
+ * A token whose slot id is negative (graph padding) is rotated in place like any other, but its
+ * append is skipped: neither cache is written for it.  Every other id must be a valid slot.  The
+ * same holds for slm_rope_kv_append_splitk below. */
 SLM_API int slm_rope_kv_append(void* q /* [T, n_heads, D] in place */, int64_t q_token_stride,
                                void* k /* [T, n_kv_heads, D] in place */, int64_t k_token_stride,
                                const void* v /* [T, n_kv_heads, D] */, int64_t v_token_stride,

@@ -146,9 +146,19 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // silu(gate) * up in fp32 on values that are already exact in T: THE formula of the SiLU*mul glue
 // kernel (kernel::act_and_mul, reference src/kernels/activation_kernels.cu:84), shared with the
 // GEMM epilogues that fuse it so that both paths give identical bits
+//
+// sigmoid(g) = 1 / (1 + 2^(-g log2 e)) is an fp32 subnormal below g = -87.3, and v_rcp_f32 flushes a
+// subnormal result to zero (below -88.7 the exp2 overflows as well), while g * sigmoid(g) * u is still
+// a NORMAL bf16 number there: silu(-88) = -5.3e-37 came out as 0.  So below g = -64 the sigmoid is
+// carried times 2^32 (exponent argument - 32, 2^-32 in place of the 1) and the product is scaled back
+// at the end by an ordinary multiply, which keeps subnormals.  Everywhere else k = 0 and one = 1: the
+// fma rounds -g log2 e exactly as the multiply did and x * 1 is x, so those bits are what they were.
+// The fma is explicit so that no caller's contraction choice can differ from another's.
 __device__ __forceinline__ float silu_mul1(const float g, const float u) {
-  const float sig = __builtin_amdgcn_rcpf(1.0f + fast_exp2(-g * 1.4426950408889634f));
-  float r = g * sig * u;
+  const bool tiny = g < -64.0f;
+  const float k = tiny ? 32.0f : 0.0f, one = tiny ? 0x1p-32f : 1.0f;
+  const float sig = __builtin_amdgcn_rcpf(one + fast_exp2(__builtin_fmaf(-g, 1.4426950408889634f, -k)));
+  float r = g * sig * u * one;
   // the product is an fp32 value in a register before any conversion to T: without this the
   // compiler may fold "multiply, then round to fp16" into one v_fma_mixlo_f16 (single rounding) in
   // some callers and not in others (v_pk_mul_f32 + v_cvt), and the fused / unfused paths would
