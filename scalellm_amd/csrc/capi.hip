@@ -18,7 +18,7 @@ const char* const kTuneNames[TUNE_COUNT] = {
     "SLM_W4_MT",            "SLM_W4_MT_WIDE",       "SLM_W4_NTW",           "SLM_W4_PC",        "SLM_W4_SPLITK",
     "SLM_W4_POST",
     "SLM_W4_KS",            "SLM_W4_KS_CW",         "SLM_W4_KS_NW",     "SLM_W4_KS_TPW",
-    "SLM_W4_KS_DBG",        "SLM_W4_KS_MT2",
+    "SLM_W4_KS_MT2",
     "SLM_W4_M128",          "SLM_W4_M128_WD",       "SLM_W4_M128_SPLITS",   "SLM_W4_M128_KW",   "SLM_W4_SPLIT_TARGET",
     "SLM_W4_M128_CT",       "SLM_ATTN_TILE_KV2",    "SLM_W4_XL_MODEL",      "SLM_W4_M128_ADMA",
     "SLM_W4_XL_SK",

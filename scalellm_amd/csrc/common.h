@@ -252,6 +252,13 @@ inline int hip_check_launch() {
   return e == hipSuccess ? SLM_OK : SLM_ERR_LAUNCH;
 }
 
+// f(bf16_tag{}) or f(f16_tag{}) for a dtype the caller has checked to be one of the two
+template <typename F>
+inline void dispatch_dtype(int dtype, F&& f) {
+  if (dtype == SLM_BF16) f(bf16_tag{});
+  else f(f16_tag{});
+}
+
 inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
 inline int ilog2(int64_t x) {
   int r = 0;

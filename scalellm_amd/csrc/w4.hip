@@ -346,7 +346,6 @@ static int gemm_impl(const slm_w4_gemm_args* a, const slm_w4_norm_prologue* np, 
   kp.silu = silu ? 1 : 0;
   kp.ks_tpw = pl.ks.tpw;
   kp.ks_groups = (int)(a->K / a->group_size);
-  kp.ks_dbg = tune_get(TUNE_W4_KS_DBG, 0);
   kp.sk_per = pl.xl_sk.sk_per; kp.sk_sync = nullptr; kp.sk_part = nullptr;
   switch (pl.kernel) {
     case W4Kernel::GEMV: launch_gemv(kp, a->dtype, pl, st); break;
@@ -369,18 +368,15 @@ static int gemm_impl(const slm_w4_gemm_args* a, const slm_w4_norm_prologue* np, 
   if (pl.split_k > 1 && !((a->flags & SLM_W4_DEFER_REDUCE) && !a->bias)) {
     const int64_t n4 = a->M * (silu ? a->N / 2 : a->N) / 4;
     const dim3 grid((unsigned)((n4 + 255) / 256)), blk(256);
-    if (silu && a->dtype == SLM_BF16)
-      hipLaunchKernelGGL(w4_splitk_reduce_silu_kernel<bf16_tag>, grid, blk, 0, st, kp.part, a->bias,
-                         a->c, a->M, a->N, a->ldc, pl.split_k);
-    else if (silu)
-      hipLaunchKernelGGL(w4_splitk_reduce_silu_kernel<f16_tag>, grid, blk, 0, st, kp.part, a->bias,
-                         a->c, a->M, a->N, a->ldc, pl.split_k);
-    else if (a->dtype == SLM_BF16)
-      hipLaunchKernelGGL(w4_splitk_reduce_kernel<bf16_tag>, grid, blk, 0, st, kp.part, a->bias, a->c,
-                         a->M, a->N, a->ldc, pl.split_k);
-    else
-      hipLaunchKernelGGL(w4_splitk_reduce_kernel<f16_tag>, grid, blk, 0, st, kp.part, a->bias, a->c,
-                         a->M, a->N, a->ldc, pl.split_k);
+    dispatch_dtype(a->dtype, [&](auto t) {
+      using T = decltype(t);
+      if (silu)
+        hipLaunchKernelGGL(w4_splitk_reduce_silu_kernel<T>, grid, blk, 0, st, kp.part, a->bias, a->c, a->M, a->N,
+                           a->ldc, pl.split_k);
+      else
+        hipLaunchKernelGGL(w4_splitk_reduce_kernel<T>, grid, blk, 0, st, kp.part, a->bias, a->c, a->M, a->N, a->ldc,
+                           pl.split_k);
+    });
     rc = hip_check_launch();
   }
   return rc;

@@ -1,6 +1,8 @@
 // w4_common.h -- shared pieces of the int4-weight GEMM kernels: the dequant helpers (one code path for the
-// GEMMs and the debug dequant kernel), the all-ones fragment word, kernel params, what each kernel file says
-// about itself, and the host checks of the format word and the group size (Mfma<T> is in common.h).
+// GEMMs and the debug dequant kernel), the all-ones fragment word, kernel params, the buffer-resource and
+// chunks-per-group helpers, the launch that opts into > 64 KiB of LDS, what each kernel file says about itself,
+// and the host checks of the format word and the group size (Mfma<T> is in common.h; the epilogues of the MFMA
+// kernels, one per accumulator layout, are in w4_epilogue.h).
 #pragma once
 #include "common.h"
 
@@ -185,7 +187,6 @@ struct GemmKParams {
   int silu;  // SLM_W4_SILU_MUL: column tiles are (gate, up) pairs, c is [M, N/2]
   int ks_tpw;     // w4_ks.hip: consecutive column tiles per workgroup (n_nblocks = tile runs)
   int ks_groups;  // w4_ks.hip: K / group_size (rows of the scale table)
-  int ks_dbg;     // w4_ks.hip: probe bits (SLM_W4_KS_DBG), 0 in production
   // w4_xl.hip, stream-K form (round 6): workgroup g (a ticket drawn at start) owns the 128-deep chunks
   // [g * sk_per, (g + 1) * sk_per) of the tile-major work list (tiles x n_chunks); sk_sync = {ticket, flag[g] ...},
   // zero at launch; sk_part = one 256 x 256 fp32 tile image per workgroup (fragment-major)
@@ -204,48 +205,29 @@ struct GemmKParams {
   void* norm_out;              // optional [M, K] T copy of the normalised activations
 };
 
-// SLM_W4_SILU_MUL epilogue of the C^T-accumulator kernels (w4_ws.hip, w4_xl.hip; split_k == 1):
-// the wave's two adjacent column tiles t0 (even: gate) and t0 + 1 (up) sit in the same lane at the
-// same (i, r), so the pair never leaves its registers.  Lane = token row0 + 32 i; the 16 values
-// are the columns (r & 3) + 8 (r >> 2) + 4 (lane >> 5): four consecutive outputs per r >> 2.
-template <typename T>
-__device__ __forceinline__ void store_ct_silu_pair(const GemmKParams& p, const f32x16 (&acc)[2][4],
-                                                   const int64_t t0, const int64_t row0,
-                                                   const int lane) {
-  if ((t0 + 1) * 32 >= p.N) return;
-  const bool wide = ((p.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.c) & 7) == 0);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int64_t gcol = t0 * 32 + 8 * q + 4 * (lane >> 5);
-    const int64_t ocol = (t0 >> 1) * 32 + 8 * q + 4 * (lane >> 5);
-    float bg[4] = {0.f, 0.f, 0.f, 0.f}, bu[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p.bias) {
-      const uint16_t* bp = reinterpret_cast<const uint16_t*>(p.bias) + gcol;
-      const u32x2 g = *reinterpret_cast<const u32x2*>(bp);
-      const u32x2 u = *reinterpret_cast<const u32x2*>(bp + 32);
-      bg[0] = lo_f32<T>(g.x); bg[1] = hi_f32<T>(g.x); bg[2] = lo_f32<T>(g.y); bg[3] = hi_f32<T>(g.y);
-      bu[0] = lo_f32<T>(u.x); bu[1] = hi_f32<T>(u.x); bu[2] = lo_f32<T>(u.y); bu[3] = hi_f32<T>(u.y);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t row = row0 + i * 32;
-      if (row >= p.M) continue;
-      float o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        o[e] = silu_mul_acc<T>(acc[0][i][4 * q + e] + bg[e], acc[1][i][4 * q + e] + bu[e]);
-      uint16_t* dst = reinterpret_cast<uint16_t*>(p.c) + row * p.ldc + ocol;
-      u32x2 w;
-      w.x = pack2<T>(o[0], o[1]);
-      w.y = pack2<T>(o[2], o[3]);
-      if (wide) {
-        *reinterpret_cast<u32x2*>(dst) = w;
-      } else {
-        dst[0] = (uint16_t)(w.x & 0xffffu); dst[1] = (uint16_t)(w.x >> 16);
-        dst[2] = (uint16_t)(w.y & 0xffffu); dst[3] = (uint16_t)(w.y >> 16);
-      }
-    }
+// raw buffer resource over [base, base + bytes): SGPR base + 32-bit offsets, out-of-range loads return zero and
+// out-of-range stores are dropped by the hardware (gfx950 flags word)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t w4_rsrc(const void* base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+
+// log2(128-deep chunks per scale group): 0 up to group 128, 30 per-channel (every chunk maps to group 0)
+__device__ __forceinline__ int w4_cpg_shift(int gs_shift) {
+  return gs_shift >= 30 ? 30 : (gs_shift > 7 ? gs_shift - 7 : 0);
+}
+
+// Launch KFN with `lds` bytes of dynamic LDS, more than the 64 KiB a kernel gets unasked: opted into once per
+// kernel (= per instantiation of this template) AND per device
+template <auto KFN>
+static void launch_big_lds(const GemmKParams& kp, int n_blocks, int threads, size_t lds, hipStream_t st) {
+  static bool opted[64] = {};
+  int devi = 0;
+  (void)hipGetDevice(&devi);
+  if (devi < 0 || devi >= 64 || !opted[devi]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (devi >= 0 && devi < 64) opted[devi] = true;
   }
+  hipLaunchKernelGGL(KFN, dim3((unsigned)n_blocks), dim3((unsigned)threads), lds, st, kp);
 }
 
 // What every int4 entry point accepts, said once (host).  A format word is GPTQ or AWQ, optionally

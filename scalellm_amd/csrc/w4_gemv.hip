@@ -440,13 +440,11 @@ void launch_gemv(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream
   gp.norm_eps = kp.norm_eps; gp.norm_res_in = kp.norm_res_in; gp.norm_res_out = kp.norm_res_out;
   gp.norm_weight = kp.norm_weight; gp.norm_out = kp.norm_out;
   const size_t lds = gemv_lds_bytes(kp.M, kp.K, kp.norm_weight != nullptr);
-  if (dtype == SLM_BF16) {
-    if (ng == 4) launch_gemv_m<bf16_tag, 2>(gp, n_wgs, lds, st);
-    else launch_gemv_m<bf16_tag, 1>(gp, n_wgs, lds, st);
-  } else {
-    if (ng == 4) launch_gemv_m<f16_tag, 2>(gp, n_wgs, lds, st);
-    else launch_gemv_m<f16_tag, 1>(gp, n_wgs, lds, st);
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (ng == 4) launch_gemv_m<T, 2>(gp, n_wgs, lds, st);
+    else launch_gemv_m<T, 1>(gp, n_wgs, lds, st);
+  });
 }
 
 }  // namespace slm

@@ -2,6 +2,7 @@
 // Takes what no specialised kernel does (w4_plan.hip: narrow layers at 32 < M <= 128 and at M > 128, small M
 // where the streams step aside); layout and dequant are described at the top of w4.hip.
 #include "w4_plan.h"
+#include "w4_epilogue.h"
 
 namespace slm {
 
@@ -261,40 +262,22 @@ __global__ void __launch_bounds__(256, (POST && PC * MT == 4 && MT < 4) ? 1 : 2)
     __syncthreads();
   }
 
-  // ---- epilogue: C/D layout of 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue (C/D layout: w4_epilogue.h)
+  const DenseRows rows{m0, p.M};
   if (p.silu && p.split_k == 1) {
     // SLM_W4_SILU_MUL: column tiles are (gate, up) pairs.  NTW == 2: both tiles of a pair are this
-    // wave's own; NTW == 1: waves (0, 1) and (2, 3) hold a pair -- the up wave hands its T-rounded
-    // tile to the gate wave through the (now idle) A buffers, same lane, same (m, r).
-    const uint16_t* bias = reinterpret_cast<const uint16_t*>(p.bias);
-    uint16_t* ex = reinterpret_cast<uint16_t*>(smem) + (wave >> 1) * (MT * 1024);
+    // wave's own; NTW == 1: waves (0, 1) and (2, 3) hold a pair, exchanged through the (now idle) A buffers
     if constexpr (NTW == 1) {
-      if (wave & 1) {
-        const float bu = bias ? lo_f32<T>((uint32_t)bias[ntile[0] * 32 + (lane & 31)]) : 0.f;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ex[(m * 16 + r) * 64 + lane] = pack1<T>(acc[0][m][r] + bu);
-      }
-      __syncthreads();
-      if (wave & 1) return;
-    }
-    if (!nvalid[0]) return;
-    const int64_t gcol = ntile[0] * 32 + (lane & 31), ocol = (ntile[0] >> 1) * 32 + (lane & 31);
-    const float bg = bias ? lo_f32<T>((uint32_t)bias[gcol]) : 0.f;
-    const float bu2 = (NTW == 2 && bias) ? lo_f32<T>((uint32_t)bias[gcol + 32]) : 0.f;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const float g = lo_f32<T>((uint32_t)pack1<T>(acc[0][m][r] + bg));
-        float u;
-        if constexpr (NTW == 2) u = lo_f32<T>((uint32_t)pack1<T>(acc[NTW - 1][m][r] + bu2));
-        else u = lo_f32<T>((uint32_t)ex[(m * 16 + r) * 64 + lane]);
-        if (row < p.M)
-          reinterpret_cast<uint16_t*>(p.c)[row * p.ldc + ocol] = pack1<T>(silu_mul1(g, u));
-      }
+      uint16_t* ex = reinterpret_cast<uint16_t*>(smem) + (wave >> 1) * (MT * 1024);
+      cd_silu_exchange<T, MT>(acc[0], rows, lane, ex, wave & 1, !(wave & 1) && nvalid[0], p.bias, ntile[0], p.c, p.ldc,
+                              ntile[0] >> 1);
+    } else {
+      if (!nvalid[0]) return;
+      const int64_t gcol = ntile[0] * 32 + (lane & 31);
+      const float bg = cd_bias<T>(p.bias, gcol), bu = cd_bias<T>(p.bias, gcol + 32);
+      cd_store_silu<T, MT>(
+          acc[0], bg, [&](int m, int r) { return lo_f32<T>((uint32_t)pack1<T>(acc[1][m][r] + bu)); }, rows, lane, p.c,
+          p.ldc, (ntile[0] >> 1) * 32 + (lane & 31));
     }
     return;
   }
@@ -307,25 +290,7 @@ __global__ void __launch_bounds__(256, (POST && PC * MT == 4 && MT < 4) ? 1 : 2)
       const uint16_t braw = reinterpret_cast<const uint16_t*>(p.bias)[n];
       bv = lo_f32<T>((uint32_t)braw);
     }
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < p.M) {
-          if (p.split_k == 1)
-            reinterpret_cast<uint16_t*>(p.c)[row * p.ldc + n] = pack1<T>(acc[t][m][r] + bv);
-          else if (p.ks_dbg & 8) {  // (probe bit 8: tile-contiguous slab layout -- consumers not adapted, timing only)
-            const int64_t tile = (int64_t)mb * p.n_nblocks + nb;
-            const int rit = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const int cit = (wave * NTW + t) * 32 + (lane & 31);
-            p.part[(int64_t)ks * p.M * p.N + tile * (BM * 128 * NTW) + rit * (128 * NTW) + cit] = acc[t][m][r];
-          } else if ((p.ks_dbg & 16) && ks != 0) {  // (probe bit 16: only slice 0 stores its slab: the traffic of an in-place reduce)
-          } else if (!(p.ks_dbg & 4))  // (probe bit 4 of SLM_W4_KS_DBG: no slab stores -- WRONG results, timing only)
-            p.part[((int64_t)ks * p.M + row) * p.N + n] = acc[t][m][r];
-        }
-      }
-    }
+    cd_store_splitk<T, MT>(acc[t], rows, lane, p.split_k == 1, p.c, p.ldc, ntile[t], bv, p.part, (int64_t)ks * p.M, p.N);
   }
 }
 
@@ -370,8 +335,7 @@ static void launch_gemm(const GemmKParams& kp, const GemmPlan& pl, hipStream_t s
 }
 
 void launch_gemm_general(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
-  if (dtype == SLM_BF16) launch_gemm<bf16_tag>(kp, pl, st);
-  else launch_gemm<f16_tag>(kp, pl, st);
+  dispatch_dtype(dtype, [&](auto t) { launch_gemm<decltype(t)>(kp, pl, st); });
 }
 
 }  // namespace slm

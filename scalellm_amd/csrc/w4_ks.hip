@@ -51,16 +51,14 @@ namespace slm {
 // raw buffer resources: SGPR base + 32-bit offsets (no 64-bit VALU address math per load), and
 // out-of-range stores are dropped by the hardware -- rows >= M and tiles past the run need no branch,
 // so the loop body is straight-line code and hipcc's vmcnt waits stay exact
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ks_rsrc(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
+// (w4_rsrc, w4_common.h)
 constexpr uint32_t KS_OOB = 0x80000000u;  // beyond every resource here (all < 2 GiB or checked < 4 GiB)
 constexpr int KS_AUX_NT = 2;              // gfx940+ cache policy bits: sc0 = 1, nt = 2, sc1 = 16
 
 constexpr int KS_SLOTS = 4;  // partial-tile slots in LDS (see the slot arithmetic in the kernel)
 
 // CW: 128-deep chunks of K per wave (1, 2, 4);  NG: scale groups per chunk (1: group >= 128,
-// 2: 64, 4: 32);  NW: waves per workgroup (4, 8);  TL: timeline probe (tools/probe_ks_timeline.py)
+// 2: 64, 4: 32);  NW: waves per workgroup (4, 8)
 // MT: 32-row tiles of tokens (1: M <= 32; 2: 33 <= M <= 64, round 4).  With MT = 2 every weight word is
 // unpacked ONCE and feeds two MFMAs (one per row tile): the stream that was VALU-issue-bound on the
 // unpack at M <= 32 (7 VALU + 1 MFMA per word) becomes 7 VALU + 2 MFMAs -- matrix-pipe-bound -- instead
@@ -71,7 +69,7 @@ constexpr int KS_SLOTS = 4;  // partial-tile slots in LDS (see the slot arithmet
 // consecutive entries of the slot sequence (2t, 2t + 1).
 // (A fragment-major activation layout was measured in round 5 -- 3.6 % -- and is kept only as
 // tools/probes/experiments/w4_ks_fragment_major_activations.diff.)
-template <typename T, int CW, int NG, int NW, bool TL = false, bool PK = false, int MT = 1>
+template <typename T, int CW, int NG, int NW, int MT = 1>
 __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef typename Mfma<T>::frag frag_t;
@@ -97,38 +95,28 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
   const int cw0 = (ks * NW + wave) * CW;         // first chunk of this wave's K slice
   const int clast = p.n_chunks - 1;
   const bool kh = lane >= 32;
-  // TL (probe instantiation, SLM_W4_KS_DBG & 4): s_memtime stamps of every phase go to `c` instead of
-  // the result -- [workgroup][wave][32] u64, read by tools/probe_ks_timeline.py
-  auto stamp = [&](int idx) {
-    if constexpr (TL) {
-      const uint64_t tm = __builtin_amdgcn_s_memtime();
-      if (lane == 0 && idx < 32)
-        reinterpret_cast<uint64_t*>(p.c)[((int64_t)blockIdx.x * NW + wave) * 32 + idx] = tm;
-    }
-  };
-  stamp(0);
 
   // arrival counters start at zero; the one workgroup barrier that publishes this sits further down,
   // under the latency of the first loads
   if (tid < KS_SLOTS) reinterpret_cast<uint32_t*>(smem + CNT_OFF)[tid] = 0u;
 
   // ---- resources (the host checks the sizes: packed weights / scale table < 4 GiB, the rest < 2 GiB)
-  const __amdgpu_buffer_rsrc_t w_rs = ks_rsrc(p.wq, (uint32_t)((uint64_t)p.K * p.N / 2));
-  const __amdgpu_buffer_rsrc_t sz_rs = ks_rsrc(p.sz, (uint32_t)((uint64_t)p.ks_groups * p.N * 4));
+  const __amdgpu_buffer_rsrc_t w_rs = w4_rsrc(p.wq, (uint32_t)((uint64_t)p.K * p.N / 2));
+  const __amdgpu_buffer_rsrc_t sz_rs = w4_rsrc(p.sz, (uint32_t)((uint64_t)p.ks_groups * p.N * 4));
   const bool has_bias = p.bias != nullptr;
-  const __amdgpu_buffer_rsrc_t b_rs = ks_rsrc(has_bias ? p.bias : (const void*)p.sz, (uint32_t)(p.N * 2));
+  const __amdgpu_buffer_rsrc_t b_rs = w4_rsrc(has_bias ? p.bias : (const void*)p.sz, (uint32_t)(p.N * 2));
   const bool final_out = p.split_k == 1;
   const __amdgpu_buffer_rsrc_t c_rs =
-      ks_rsrc(p.c, final_out ? (uint32_t)(((p.M - 1) * p.ldc + (p.silu ? p.N / 2 : p.N)) * 2) : 0u);
+      w4_rsrc(p.c, final_out ? (uint32_t)(((p.M - 1) * p.ldc + (p.silu ? p.N / 2 : p.N)) * 2) : 0u);
   const __amdgpu_buffer_rsrc_t part_rs =
-      ks_rsrc(final_out ? nullptr : p.part + (int64_t)ks * p.M * p.N, final_out ? 0u : (uint32_t)(p.M * p.N * 4));
+      w4_rsrc(final_out ? nullptr : p.part + (int64_t)ks * p.M * p.N, final_out ? 0u : (uint32_t)(p.M * p.N * 4));
 
   const uint32_t w_voff = (uint32_t)lane * 16u;
   const uint32_t sz_voff = (uint32_t)(lane & 31) * 4u;
   const uint32_t b_voff = (uint32_t)(lane & 31) * 2u;
   const uint32_t kt_stride = (uint32_t)n_tiles * 1024u;  // bytes per 64-deep kt
   const uint32_t sz_stride = (uint32_t)p.N * 4u;         // bytes per scale group
-  const int cpg_shift = p.gs_shift >= 30 ? 30 : (p.gs_shift > 7 ? p.gs_shift - 7 : 0);
+  const int cpg_shift = w4_cpg_shift(p.gs_shift);
   uint32_t woff[CW][2], soff[CW][NG];
 #pragma unroll
   for (int c = 0; c < CW; ++c) {
@@ -141,14 +129,13 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
       soff[c][g] = grp * sz_stride + (uint32_t)nt0 * 128u;
     }
   }
-  const uint32_t w_dbg = (p.ks_dbg & 2) ? KS_OOB : 0u;  // probes: bit 0 = no activation loads, bit 1 = no weight loads
   u32x4 ring[RD][CW][2];
   uint32_t szr[RD][CW][NG];
   uint32_t bsr[RD];
   auto w_load = [&](int t, int c, int h) -> u32x4 {
     const uint32_t tc = (uint32_t)min(t, ntl - 1);  // tiles past the run: clamped duplicates, never stored
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                         w_rs, (int)w_voff, (int)((woff[c][h] + tc * 1024u) | w_dbg), KS_AUX_NT));
+                                         w_rs, (int)w_voff, (int)(woff[c][h] + tc * 1024u), KS_AUX_NT));
   };
   auto sz_load = [&](int t, int c, int g) -> uint32_t {
     const uint32_t tc = (uint32_t)min(t, ntl - 1);
@@ -178,12 +165,6 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  stamp(1);
-  {  // probe (SLM_W4_KS_DBG bits 8..14): delay the second wave of every SIMD by 256-cycle steps
-    const int nsl = (p.ks_dbg >> 8) & 127;
-    if (wave >= NW / 2)
-      for (int i = 0; i < nsl; ++i) __builtin_amdgcn_s_sleep(4);
-  }
 
   // ---- activations of this wave's K slice -> A fragments (row = lane & 31, k = 16 j + 8 (lane >> 5) ..+7)
   // through LDS.  Staging buffer b of wave w = its OWN partial-tile slots 2b and 2b + 1 (2 x 4 KiB: one
@@ -243,7 +224,7 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
       const int c = v / MT, mt = v % MT;
       const int cabs = cw0 + c;
       // chunks past K: out-of-range loads write zeros (zero activations x clamped weights = 0)
-      const uint32_t a_soff = (cabs <= clast && !(p.ks_dbg & 1)) ? (uint32_t)cabs * 256u : KS_OOB;
+      const uint32_t a_soff = cabs <= clast ? (uint32_t)cabs * 256u : KS_OOB;
       // rows >= M are never stored and MFMA rows are independent: their four-row DMA instructions are
       // skipped (the staging memory then holds whatever was there -- any bit pattern is fine).  At
       // M <= 4 that is 1/8 of the activation traffic and of the LDS fill, the bulk of the prologue.
@@ -278,7 +259,6 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
         xsum_chunk(c0 - 2);
         xsum_chunk(c0 - 1);
       }
-      stamp(c0 == 0 ? 2 : 31);
       if (c0 == 0)  // counters zeroed (top of the kernel) before anybody can publish a tile
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       // the DMA is invisible to the compiler: explicit wait (also lands the ring, issued before it)
@@ -320,8 +300,6 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
     }
   }
 
-  if constexpr (TL) asm volatile("" : "+v"(xa[0][0]));
-  stamp(3);
   uint32_t magic_v = W4Magic<T>::bits;
   asm volatile("" : "+v"(magic_v));  // keep it in a VGPR (not re-materialised as a literal)
   uint32_t mask_s = 0x000F000Fu;
@@ -359,7 +337,6 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
         asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(seen) : "v"(caddr) : "memory");
       } while ((uint32_t)__builtin_amdgcn_readfirstlane(seen) < target);
     }
-    stamp(6 + 4 * (tp < 0 ? 0 : tp));
     f32x4 pv4[MT][RPW == 4 ? NW : 1];
     f32x2 pv2[MT][RPW == 2 ? NW : 1];
 #pragma unroll
@@ -398,14 +375,13 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
                      : "v"(paddr), "v"(one)
                      : "memory");
       }
-      stamp(5 + 4 * t_pub);
     }
     // store (straight-line: disabled stores go out of range and are dropped).  C/D layout of the
     // 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     const int nt = nt0 + tp;
     const uint32_t col = (uint32_t)nt * 32u + (uint32_t)(lane & 31);
     const uint32_t ocol = silu ? (uint32_t)(nt >> 1) * 32u + (uint32_t)(lane & 31) : col;
-    const bool c_on = !TL && live && final_out && (!silu || (tp & 1));
+    const bool c_on = live && final_out && (!silu || (tp & 1));
     const bool part_on = live && !final_out;
     const float bv = has_bias ? lo_f32<T>(braw) : 0.f;
 #pragma unroll
@@ -435,11 +411,6 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
                                               (int)(part_on ? row * n4 + col * 4u : KS_OOB), 0, 0);
       }
     }
-    if constexpr (TL) {
-      float keep = hold[0][0];
-      asm volatile("" : "+v"(keep));
-      stamp(7 + 4 * (tp < 0 ? 0 : tp));
-    }
   };
 
   uint32_t bprev = 0u;
@@ -449,7 +420,6 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
 #pragma unroll
     for (int d = 0; d < RD; ++d) {
       const int t = it * RD + d;
-      stamp(4 + 4 * t);
       // ---- scales of this tile (loaded one ring turn ago), then their registers take the loads for
       // tile t + RD right away: issued BEFORE this tile's weight refills, so waiting for them at the
       // start of tile t + RD leaves a full ring of weight loads in flight
@@ -526,21 +496,10 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
           }
           if (s2 > 0 && jj == (WPG > 1 ? 1 : 0)) {
             const float sv = sc[s2 - 1];
-            if constexpr (PK) {
-              const f32x2 sv2 = {sv, sv};
 #pragma unroll
-              for (int r = 0; r < 16; r += 2) {
-                f32x2 a2 = {acc[0][r], acc[0][r + 1]};
-                const f32x2 t2 = {tmp[0][(s2 - 1) % PP][r], tmp[0][(s2 - 1) % PP][r + 1]};
-                a2 = __builtin_elementwise_fma(sv2, t2, a2);
-                acc[0][r] = a2.x; acc[0][r + 1] = a2.y;
-              }
-            } else {
+            for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
-              for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][r] = fmaf(sv, tmp[mt][(s2 - 1) % PP][r], acc[mt][r]);
-              }
+              for (int r = 0; r < 16; ++r) acc[mt][r] = fmaf(sv, tmp[mt][(s2 - 1) % PP][r], acc[mt][r]);
             }
             // pin the epilogue HERE (under this segment's MFMAs): without an anchor the scheduler
             // sinks all of a tile's epilogues to the tile end and keeps every partial tile live.
@@ -562,21 +521,10 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
         }
         if (s2 == NGW - 1) {
           const float sv = sc[s2];
-          if constexpr (PK) {
-            const f32x2 sv2 = {sv, sv};
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              f32x2 a2 = {acc[0][r], acc[0][r + 1]};
-              const f32x2 t2 = {tmp[0][s2 % PP][r], tmp[0][s2 % PP][r + 1]};
-              a2 = __builtin_elementwise_fma(sv2, t2, a2);
-              acc[0][r] = a2.x; acc[0][r + 1] = a2.y;
-            }
-          } else {
+          for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mt][r] = fmaf(sv, tmp[mt][s2 % PP][r], acc[mt][r]);
-            }
+            for (int r = 0; r < 16; ++r) acc[mt][r] = fmaf(sv, tmp[mt][s2 % PP][r], acc[mt][r]);
           }
         }
       }
@@ -592,7 +540,7 @@ __global__ void __launch_bounds__(NW * 64, 2) w4a16_gemm_ks_kernel(const GemmKPa
 // 33 <= M <= 64: two row tiles, one chunk per wave, 8 waves (the register budget: see the kernel header)
 template <typename T, int NG>
 static void launch_ks_mt2(const GemmKParams& kp, int n_blocks, hipStream_t st) {
-  hipLaunchKernelGGL((w4a16_gemm_ks_kernel<T, 1, NG, 8, false, false, 2>), dim3((unsigned)n_blocks), dim3(512),
+  hipLaunchKernelGGL((w4a16_gemm_ks_kernel<T, 1, NG, 8, 2>), dim3((unsigned)n_blocks), dim3(512),
                      w4_ks_lds_bytes(8), st, kp);
 }
 
@@ -641,27 +589,11 @@ bool gemm_ks_config_ok(int ng, int cw, int nw, int mt) {
 
 void launch_gemm_ks(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
   const int ng = pl.ng, mt = pl.ks.mt, cw = pl.ks.cw, nw = pl.ks.nw, n_blocks = pl.n_blocks();
-  if (mt == 2) {  // (ng == 1: gemm_ks_config_ok)
-    if (dtype == SLM_BF16) launch_ks_mt2<bf16_tag, 1>(kp, n_blocks, st);
-    else launch_ks_mt2<f16_tag, 1>(kp, n_blocks, st);
-    return;
-  }
-  if ((kp.ks_dbg & 8) && !(kp.ks_dbg & 4) && dtype == SLM_BF16 && ng == 1 && nw == 8 && cw == 4) {  // packed-fma probe
-    hipLaunchKernelGGL((w4a16_gemm_ks_kernel<bf16_tag, 4, 1, 8, false, true>), dim3((unsigned)n_blocks), dim3(512),
-                       w4_ks_lds_bytes(8), st, kp);
-    return;
-  }
-  if ((kp.ks_dbg & 4) && dtype == SLM_BF16 && ng == 1 && nw == 8 && (cw == 4 || cw == 2)) {  // timeline probe
-    if (cw == 4)
-      hipLaunchKernelGGL((w4a16_gemm_ks_kernel<bf16_tag, 4, 1, 8, true>), dim3((unsigned)n_blocks), dim3(512),
-                         w4_ks_lds_bytes(8), st, kp);
-    else
-      hipLaunchKernelGGL((w4a16_gemm_ks_kernel<bf16_tag, 2, 1, 8, true>), dim3((unsigned)n_blocks), dim3(512),
-                         w4_ks_lds_bytes(8), st, kp);
-    return;
-  }
-  if (dtype == SLM_BF16) launch_ks_cw<bf16_tag>(kp, ng, cw, nw, n_blocks, st);
-  else launch_ks_cw<f16_tag>(kp, ng, cw, nw, n_blocks, st);
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (mt == 2) launch_ks_mt2<T, 1>(kp, n_blocks, st);  // (ng == 1: gemm_ks_config_ok)
+    else launch_ks_cw<T>(kp, ng, cw, nw, n_blocks, st);
+  });
 }
 
 }  // namespace slm

@@ -29,16 +29,13 @@
 // Epilogues as in w4.hip: 16-bit store (+ bias), fp32 split-K slabs (reduce kernel or the consumer,
 // SLM_W4_DEFER_REDUCE), SiLU*mul on (gate, up) tile pairs held by adjacent waves (SLM_W4_SILU_MUL).
 #include "w4_plan.h"
+#include "w4_epilogue.h"
 
 namespace slm {
 
 constexpr int M128_KC = 64;               // K chunk of the main loop
 constexpr int M128_BUF = 128 * 128;       // one activation buffer: 128 rows x 64 k x 2 B
 constexpr uint32_t M128_OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t m128_rsrc(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // NG: scale groups per 64-deep chunk (1: group size >= 64, 2: group size 32)
 // WD: weight ring depth in chunks (= unroll of the chunk loop; the host guarantees chunks % WD == 0)
@@ -98,9 +95,9 @@ w4a16_gemm_m128_kernel(const GemmKParams p) {
   const int ntile = nvalid ? gt : n_tiles - 1;  // (clamped: computes on the last valid tile, no store)
 
   // ---- resources -------------------------------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t a_rs = m128_rsrc(p.a, (uint32_t)(((p.M - 1) * p.lda + p.K) * 2));
-  const __amdgpu_buffer_rsrc_t w_rs = m128_rsrc(p.wq, (uint32_t)((uint64_t)p.K * p.N / 2));
-  const __amdgpu_buffer_rsrc_t sz_rs = m128_rsrc(p.sz, (uint32_t)((uint64_t)p.ks_groups * p.N * 4));
+  const __amdgpu_buffer_rsrc_t a_rs = w4_rsrc(p.a, (uint32_t)(((p.M - 1) * p.lda + p.K) * 2));
+  const __amdgpu_buffer_rsrc_t w_rs = w4_rsrc(p.wq, (uint32_t)((uint64_t)p.K * p.N / 2));
+  const __amdgpu_buffer_rsrc_t sz_rs = w4_rsrc(p.sz, (uint32_t)((uint64_t)p.ks_groups * p.N * 4));
 
   // activations: thread -> AI x (row, 16-B slot) of the 128 x 64 tile
   uint32_t a_voff[AI], a_lds[AI];
@@ -289,52 +286,21 @@ w4a16_gemm_m128_kernel(const GemmKParams p) {
   }
   const bool owner = kw == 0;   // the wave that holds the tile's sums
 
-  // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue (C/D layout: w4_epilogue.h)
+  const DenseRows rows{0, p.M};
+  const int64_t n = (int64_t)ntile * 32 + (lane & 31);
   if (p.silu && p.split_k == 1) {
-    // SLM_W4_SILU_MUL: column tiles are (gate, up) pairs held by waves (0, 1) and (2, 3): the up wave
-    // hands its T-rounded tile to the gate wave through the (now idle) activation buffers
-    const uint16_t* bias = reinterpret_cast<const uint16_t*>(p.bias);
+    // SLM_W4_SILU_MUL: column tiles are (gate, up) pairs held by waves (0, 1) and (2, 3), exchanged through
+    // the (now idle) activation buffers
     uint16_t* ex = reinterpret_cast<uint16_t*>(smem) + (ct >> 1) * (MT * 1024);
-    if (owner && (ct & 1)) {
-      const float bu = bias ? lo_f32<T>((uint32_t)bias[ntile * 32 + (lane & 31)]) : 0.f;
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ex[(m * 16 + r) * 64 + lane] = pack1<T>(acc[m][r] + bu);
-    }
-    __syncthreads();
-    if (!owner || (ct & 1) || !nvalid) return;
-    const int64_t gcol = (int64_t)ntile * 32 + (lane & 31), ocol = (int64_t)(ntile >> 1) * 32 + (lane & 31);
-    const float bg = bias ? lo_f32<T>((uint32_t)bias[gcol]) : 0.f;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const float g = lo_f32<T>((uint32_t)pack1<T>(acc[m][r] + bg));
-        const float uu = lo_f32<T>((uint32_t)ex[(m * 16 + r) * 64 + lane]);
-        if (row < p.M) reinterpret_cast<uint16_t*>(p.c)[row * p.ldc + ocol] = pack1<T>(silu_mul1(g, uu));
-      }
-    }
+    cd_silu_exchange<T, MT>(acc, rows, lane, ex, owner && (ct & 1), owner && !(ct & 1) && nvalid, p.bias, ntile, p.c,
+                            p.ldc, ntile >> 1);
     return;
   }
   if (!owner || !nvalid) return;
-  const int64_t n = (int64_t)ntile * 32 + (lane & 31);
   float bv = 0.f;
   if (p.split_k == 1 && p.bias) bv = lo_f32<T>((uint32_t)reinterpret_cast<const uint16_t*>(p.bias)[n]);
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t row = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (row < p.M) {
-        if (p.split_k == 1)
-          reinterpret_cast<uint16_t*>(p.c)[row * p.ldc + n] = pack1<T>(acc[m][r] + bv);
-        else
-          p.part[((int64_t)ks * p.M + row) * p.N + n] = acc[m][r];
-      }
-    }
-  }
+  cd_store_splitk<T, MT>(acc, rows, lane, p.split_k == 1, p.c, p.ldc, ntile, bv, p.part, (int64_t)ks * p.M, p.N);
 }
 
 template <typename T, int KW, int CT, bool ADMA>
@@ -357,17 +323,13 @@ static void launch_m128_t(const GemmKParams& kp, int ng, int wd, int n_blocks, h
 void launch_gemm_m128(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
   const int ng = pl.ng == 4 ? 2 : 1;  // scale groups per 64-deep chunk
   const int wd = pl.m128.wd, kw = pl.m128.kw, ct = pl.m128.ct, adma = pl.m128.adma, n_blocks = pl.n_blocks();
-  if (dtype == SLM_BF16) {
-    if (ct == 8 && adma) launch_m128_t<bf16_tag, 1, 8, true>(kp, ng, wd, n_blocks, st);
-    else if (ct == 8) launch_m128_t<bf16_tag, 1, 8, false>(kp, ng, wd, n_blocks, st);
-    else if (kw == 2) launch_m128_t<bf16_tag, 2, 4, false>(kp, ng, wd, n_blocks, st);
-    else launch_m128_t<bf16_tag, 1, 4, false>(kp, ng, wd, n_blocks, st);
-  } else {
-    if (ct == 8 && adma) launch_m128_t<f16_tag, 1, 8, true>(kp, ng, wd, n_blocks, st);
-    else if (ct == 8) launch_m128_t<f16_tag, 1, 8, false>(kp, ng, wd, n_blocks, st);
-    else if (kw == 2) launch_m128_t<f16_tag, 2, 4, false>(kp, ng, wd, n_blocks, st);
-    else launch_m128_t<f16_tag, 1, 4, false>(kp, ng, wd, n_blocks, st);
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (ct == 8 && adma) launch_m128_t<T, 1, 8, true>(kp, ng, wd, n_blocks, st);
+    else if (ct == 8) launch_m128_t<T, 1, 8, false>(kp, ng, wd, n_blocks, st);
+    else if (kw == 2) launch_m128_t<T, 2, 4, false>(kp, ng, wd, n_blocks, st);
+    else launch_m128_t<T, 1, 4, false>(kp, ng, wd, n_blocks, st);
+  });
 }
 
 }  // namespace slm

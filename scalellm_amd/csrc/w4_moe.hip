@@ -15,6 +15,7 @@
 // device-side n_padded return at once: the grid is sized for the worst case so that a captured graph replays
 // for any routing.
 #include "w4_stream32.h"
+#include "w4_epilogue.h"
 
 namespace slm {
 
@@ -77,44 +78,19 @@ __global__ void __launch_bounds__(256, 2) w4a16_moe_gemm_kernel(const MoeGemmKPa
   const char* szlane = p.sz + (int64_t)e * p.sz_stride + (nt * 32 + (lane & 31)) * 4;
   const uint32_t wstride = (uint32_t)(n_tiles * 1024);  // bytes per 64-deep half chunk
   const uint32_t szstride = (uint32_t)(p.N * 4);        // bytes per scale group
-  const int cpg_shift = p.gs_shift >= 30 ? 30 : (p.gs_shift > 7 ? p.gs_shift - 7 : 0);
-  const f32x16 acc = w4_stream32<T, NG, SPAN>(smem, a_src, a_dst, wlane, szlane, wstride, szstride, cpg_shift, 0,
-                                              p.n_chunks, lane & 31, lane >> 5);
+  const f32x16 acc[1] = {w4_stream32<T, NG, SPAN>(smem, a_src, a_dst, wlane, szlane, wstride, szstride,
+                                                  w4_cpg_shift(p.gs_shift), 0, p.n_chunks, lane & 31, lane >> 5)};
 
-  // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5);
-  // the row goes to C[idx]; s_idx was written before the first barrier
-  const int64_t ncol = nt * 32 + (lane & 31);
-  uint16_t* cbase = reinterpret_cast<uint16_t*>(p.c);
+  // ---- epilogue (C/D layout: w4_epilogue.h); the row goes to C[idx]; s_idx was written before the first barrier
+  const ScatterRows rows{s_idx, p.n_flat, p.row_scale};
   if (p.silu) {
-    // SLM_W4_SILU_MUL: waves (0, 1) and (2, 3) hold a (gate, up) tile pair; the up wave hands its
-    // T-rounded tile to the gate wave through the (now idle) A buffers; same lane, same r
+    // SLM_W4_SILU_MUL: waves (0, 1) and (2, 3) hold a (gate, up) tile pair
     uint16_t* ex = reinterpret_cast<uint16_t*>(smem) + (wave >> 1) * 1024;
-    if (wave & 1) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ex[r * 64 + lane] = pack1<T>(acc[r]);
-    }
-    __syncthreads();
-    if ((wave & 1) || !nvalid) return;
-    const int64_t ocol = (nt >> 1) * 32 + (lane & 31);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int fi = s_idx[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
-      const float g = lo_f32<T>((uint32_t)pack1<T>(acc[r]));
-      const float u = lo_f32<T>((uint32_t)ex[r * 64 + lane]);
-      if ((unsigned)fi < (unsigned)p.n_flat) cbase[(int64_t)fi * p.ldc + ocol] = pack1<T>(silu_mul1(g, u));
-    }
+    cd_silu_exchange<T, 1>(acc, rows, lane, ex, wave & 1, !(wave & 1) && nvalid, nullptr, 0, p.c, p.ldc, nt >> 1);
     return;
   }
   if (!nvalid) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int fi = s_idx[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
-    if ((unsigned)fi < (unsigned)p.n_flat) {
-      float v = acc[r];
-      if (p.row_scale) v *= p.row_scale[fi];
-      cbase[(int64_t)fi * p.ldc + ncol] = pack1<T>(v);
-    }
-  }
+  cd_store<T, 1>(acc, rows, lane, p.c, p.ldc, nt, 0.f);
 }
 
 template <typename T, int NG, bool SPAN>
@@ -186,8 +162,7 @@ SLM_API int slm_moe_w4a16_gemm(const slm_moe_gemm_args* a, void* stream) {
   const int ng = gs == 32 ? 4 : gs == 64 ? 2 : 1;
   hip_clear_error();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a->dtype == SLM_BF16) launch_moe_ng<bf16_tag>(kp, ng, (unsigned)grid, st);
-  else launch_moe_ng<f16_tag>(kp, ng, (unsigned)grid, st);
+  dispatch_dtype(a->dtype, [&](auto t) { launch_moe_ng<decltype(t)>(kp, ng, (unsigned)grid, st); });
   return hip_check_launch();
 }
 

@@ -75,11 +75,12 @@ __global__ void __launch_bounds__(256, 2) w4a16_gemm_small_kernel(const GemmKPar
   const char* szlane = reinterpret_cast<const char*>(p.sz + nt * 32 + (lane & 31));
   const uint32_t wstride = (uint32_t)(n_tiles * 1024);  // bytes per 64-deep half chunk
   const uint32_t szstride = (uint32_t)(p.N * 4);        // bytes per scale group
-  const int cpg_shift = p.gs_shift >= 30 ? 30 : (p.gs_shift > 7 ? p.gs_shift - 7 : 0);  // log2(chunks per group)
-  const f32x16 acc = w4_stream32<T, NG, SPAN>(smem, a_src, a_dst, wlane, szlane, wstride, szstride, cpg_shift, c0,
-                                              c1, lane & 31, lane >> 5);
+  const f32x16 acc = w4_stream32<T, NG, SPAN>(smem, a_src, a_dst, wlane, szlane, wstride, szstride,
+                                              w4_cpg_shift(p.gs_shift), c0, c1, lane & 31, lane >> 5);
 
-  // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Kept local
+  // and written out: with the shared cd_store / cd_silu_exchange of w4_epilogue.h gate_up at M = 32 measured 2.6 %
+  // slower, and with only the row through cd_row() still 3.9 % (hipcc schedules the whole kernel differently)
   const int64_t ncol = nt * 32 + (lane & 31);
   float bv = 0.f;
   if (p.split_k == 1 && p.bias) {
@@ -134,9 +135,7 @@ static void launch_small_ng(const GemmKParams& kp, int ng, int n_blocks, hipStre
 }
 
 void launch_gemm_small(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
-  const int ng = pl.ng, n_blocks = pl.n_blocks();
-  if (dtype == SLM_BF16) launch_small_ng<bf16_tag>(kp, ng, n_blocks, st);
-  else launch_small_ng<f16_tag>(kp, ng, n_blocks, st);
+  dispatch_dtype(dtype, [&](auto t) { launch_small_ng<decltype(t)>(kp, pl.ng, pl.n_blocks(), st); });
 }
 
 }  // namespace slm

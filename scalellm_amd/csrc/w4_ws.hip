@@ -34,6 +34,7 @@
 // (~2000 cycles) to land: with one 64-deep chunk of lead (the previous version) the measured
 // issue -> landed time of a 32 KiB chunk (~1100 cycles from L2, more from HBM) was fully exposed.
 #include "w4_plan.h"
+#include "w4_epilogue.h"
 
 namespace slm {
 
@@ -304,74 +305,24 @@ __global__ void __launch_bounds__(512, 2) w4a16_gemm_ws_kernel(const GemmKParams
   // accumulator tile is C^T: this lane holds token m = tile row base + (lane & 31) and the 16
   // columns n = 32 t + (r & 3) + 8 (r >> 2) + 4 (lane >> 5) -- four consecutive columns per
   // r >> 2, i.e. one 8-byte (bf16/fp16) or 16-byte (fp32 partial) store instead of four 2-byte ones.
-  if (p.silu && p.split_k == 1) {
-    store_ct_silu_pair<T>(p, acc, (int64_t)nb * 4 + nh * 2, m0 + mh * 128 + (lane & 31), lane);
-    return;
-  }
-  const bool wide = ((p.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.c) & 7) == 0);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int64_t t = (int64_t)nb * 4 + nh * 2 + j;
-    if (t >= n_tiles) continue;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t ncol = t * 32 + 8 * q + 4 * (lane >> 5);
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (p.split_k == 1 && p.bias) {
-        const u32x2 b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(p.bias) + ncol);
-        bv[0] = lo_f32<T>(b.x); bv[1] = hi_f32<T>(b.x);
-        bv[2] = lo_f32<T>(b.y); bv[3] = hi_f32<T>(b.y);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t row = m0 + (mh * 4 + i) * 32 + (lane & 31);
-        if (row >= p.M) continue;
-        const float v0 = acc[j][i][4 * q + 0], v1 = acc[j][i][4 * q + 1];
-        const float v2 = acc[j][i][4 * q + 2], v3 = acc[j][i][4 * q + 3];
-        if (p.split_k == 1) {
-          uint16_t* dst = reinterpret_cast<uint16_t*>(p.c) + row * p.ldc + ncol;
-          u32x2 o;
-          o.x = pack2<T>(v0 + bv[0], v1 + bv[1]);
-          o.y = pack2<T>(v2 + bv[2], v3 + bv[3]);
-          if (wide) {
-            *reinterpret_cast<u32x2*>(dst) = o;
-          } else {
-            dst[0] = (uint16_t)(o.x & 0xffffu); dst[1] = (uint16_t)(o.x >> 16);
-            dst[2] = (uint16_t)(o.y & 0xffffu); dst[3] = (uint16_t)(o.y >> 16);
-          }
-        } else {
-          const f32x4 o = {v0, v1, v2, v3};
-          *reinterpret_cast<f32x4*>(p.part + ((int64_t)ks * p.M + row) * p.N + ncol) = o;
-        }
-      }
-    }
-  }
+  // (ct_store, w4_epilogue.h; wave (mh, nh) holds column tiles 4 nb + 2 nh, + 1)
+  ct_store<T>(p, acc, (int64_t)nb * 4 + nh * 2, m0 + mh * 128 + (lane & 31), lane, ks, p.split_k == 1);
 }
 
-template <typename T, int NGC, bool WNT>
+template <typename T, int NGC>
 static void launch_ws(const GemmKParams& kp, int n_blocks, hipStream_t st) {
-  auto kfn = w4a16_gemm_ws_kernel<T, NGC, WNT>;
-  static bool opted[64] = {};  // > 64 KiB of dynamic LDS: opted into once per kernel AND per device
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (devi < 0 || devi >= 64 || !opted[devi]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_WS_LDS_BYTES);
-    if (devi >= 0 && devi < 64) opted[devi] = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3((unsigned)n_blocks), dim3(512), W4_WS_LDS_BYTES, st, kp);
+  // every weight read by one row block only: stream it past the caches
+  if (kp.n_mblocks <= 1) launch_big_lds<w4a16_gemm_ws_kernel<T, NGC, true>>(kp, n_blocks, 512, W4_WS_LDS_BYTES, st);
+  else launch_big_lds<w4a16_gemm_ws_kernel<T, NGC, false>>(kp, n_blocks, 512, W4_WS_LDS_BYTES, st);
 }
 
 void launch_gemm_ws(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
-  const int ng = pl.ng, n_blocks = pl.n_blocks();  // ng = scale groups per 128 of K: 4 for group 32 -> 2 per 64-deep chunk
-  const bool once = kp.n_mblocks <= 1;  // every weight read by one row block only: stream it past the caches
-  if (dtype == SLM_BF16) {
-    if (ng == 4) (once ? launch_ws<bf16_tag, 2, true>(kp, n_blocks, st) : launch_ws<bf16_tag, 2, false>(kp, n_blocks, st));
-    else (once ? launch_ws<bf16_tag, 1, true>(kp, n_blocks, st) : launch_ws<bf16_tag, 1, false>(kp, n_blocks, st));
-  } else {
-    if (ng == 4) (once ? launch_ws<f16_tag, 2, true>(kp, n_blocks, st) : launch_ws<f16_tag, 2, false>(kp, n_blocks, st));
-    else (once ? launch_ws<f16_tag, 1, true>(kp, n_blocks, st) : launch_ws<f16_tag, 1, false>(kp, n_blocks, st));
-  }
+  const int n_blocks = pl.n_blocks();
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (pl.ng == 4) launch_ws<T, 2>(kp, n_blocks, st);  // group 32: two scale groups per 64-deep chunk
+    else launch_ws<T, 1>(kp, n_blocks, st);
+  });
 }
 
 }  // namespace slm

@@ -17,6 +17,7 @@
 // prefetch reads of the next unit, so lgkmcnt(6) covers them; its DMA of unit g+2 is older than 6
 // DMAs and 2 refills).  LDS: A 7 x 16 KiB + B 3 x 16 KiB = 160 KiB, one workgroup per CU.
 #include "w4_plan.h"
+#include "w4_epilogue.h"
 
 namespace slm {
 
@@ -223,58 +224,15 @@ __device__ __forceinline__ void xl_pass(const GemmKParams& p, char* smem, const 
   if constexpr (MULTI) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// ---- epilogue (C^T accumulators: lane = token, 4 consecutive columns per r >> 2) ----
-// final = true: T(acc + bias) into c;  false: fp32 into the split-K slab `ks` of p.part
+// ---- epilogue (C^T accumulators: ct_store, w4_epilogue.h): wave (mh, nq) holds column tiles 8 nb + 2 nq, + 1 over
+// the rows 256 mb + 128 mh ..
 template <typename T>
 __device__ __forceinline__ void xl_store(const GemmKParams& p, const f32x16 (&acc)[2][4], const int nb, const int mb,
-                                         const int ks, const bool final) {
+                                         const int ks, const bool final_out) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int64_t m0 = (int64_t)mb * 256;
-  const int64_t n_tiles = p.N / 32;
   const int mh = wave >> 2, nq = wave & 3;
-  if (p.silu && final) {
-    store_ct_silu_pair<T>(p, acc, (int64_t)nb * 8 + nq * 2, m0 + mh * 128 + (lane & 31), lane);
-    return;
-  }
-  const bool wide = ((p.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.c) & 7) == 0);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int64_t t = (int64_t)nb * 8 + nq * 2 + j;
-    if (t >= n_tiles) continue;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t ncol = t * 32 + 8 * q + 4 * (lane >> 5);
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (final && p.bias) {
-        const u32x2 b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(p.bias) + ncol);
-        bv[0] = lo_f32<T>(b.x); bv[1] = hi_f32<T>(b.x);
-        bv[2] = lo_f32<T>(b.y); bv[3] = hi_f32<T>(b.y);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t row = m0 + (mh * 4 + i) * 32 + (lane & 31);
-        if (row >= p.M) continue;
-        const float v0 = acc[j][i][4 * q + 0], v1 = acc[j][i][4 * q + 1];
-        const float v2 = acc[j][i][4 * q + 2], v3 = acc[j][i][4 * q + 3];
-        if (final) {
-          uint16_t* dst = reinterpret_cast<uint16_t*>(p.c) + row * p.ldc + ncol;
-          u32x2 o;
-          o.x = pack2<T>(v0 + bv[0], v1 + bv[1]);
-          o.y = pack2<T>(v2 + bv[2], v3 + bv[3]);
-          if (wide) {
-            *reinterpret_cast<u32x2*>(dst) = o;
-          } else {
-            dst[0] = (uint16_t)(o.x & 0xffffu); dst[1] = (uint16_t)(o.x >> 16);
-            dst[2] = (uint16_t)(o.y & 0xffffu); dst[3] = (uint16_t)(o.y >> 16);
-          }
-        } else {
-          const f32x4 o = {v0, v1, v2, v3};
-          *reinterpret_cast<f32x4*>(p.part + ((int64_t)ks * p.M + row) * p.N + ncol) = o;
-        }
-      }
-    }
-  }
+  ct_store<T>(p, acc, (int64_t)nb * 8 + nq * 2, (int64_t)mb * 256 + mh * 128 + (lane & 31), lane, ks, final_out);
 }
 
 template <typename T, int NGC, bool WNT>
@@ -336,15 +294,13 @@ __global__ void __launch_bounds__(512, 2) w4a16_gemm_xl_sk_kernel(const GemmKPar
   const int64_t w1 = w0 + per < W ? w0 + per : W;
   const int t_first = (int)(w0 / nc), t_last = (int)((w1 - 1) / nc);
   const bool has_partial = w1 < (int64_t)(t_last + 1) * nc;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(p.sk_part, 0, (int)(W4_XL_SK_WGS * W4_XL_SK_SLOT_BYTES), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = w4_rsrc(p.sk_part, (uint32_t)(W4_XL_SK_WGS * W4_XL_SK_SLOT_BYTES));
   unsigned* flags = p.sk_sync + 1;
   f32x16 acc[2][4];
   if (has_partial) {
     const int64_t tb = (int64_t)t_last * nc;
     const int k0 = (int)((w0 > tb ? w0 : tb) - tb), k1 = (int)(w1 - tb);
     xl_pass<T, NGC, WNT, true>(p, smem, t_last % p.n_nblocks, t_last / p.n_nblocks, 2 * k0, 2 * k1, acc);
-    if (!(p.ks_dbg & 1))
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -370,7 +326,7 @@ __global__ void __launch_bounds__(512, 2) w4a16_gemm_xl_sk_kernel(const GemmKPar
     const int64_t tb = (int64_t)t * nc;
     const int k0 = (int)((w0 > tb ? w0 : tb) - tb);
     xl_pass<T, NGC, WNT, true>(p, smem, t % p.n_nblocks, t / p.n_nblocks, 2 * k0, 2 * nc, acc);
-    if (k0 > 0 && !(p.ks_dbg & 2)) {   // the partial slots of the workgroups in front, in workgroup order
+    if (k0 > 0) {   // the partial slots of the workgroups in front, in workgroup order
       const int g_first = (int)(tb / per);
       for (int gp = g_first; gp < g; ++gp) {
         if (threadIdx.x == 0) {
@@ -404,56 +360,29 @@ __global__ void __launch_bounds__(512, 2) w4a16_gemm_xl_sk_kernel(const GemmKPar
   }
 }
 
-template <typename T, int NGC, bool WNT>
-static void launch_xl_sk(const GemmKParams& kp, int n_wgs, hipStream_t st) {
-  auto kfn = w4a16_gemm_xl_sk_kernel<T, NGC, WNT>;
-  static bool opted[64] = {};  // > 64 KiB of dynamic LDS: opted into once per kernel AND per device
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (devi < 0 || devi >= 64 || !opted[devi]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_XL_LDS_BYTES);
-    if (devi >= 0 && devi < 64) opted[devi] = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3((unsigned)n_wgs), dim3(512), W4_XL_LDS_BYTES, st, kp);
-}
-
 void launch_gemm_xl_sk(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
-  const int ng = pl.ng, n_wgs = W4_XL_SK_WGS;
   // (several row blocks always re-read the weights here: cacheable loads)
-  if (dtype == SLM_BF16) {
-    if (ng == 4) launch_xl_sk<bf16_tag, 2, false>(kp, n_wgs, st);
-    else launch_xl_sk<bf16_tag, 1, false>(kp, n_wgs, st);
-  } else {
-    if (ng == 4) launch_xl_sk<f16_tag, 2, false>(kp, n_wgs, st);
-    else launch_xl_sk<f16_tag, 1, false>(kp, n_wgs, st);
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (pl.ng == 4) launch_big_lds<w4a16_gemm_xl_sk_kernel<T, 2, false>>(kp, W4_XL_SK_WGS, 512, W4_XL_LDS_BYTES, st);
+    else launch_big_lds<w4a16_gemm_xl_sk_kernel<T, 1, false>>(kp, W4_XL_SK_WGS, 512, W4_XL_LDS_BYTES, st);
+  });
 }
 
-template <typename T, int NGC, bool WNT>
+template <typename T, int NGC>
 static void launch_xl(const GemmKParams& kp, int n_blocks, hipStream_t st) {
-  auto kfn = w4a16_gemm_xl_kernel<T, NGC, WNT>;
-  static bool opted[64] = {};  // > 64 KiB of dynamic LDS: opted into once per kernel AND per device
-  int devi = 0;
-  (void)hipGetDevice(&devi);
-  if (devi < 0 || devi >= 64 || !opted[devi]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_XL_LDS_BYTES);
-    if (devi >= 0 && devi < 64) opted[devi] = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3((unsigned)n_blocks), dim3(512), W4_XL_LDS_BYTES, st, kp);
+  // every weight read by one row block only: stream it past the caches
+  if (kp.n_mblocks <= 1) launch_big_lds<w4a16_gemm_xl_kernel<T, NGC, true>>(kp, n_blocks, 512, W4_XL_LDS_BYTES, st);
+  else launch_big_lds<w4a16_gemm_xl_kernel<T, NGC, false>>(kp, n_blocks, 512, W4_XL_LDS_BYTES, st);
 }
 
 void launch_gemm_xl(const GemmKParams& kp, int dtype, const GemmPlan& pl, hipStream_t st) {
-  const int ng = pl.ng, n_blocks = pl.n_blocks();  // ng = scale groups per 128 of K: 4 for group 32 -> 2 per 64-deep chunk
-  const bool once = kp.n_mblocks <= 1;  // every weight read by one row block only: stream it past the caches
-  if (dtype == SLM_BF16) {
-    if (ng == 4) (once ? launch_xl<bf16_tag, 2, true>(kp, n_blocks, st) : launch_xl<bf16_tag, 2, false>(kp, n_blocks, st));
-    else (once ? launch_xl<bf16_tag, 1, true>(kp, n_blocks, st) : launch_xl<bf16_tag, 1, false>(kp, n_blocks, st));
-  } else {
-    if (ng == 4) (once ? launch_xl<f16_tag, 2, true>(kp, n_blocks, st) : launch_xl<f16_tag, 2, false>(kp, n_blocks, st));
-    else (once ? launch_xl<f16_tag, 1, true>(kp, n_blocks, st) : launch_xl<f16_tag, 1, false>(kp, n_blocks, st));
-  }
+  const int n_blocks = pl.n_blocks();
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (pl.ng == 4) launch_xl<T, 2>(kp, n_blocks, st);  // group 32: two scale groups per 64-deep chunk
+    else launch_xl<T, 1>(kp, n_blocks, st);
+  });
 }
 
 }  // namespace slm
