@@ -636,7 +636,11 @@ SLM_API int32_t slm_decode_lane_policy_measured(const slm_lane_query* q);
 /*    A row's outputs depend only on its logits, parameters, seed and         */
 /*    position: not on its row index, the batch, or eager vs graph replay.    */
 /*    Bit-identical across repeats (no float atomics; fixed reduction order). */
-/*    Finite logits assumed.  One 1024-thread workgroup per row.              */
+/*    Logits are finite or -inf (a token an earlier slm_logits_process       */
+/*    filtered): a -inf carries no mass, is never drawn, has logprob -inf and */
+/*    ranks after every finite value, by id.  Each row needs one finite       */
+/*    logit; +inf and NaN are not supported.  One 1024-thread workgroup per   */
+/*    row.                                                                    */
 /* ========================================================================== */
 #define SLM_SAMPLE_MAX_TOP 20
 typedef struct slm_sampling_args {
