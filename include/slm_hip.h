@@ -1052,6 +1052,73 @@ SLM_API int slm_mla_set_kv_cache(const int32_t* slot_ids /* [n_tokens] */, const
                                  int64_t k_rope_slot_stride, int64_t n_tokens, int32_t head_dim,
                                  int32_t rope_head_dim, int32_t dtype, void* stream);
 
+/* ========================================================================== */
+/* 12. Gemma family: Gemma RMSNorm (plain, sandwich, embedding) and soft cap  */
+/*    mirrors   kernel::gemma_rms_norm  src/kernels/layernorm_kernels.cu:66   */
+/*              (math src/layers/normalization.h:31-40), the layer of         */
+/*              src/models/google/gemma2.h:186-204, its scaled embedding      */
+/*              (:236-238,270) and its logit cap (:341-342)                   */
+/*    GN(h, w)[i] = T(h[i] * rs * (1 + w[i])),  rs = rsqrt(mean(h^2) + eps):  */
+/*    fp32 arithmetic and ONE rounding to T (f16 / bf16) at the end -- Gemma's */
+/*    (x (1 + w)).to(T), not section 3's T(T(h rs) w).  h is always a row of  */
+/*    T values.  One launch, one workgroup per token.  The form is chosen by  */
+/*    which pointers are set:                                                 */
+/*      A plain     x, pre_weight, out                                        */
+/*                    out = GN(x, pre_weight)                                 */
+/*      B sandwich  residual (in/out), x OR partials (+ n_splits),            */
+/*                  post_weight (NULL: y = x, Gemma-1's plain residual        */
+/*                  layer), pre_weight and out (both set or both NULL)        */
+/*                    y = GN(x, post_weight); residual = T(y + residual);     */
+/*                    out = GN(residual, pre_weight)   (skipped when NULL)    */
+/*                  partials = fp32 split-K slabs [n_splits, n_tokens, dim]   */
+/*                  of a deferred GEMM (SLM_W4_DEFER_REDUCE); x is then       */
+/*                  T(sum of the slabs), summed and rounded exactly as the    */
+/*                  reduce kernel and slm_rms_norm_splitk do                  */
+/*      C embed     table [vocab, dim], token_ids [n_tokens], x_scale,        */
+/*                  residual (output only), pre_weight, out                   */
+/*                    residual = T(table[id] * x_scale);                      */
+/*                    out = GN(residual, pre_weight)                          */
+/*                  x_scale is used as the fp32 value given: pass a value of  */
+/*                  T (Gemma: T(sqrt(hidden))) and the product is exact       */
+/*                  before its rounding.  An id outside [0, vocab) is clamped */
+/*                  into the table.                                           */
+/*    out may be x.  Every other pointer combination: SLM_ERR_INVALID_ARG     */
+/*    before any launch.  dim % 8 == 0 and dim <= 16384 and f16 / bf16, else  */
+/*    SLM_ERR_UNSUPPORTED; every pointer 16-byte aligned (token_ids: 4), else */
+/*    SLM_ERR_ALIGNMENT.  Rows at or beyond n_tokens are never written;       */
+/*    n_tokens == 0 is SLM_OK without a launch.                               */
+/* ========================================================================== */
+typedef struct slm_gemma_norm_args {
+  void* out;                 /* [n_tokens, dim]                                */
+  const void* x;             /* [n_tokens, dim], or NULL                       */
+  const float* partials;     /* [n_splits, n_tokens, dim] fp32, or NULL        */
+  const void* post_weight;   /* [dim], or NULL                                 */
+  const void* pre_weight;    /* [dim], or NULL (form B only)                   */
+  void* residual;            /* [n_tokens, dim], or NULL (form A)              */
+  const void* table;         /* [vocab, dim], or NULL                          */
+  const int32_t* token_ids;  /* [n_tokens], or NULL                            */
+  int64_t vocab;             /* rows of table (form C)                         */
+  int64_t n_tokens;
+  int64_t dim;
+  int32_t n_splits;          /* slabs in partials                              */
+  int32_t dtype;             /* slm_dtype of every 16-bit tensor               */
+  float x_scale;             /* form C                                         */
+  float eps;
+} slm_gemma_norm_args;
+
+SLM_API int slm_gemma_norm(const slm_gemma_norm_args* a, void* stream);
+
+/* out = T(cap * tanh(x / cap)) over [n_rows, row_len] contiguous, in fp32 with ONE rounding to T.
+ * The reference (gemma2.h:341-342) runs three element-wise ops on T and rounds three times (after the
+ * division, after tanh, after the multiplication); this rounds once, so it is the closer of the two
+ * to the real-valued function and differs from the reference in the last place of some elements.
+ * tanh keeps a relative error of a few fp32 ulps at every magnitude (an odd polynomial below
+ * |x / cap| = 0.25).  out == x (in place) is allowed.  cap must be positive and finite
+ * (SLM_ERR_INVALID_ARG); row_len % 8 == 0 and f16 / bf16 (SLM_ERR_UNSUPPORTED); 16-byte aligned
+ * pointers (SLM_ERR_ALIGNMENT); n_rows == 0 is SLM_OK without a launch. */
+SLM_API int slm_soft_cap(void* out, const void* x, int64_t n_rows, int64_t row_len, float cap, int32_t dtype,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

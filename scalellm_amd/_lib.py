@@ -193,6 +193,16 @@ class MlaArgs(C.Structure):
     ]
 
 
+class GemmaNormArgs(C.Structure):
+    """struct slm_gemma_norm_args (include/slm_hip.h section 12)."""
+    _fields_ = [
+        ("out", C.c_void_p), ("x", C.c_void_p), ("partials", C.c_void_p), ("post_weight", C.c_void_p),
+        ("pre_weight", C.c_void_p), ("residual", C.c_void_p), ("table", C.c_void_p), ("token_ids", C.c_void_p),
+        ("vocab", C.c_int64), ("n_tokens", C.c_int64), ("dim", C.c_int64),
+        ("n_splits", C.c_int32), ("dtype", C.c_int32), ("x_scale", C.c_float), ("eps", C.c_float),
+    ]
+
+
 SLM_MOE_SILU_MUL = 2    # slm_moe_gemm flags
 SLM_MOE_GEMM_BLOCK = 32  # rows per block of the grouped GEMM: the align step's block_size
 
@@ -324,6 +334,9 @@ def lib() -> C.CDLL:
         ("slm_mla_set_kv_cache", C.c_int,
          [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
           C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+        ("slm_gemma_norm", C.c_int, [C.POINTER(GemmaNormArgs), C.c_void_p]),
+        ("slm_soft_cap", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
     ]:
         fn = getattr(L, name)  # AttributeError here = library/header mismatch: fail loudly
         fn.restype = restype

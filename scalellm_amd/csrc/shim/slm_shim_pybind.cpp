@@ -51,6 +51,27 @@ PYBIND11_MODULE(_slm_shim, m) {
                          std::optional<torch::Tensor> bias, float eps) {
     llm::kernel::layer_norm(out, input, weight, bias.has_value() ? *bias : torch::Tensor(), eps);
   });
+  m.def("gemma_rms_norm", [](torch::Tensor out, torch::Tensor input, torch::Tensor weight, float eps) {
+    llm::kernel::gemma_rms_norm(out, input, weight, eps);
+  });
+  m.def("gemma_sandwich_norm",
+        [](std::optional<torch::Tensor> out, const torch::Tensor& input, std::optional<torch::Tensor> post_weight,
+           torch::Tensor residual, std::optional<torch::Tensor> pre_weight, float eps) {
+          slm::gemma_sandwich_norm(out.value_or(torch::Tensor()), input, post_weight.value_or(torch::Tensor()),
+                                   residual, pre_weight.value_or(torch::Tensor()), eps);
+        },
+        py::arg("out"), py::arg("input"), py::arg("post_weight"), py::arg("residual"), py::arg("pre_weight"),
+        py::arg("eps"));
+  m.def("soft_cap", &slm::soft_cap, py::arg("out"), py::arg("input"), py::arg("cap"));
+  py::class_<slm::GemmaRMSNorm>(m, "GemmaRMSNorm")
+      .def(py::init([](int64_t dim, float eps, const torch::Tensor& like) {
+             return slm::GemmaRMSNorm(dim, eps, like.options());
+           }),
+           py::arg("dim"), py::arg("eps"), py::arg("like"))
+      .def("forward", &slm::GemmaRMSNorm::forward)
+      .def("load_weight", &slm::GemmaRMSNorm::load_weight)
+      .def("verify_loaded_weights", &slm::GemmaRMSNorm::verify_loaded_weights, py::arg("prefix") = "")
+      .def_property_readonly("weight", &slm::GemmaRMSNorm::weight);
   m.def("gelu_new", &llm::kernel::gelu_new, py::arg("input"));
   m.def("gelu_fast", &llm::kernel::gelu_fast, py::arg("input"));
   m.def("gelu_new_with_mul", &llm::kernel::gelu_new_with_mul, py::arg("input"));

@@ -260,6 +260,20 @@ torch::Tensor silu_with_mul(torch::Tensor input) {
   return out;
 }
 
+void gemma_rms_norm(torch::Tensor& out, torch::Tensor input, torch::Tensor weight, float epsilon) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  TORCH_CHECK(input.is_contiguous() && out.is_contiguous() && weight.is_contiguous(), "gemma_rms_norm: contiguous tensors");
+  slm_gemma_norm_args a = {};
+  a.out = out.mutable_data_ptr();
+  a.x = input.const_data_ptr();
+  a.pre_weight = weight.const_data_ptr();
+  a.dim = input.size(-1);
+  a.n_tokens = a.dim ? input.numel() / a.dim : 0;
+  a.dtype = dtype_code(input);
+  a.eps = epsilon;
+  check(slm_gemma_norm(&a, current_stream(input)), "slm_gemma_norm");
+}
+
 }  // namespace kernel
 }  // namespace llm
 
@@ -521,6 +535,53 @@ void gptq_gemm(const torch::Tensor& A, const torch::Tensor& B, torch::Tensor& C,
 }  // namespace marlin
 
 namespace slm {
+
+torch::Tensor GemmaRMSNorm::forward(const torch::Tensor& input) const {
+  auto out = torch::empty_like(input);
+  llm::kernel::gemma_rms_norm(out, input, weight_, eps_);
+  return out;
+}
+
+void GemmaRMSNorm::load_weight(const torch::Tensor& weight) {
+  TORCH_CHECK(weight.sizes() == weight_.sizes(), "weight size mismatch: ", weight.sizes(), " vs ", weight_.sizes());
+  weight_.copy_(weight);
+  is_loaded_ = true;
+}
+
+void GemmaRMSNorm::verify_loaded_weights(const std::string& prefix) const {
+  TORCH_CHECK(is_loaded_, "weight is not loaded for ", prefix, "weight");
+}
+
+void gemma_sandwich_norm(torch::Tensor out, const torch::Tensor& input, const torch::Tensor& post_weight,
+                         torch::Tensor residual, const torch::Tensor& pre_weight, float epsilon) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  TORCH_CHECK(input.is_contiguous() && residual.is_contiguous() && (!out.defined() || out.is_contiguous()),
+              "gemma_sandwich_norm: contiguous tensors");
+  TORCH_CHECK(residual.sizes() == input.sizes() && (!out.defined() || out.sizes() == input.sizes()),
+              "gemma_sandwich_norm: residual / out do not match the input");
+  slm_gemma_norm_args a = {};
+  a.out = out.defined() ? out.mutable_data_ptr() : nullptr;
+  a.x = input.const_data_ptr();
+  a.post_weight = post_weight.defined() ? post_weight.const_data_ptr() : nullptr;
+  a.pre_weight = pre_weight.defined() ? pre_weight.const_data_ptr() : nullptr;
+  a.residual = residual.mutable_data_ptr();
+  a.dim = input.size(-1);
+  a.n_tokens = a.dim ? input.numel() / a.dim : 0;
+  a.dtype = dtype_code(input);
+  a.eps = epsilon;
+  check(slm_gemma_norm(&a, current_stream(input)), "slm_gemma_norm");
+}
+
+void soft_cap(torch::Tensor out, const torch::Tensor& input, float cap) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  TORCH_CHECK(input.is_contiguous() && out.is_contiguous() && out.sizes() == input.sizes() &&
+                  out.scalar_type() == input.scalar_type() && input.dim() >= 1,
+              "soft_cap: contiguous input / out of one shape and dtype");
+  const int64_t row = input.size(-1);
+  check(slm_soft_cap(out.mutable_data_ptr(), input.const_data_ptr(), row ? input.numel() / row : 0, row, cap,
+                     dtype_code(input), current_stream(input)),
+        "slm_soft_cap");
+}
 
 size_t marlin_sz_cache_entries() {
   std::lock_guard<std::mutex> lk(marlin::g_sz_mu);

@@ -16,6 +16,7 @@
 
 #include <memory>
 #include <optional>
+#include <string>
 #include <vector>
 
 namespace llm {
@@ -73,6 +74,9 @@ torch::Tensor gelu_new(torch::Tensor input);
 torch::Tensor gelu_fast(torch::Tensor input);
 torch::Tensor gelu_new_with_mul(torch::Tensor input);
 torch::Tensor gelu_fast_with_mul(torch::Tensor input);
+// src/kernels/layernorm_kernels.h:11-14: out = T(x * rsqrt(mean(x^2) + eps) * (1 + weight)), fp32 arithmetic and
+// one rounding (include/slm_hip.h section 12, form A)
+void gemma_rms_norm(torch::Tensor& out, torch::Tensor input, torch::Tensor weight, float epsilon);
 
 }  // namespace kernel
 }  // namespace llm
@@ -129,6 +133,32 @@ inline int64_t uniform_kv_hint(int64_t kv_total_len, int64_t n_seqs, int64_t q_m
   return block_table_len == n_seqs * blocks ? n_seqs * kv_max_seq_len : 0;
 }
 
+
+// llm::GemmaRMSNormImpl (src/layers/normalization.h:142-168): forward = kernel::gemma_rms_norm.  `weight` holds the
+// checkpoint's values; the + 1 is applied in the kernel.
+class GemmaRMSNorm {
+ public:
+  GemmaRMSNorm(int64_t dim, float eps, const torch::TensorOptions& options)
+      : weight_(torch::empty({dim}, options)), eps_(eps) {}
+  torch::Tensor forward(const torch::Tensor& input) const;
+  // copies `weight` when the dictionary has one (normalization.h: load_state_dict); sizes must match
+  void load_weight(const torch::Tensor& weight);
+  void verify_loaded_weights(const std::string& prefix = "") const;
+  const torch::Tensor& weight() const { return weight_; }
+
+ private:
+  torch::Tensor weight_;
+  bool is_loaded_ = false;
+  float eps_;
+};
+
+// The Gemma-2 sandwich (src/models/google/gemma2.h:186-204) in one launch (section 12, form B):
+// y = GN(input, post_weight) (undefined post_weight: y = input); residual = T(y + residual) in place;
+// out = GN(residual, pre_weight) (out and pre_weight both undefined: skipped).
+void gemma_sandwich_norm(torch::Tensor out, const torch::Tensor& input, const torch::Tensor& post_weight,
+                         torch::Tensor residual, const torch::Tensor& pre_weight, float epsilon);
+// out = T(cap * tanh(input / cap)) (gemma2.h:341-342), one pass and one rounding; out may be input
+void soft_cap(torch::Tensor out, const torch::Tensor& input, float cap);
 
 // int4 linear in the library's packed layout.  Built once from CHECKPOINT-format tensors (the
 // same tensors the reference's load_state_dict collects), then forward() = one GEMM launch.

@@ -865,6 +865,101 @@ def gelu_fast_with_mul(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> t
     return _gelu(x, GELU_FAST, True, out)
 
 
+# ---------------------------------------------------------------------------------------
+# Gemma family (slm_hip.h section 12)
+# ---------------------------------------------------------------------------------------
+def _gemma_norm(what: str, dim: int, n_tokens: int, dtype_of: torch.Tensor, eps: float, **ptrs) -> None:
+    g = _lib.GemmaNormArgs()
+    for name, t in ptrs.items():
+        if isinstance(t, torch.Tensor):
+            if not t.is_contiguous():
+                raise SlmError(f"{what} needs contiguous tensors ({name})")
+            setattr(g, name, t.data_ptr())
+        elif t is not None:
+            setattr(g, name, t)
+    g.n_tokens, g.dim, g.dtype, g.eps = n_tokens, dim, _dtype_code(dtype_of), float(eps)
+    check(_lib.lib().slm_gemma_norm(C.byref(g), _stream()), "slm_gemma_norm")
+
+
+def _same_t(what: str, ref: torch.Tensor, **tensors) -> None:
+    for name, t in tensors.items():
+        if t is not None and t.dtype != ref.dtype:
+            raise SlmError(f"{what}: {name} is {t.dtype}, expected {ref.dtype}")
+
+
+def gemma_rms_norm(out: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, eps: float) -> None:
+    """kernel::gemma_rms_norm (layernorm_kernels.cu:66-117): out = T(x * rsqrt(mean(x^2) + eps) * (1 + weight)),
+    fp32 arithmetic and one rounding.  out may be x."""
+    _require_gpu(out, x, weight)
+    dim = x.size(-1)
+    if weight.numel() != dim or out.shape != x.shape:
+        raise SlmError("gemma_rms_norm: weight / out do not match the input")
+    _same_t("gemma_rms_norm", x, out=out, weight=weight)
+    _gemma_norm("gemma_rms_norm", dim, x.numel() // dim, x, eps, out=out, x=x, pre_weight=weight)
+
+
+def gemma_sandwich_norm(out: Optional[torch.Tensor], x: torch.Tensor, post_weight: Optional[torch.Tensor],
+                        residual: torch.Tensor, pre_weight: Optional[torch.Tensor], eps: float,
+                        partials: Optional[DeferredPartials] = None) -> None:
+    """The Gemma-2 sandwich (gemma2.h:186-204) in one launch: y = GN(x, post_weight) (None: y = x),
+    residual = T(y + residual) in place, out = GN(residual, pre_weight) (pre_weight and out both None: skipped).
+
+    partials (truthy): `x` was NOT written -- it only gives the shape; the gptq_gemm(..., defer_reduce=True)
+    that returned the handle left fp32 split-K slabs, which the kernel sums and rounds as rms_norm(partials=...)
+    does (identical bits to the reduced x, one launch less)."""
+    _require_gpu(out, x, post_weight, residual, pre_weight)
+    dim = x.size(-1)
+    if residual.shape != x.shape or (out is not None and out.shape != x.shape):
+        raise SlmError("gemma_sandwich_norm: residual / out do not match the input")
+    if (out is None) != (pre_weight is None):
+        raise SlmError("gemma_sandwich_norm: out and pre_weight go together")
+    for w in (post_weight, pre_weight):
+        if w is not None and w.numel() != dim:
+            raise SlmError("gemma_sandwich_norm: a weight does not match the input's last dimension")
+    _same_t("gemma_sandwich_norm", x, out=out, post_weight=post_weight, residual=residual, pre_weight=pre_weight)
+    kw = dict(out=out, post_weight=post_weight, residual=residual, pre_weight=pre_weight)
+    if partials:
+        if not isinstance(partials, DeferredPartials):
+            raise SlmError("gemma_sandwich_norm(partials=...) takes the handle gptq_gemm(defer_reduce=True) returned")
+        partials.check(x.device, x.numel(), "gemma_sandwich_norm(partials=...)")
+        kw.update(partials=partials.ptr, n_splits=partials.splits)
+    else:
+        kw.update(x=x)
+    _gemma_norm("gemma_sandwich_norm", dim, x.numel() // dim, x, eps, **kw)
+
+
+def gemma_embed_norm(out: torch.Tensor, residual: torch.Tensor, table: torch.Tensor, token_ids: torch.Tensor,
+                     x_scale: float, weight: torch.Tensor, eps: float) -> None:
+    """Embedding, Gemma's scale and the first input norm (gemma2.h:236-238,270) in one launch:
+    residual = T(table[token_ids] * x_scale), out = GN(residual, weight).  x_scale is rounded to the tensors'
+    dtype first, as the reference's T(sqrt(hidden)) is, which makes the product exact before its rounding."""
+    _require_gpu(out, residual, table, token_ids, weight)
+    if table.dim() != 2 or token_ids.dtype != torch.int32 or token_ids.dim() != 1:
+        raise SlmError("gemma_embed_norm takes a [vocab, dim] table and int32 [n_tokens] ids")
+    dim, n = table.size(1), token_ids.numel()
+    if tuple(out.shape) != (n, dim) or tuple(residual.shape) != (n, dim) or weight.numel() != dim:
+        raise SlmError("gemma_embed_norm: out / residual / weight do not match [n_tokens, dim]")
+    _same_t("gemma_embed_norm", table, out=out, residual=residual, weight=weight)
+    scale = torch.tensor(float(x_scale), dtype=table.dtype).float().item()
+    _gemma_norm("gemma_embed_norm", dim, n, table, eps, out=out, residual=residual, table=table,
+                token_ids=token_ids, pre_weight=weight, vocab=table.size(0), x_scale=scale)
+
+
+def soft_cap(x: torch.Tensor, cap: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = T(cap * tanh(x / cap)) (gemma2.h:341-342; one pass and ONE rounding where the reference's three
+    element-wise ops round three times).  out defaults to x: in place."""
+    _require_gpu(x, out)
+    if out is None:
+        out = x
+    if x.dim() < 1 or not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape or \
+            out.dtype != x.dtype:
+        raise SlmError("soft_cap needs contiguous x / out of one shape and dtype")
+    row = x.size(-1)
+    check(_lib.lib().slm_soft_cap(out.data_ptr(), x.data_ptr(), x.numel() // max(row, 1), row, float(cap),
+                                  _dtype_code(x), _stream()), "slm_soft_cap")
+    return out
+
+
 def apply_rotary_pos_emb(query: torch.Tensor, key: torch.Tensor, positions: torch.Tensor,
                          cos_sin: torch.Tensor, rotary_dim: int, interleaved: bool,
                          value: Optional[torch.Tensor] = None,

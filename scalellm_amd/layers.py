@@ -13,6 +13,7 @@ the reference so parity tests read like the reference's own layer tests.
                           qlinear_gptq_marlin_impl.cpp:74-330 (TP sharding dims, lazy repack on
                           first forward, all-reduce then bias for row-parallel)
   LayerNorm            <- llm::LayerNormImpl          src/layers/normalization.h:68-110
+  GemmaRMSNorm         <- llm::GemmaRMSNormImpl       src/layers/normalization.h:142-168
   Activation           <- llm::Activation             src/layers/activation.h:36-46, activation.cpp:80-140
                           (the LayerNorm model families -- GPT-2, BASELINE configs[0] -- next to the
                           RMSNorm / SiLU pair the Llama path uses)
@@ -382,6 +383,38 @@ class LayerNorm:
         out = torch.empty_like(input)
         x2 = input.view(-1, input.size(-1))
         kernels.layer_norm(out.view(-1, input.size(-1)), x2, self.weight, self.bias, self.eps)
+        return out
+
+    __call__ = forward
+
+
+class GemmaRMSNorm:
+    """llm::GemmaRMSNormImpl (normalization.h:142-168): GemmaRMSNormImpl(dim, eps, options); forward =
+    kernel::gemma_rms_norm on the GPU -> slm_gemma_norm, form A.  `weight` is the checkpoint's (the + 1 is
+    applied in the kernel, in fp32)."""
+
+    def __init__(self, dim: int, eps: float, dtype: torch.dtype = torch.bfloat16, device="cuda"):
+        self.eps = float(eps)
+        self.weight = torch.empty(dim, dtype=dtype, device=device)
+        self._loaded = {"weight": False}
+
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor]) -> None:
+        t = state_dict.get("weight")
+        if t is None:
+            return
+        if tuple(t.shape) != tuple(self.weight.shape):
+            raise ValueError(f"weight size mismatch: {tuple(t.shape)} vs {tuple(self.weight.shape)}")
+        self.weight.copy_(t)
+        self._loaded["weight"] = True
+
+    def verify_loaded_weights(self, prefix: str = "") -> None:
+        for name, ok in self._loaded.items():
+            if not ok:
+                raise RuntimeError(f"weight is not loaded for {prefix}{name}")
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:  # noqa: A002 (the reference's argument name)
+        out = torch.empty_like(input)
+        kernels.gemma_rms_norm(out.view(-1, input.size(-1)), input.view(-1, input.size(-1)), self.weight, self.eps)
         return out
 
     __call__ = forward
