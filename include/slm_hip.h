@@ -1119,6 +1119,78 @@ SLM_API int slm_gemma_norm(const slm_gemma_norm_args* a, void* stream);
 SLM_API int slm_soft_cap(void* out, const void* x, int64_t n_rows, int64_t row_len, float cap, int32_t dtype,
                          void* stream);
 
+/* ========================================================================== */
+/* 13. Dense linear: unquantised f16 / bf16 weights in checkpoint layout      */
+/*    replaces  F::linear in {Column,Row}ParallelLinearImpl::forward          */
+/*              src/layers/linear/parallel_linear.cpp (weight [out, in])      */
+/*      C[M, N] = T( A[M, K] . W[N, K]^T + bias[N] )                          */
+/*    fp32 accumulate, ONE rounding to T.  W is the checkpoint tensor [N, K], */
+/*    k-contiguous, row stride ldw >= K, never prepacked; A has row stride    */
+/*    lda, C row stride ldc (elements); every row 16-byte aligned.            */
+/*    Shapes: K % 32 == 0, N % 32 == 0 (N % 64 with SLM_LINEAR_SILU_MUL), any */
+/*    M >= 1, f16 / bf16: anything else SLM_ERR_UNSUPPORTED.  A null pointer  */
+/*    or lda < K, ldw < K, ldc < output width: SLM_ERR_INVALID_ARG; all of it */
+/*    before any launch.  M == 0 is SLM_OK without a launch.                  */
+/*    Launch shape (csrc/dense.hip): one wave owns one 32-column tile over    */
+/*    one K slice and `row_tiles` (1 / 2 / 4) 32-row accumulator tiles;       */
+/*    `waves` (1 / 2 / 4, >= row_tiles) waves of a workgroup sit on adjacent  */
+/*    column tiles and share the activation image in LDS.  Rows beyond        */
+/*    32 * row_tiles go to further row blocks of the grid, which stream the   */
+/*    weights again: correct at every M, tuned for decode (M <= 128) only.    */
+/*    K split: split_k (1..16) contiguous ranges of whole 128-deep chunks of  */
+/*    K, the K % 128 tail with the last; every slice writes an fp32 slab      */
+/*    [M][N], slabs [split_k][M][N] at the START of `workspace`, summed in    */
+/*    slice order by a second launch (+ bias, one rounding) -- or left to the */
+/*    consumer (SLM_LINEAR_DEFER_REDUCE).  No atomics, no cross-workgroup     */
+/*    hand-off.  split_k = the largest value that keeps row_blocks *          */
+/*    col_groups * split_k <= 256 (the CUs) with >= 4 chunks per slice.       */
+/*    Knobs: SLM_LINEAR_SPLITK, SLM_LINEAR_RT, SLM_LINEAR_NW (section 0).     */
+/* ========================================================================== */
+typedef struct slm_linear_args {
+  const void* a;        /* [M, K] T, row stride lda                           */
+  const void* w;        /* [N, K] T, row stride ldw                           */
+  const void* bias;     /* [N] T or NULL                                      */
+  void* c;              /* [M, N] T ([M, N/2] with SLM_LINEAR_SILU_MUL), row stride ldc */
+  int64_t M, K, N;
+  int64_t lda, ldw, ldc;
+  int32_t dtype;
+  int32_t flags;        /* SLM_LINEAR_* bits, 0 = none                        */
+  void* workspace;      /* split-K slabs                                      */
+  size_t workspace_bytes;
+} slm_linear_args;
+
+/* flags: as SLM_W4_DEFER_REDUCE -- a split call leaves its fp32 slabs at the start of `workspace`
+ * and does NOT write c; ignored (normal reduce) when bias != NULL.  Ask slm_linear_deferred_splits. */
+#define SLM_LINEAR_DEFER_REDUCE 1
+/* flags: rows [0, N/2) of W are the gate, [N/2, N) the up projection and c is [M, N/2]:
+ *   c[m, i] = T( silu(g) * u ),  g = T(acc[m, i] + bias[i]),  u = T(acc[m, N/2 + i] + bias[N/2 + i])
+ * -- the bits of slm_linear into [M, N] followed by slm_silu_mul.  N % 64 == 0; never split over K;
+ * cannot be combined with SLM_LINEAR_DEFER_REDUCE (SLM_ERR_INVALID_ARG). */
+#define SLM_LINEAR_SILU_MUL 2
+/* flags: scheduling hint as SLM_W4_SHARES_CHIP; accepted, the plan does not depend on it today. */
+#define SLM_LINEAR_SHARES_CHIP 4
+
+typedef struct slm_linear_plan_info {
+  int32_t row_tiles;        /* 32-row accumulator tiles per wave: 1 / 2 / 4                         */
+  int32_t waves;            /* waves (adjacent column tiles) per workgroup: 1 / 2 / 4               */
+  int32_t row_blocks;       /* ceil(M / (32 * row_tiles))                                           */
+  int32_t col_groups;       /* workgroups per row block and K slice                                 */
+  int32_t split_k;          /* K slices, 1..16                                                      */
+  int32_t n_chunks;         /* K / 128                                                              */
+  int32_t tail_units;       /* (K % 128) / 32: consumed by the LAST slice                           */
+  int32_t slice_chunk[17];  /* slice j covers chunks [slice_chunk[j], slice_chunk[j + 1])           */
+  uint64_t lds_bytes;       /* static LDS of the launch                                             */
+  uint64_t workspace_bytes; /* split_k * M * N * 4 when split_k > 1, else 0                         */
+} slm_linear_plan_info;
+
+/* The launch slm_linear gives `a`: a pure function of (M, N, K, dtype, flags, bias != NULL, tuning table);
+ * no HIP call, works without a GPU.  The two queries below read from the same plan. */
+SLM_API int slm_linear_plan(const slm_linear_args* a, slm_linear_plan_info* out);
+SLM_API size_t slm_linear_workspace_bytes(const slm_linear_args* a);
+/* number of slabs the call will leave in the workspace (>= 2), or 0 when it writes c as usual */
+SLM_API int32_t slm_linear_deferred_splits(const slm_linear_args* a);
+SLM_API int slm_linear(const slm_linear_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

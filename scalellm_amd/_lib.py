@@ -203,6 +203,36 @@ class GemmaNormArgs(C.Structure):
     ]
 
 
+class LinearArgs(C.Structure):
+    """struct slm_linear_args (include/slm_hip.h section 13)."""
+    _fields_ = [
+        ("a", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("c", C.c_void_p),
+        ("M", C.c_int64), ("K", C.c_int64), ("N", C.c_int64),
+        ("lda", C.c_int64), ("ldw", C.c_int64), ("ldc", C.c_int64),
+        ("dtype", C.c_int32), ("flags", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class LinearPlanInfo(C.Structure):
+    """struct slm_linear_plan_info (include/slm_hip.h section 13)."""
+    _fields_ = [
+        ("row_tiles", C.c_int32), ("waves", C.c_int32), ("row_blocks", C.c_int32), ("col_groups", C.c_int32),
+        ("split_k", C.c_int32), ("n_chunks", C.c_int32), ("tail_units", C.c_int32),
+        ("slice_chunk", C.c_int32 * 17),
+        ("lds_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64),
+    ]
+
+    def slice_k_range(self, j: int):
+        """[k0, k1) of K slice j: whole 128-deep chunks, the K % 128 tail with the last slice."""
+        k0, k1 = 128 * self.slice_chunk[j], 128 * self.slice_chunk[j + 1]
+        return k0, k1 + (32 * self.tail_units if j == self.split_k - 1 else 0)
+
+
+SLM_LINEAR_DEFER_REDUCE = 1
+SLM_LINEAR_SILU_MUL = 2
+SLM_LINEAR_SHARES_CHIP = 4
+
 SLM_MOE_SILU_MUL = 2    # slm_moe_gemm flags
 SLM_MOE_GEMM_BLOCK = 32  # rows per block of the grouped GEMM: the align step's block_size
 
@@ -335,6 +365,10 @@ def lib() -> C.CDLL:
          [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
           C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
         ("slm_gemma_norm", C.c_int, [C.POINTER(GemmaNormArgs), C.c_void_p]),
+        ("slm_linear", C.c_int, [C.POINTER(LinearArgs), C.c_void_p]),
+        ("slm_linear_workspace_bytes", C.c_size_t, [C.POINTER(LinearArgs)]),
+        ("slm_linear_deferred_splits", C.c_int32, [C.POINTER(LinearArgs)]),
+        ("slm_linear_plan", C.c_int, [C.POINTER(LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_soft_cap", C.c_int,
          [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
     ]:

@@ -64,6 +64,8 @@ def from_decode_step(step, block_size: int, max_tokens: int, fused: bool = True,
     from .decode import hf_state_dict
     shim = load_shim()
     s = step.shape
+    if getattr(step, "dense", False):
+        raise ValueError("the C++ host step is built for int4 checkpoints: it has no unquantised form")
     qa = step.layers[0]["qkv"].quant_args
     if qa.bits != 4 or qa.desc_act:
         raise ValueError("the C++ host step is built for 4-bit, non-act-order checkpoints")

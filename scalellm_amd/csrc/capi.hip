@@ -22,6 +22,7 @@ const char* const kTuneNames[TUNE_COUNT] = {
     "SLM_W4_M128",          "SLM_W4_M128_WD",       "SLM_W4_M128_SPLITS",   "SLM_W4_M128_KW",   "SLM_W4_SPLIT_TARGET",
     "SLM_W4_M128_CT",       "SLM_ATTN_TILE_KV2",    "SLM_W4_XL_MODEL",      "SLM_W4_M128_ADMA",
     "SLM_W4_XL_SK",
+    "SLM_LINEAR_SPLITK",    "SLM_LINEAR_RT",        "SLM_LINEAR_NW",
 };
 std::atomic<int32_t> g_tune[TUNE_COUNT];
 std::once_flag g_tune_once;

@@ -11,6 +11,7 @@
 #include "slm_llama_hip.h"
 #include "slm_mla_hip.h"
 #include "slm_moe_hip.h"
+#include "slm_linear_hip.h"
 #include "slm_qlinear_hip.h"
 #include "slm_rejection_sampler_hip.h"
 #include "slm_sampling_hip.h"
@@ -135,6 +136,36 @@ PYBIND11_MODULE(_slm_shim, m) {
               in_features, out_features, bias, input_is_parallelized,
               make_args(quant_method, bits, group_size, desc_act, is_sym, zero_point),
               slm::ParallelArgs(rank, world_size, nullptr),
+              torch::dtype(dtype).device(torch::Device(torch::kCUDA, device_index)));
+        });
+  // the unquantised layers through THEIR factory (parallel_linear.cpp:167-217): an empty quant_method gives the
+  // dense HIP impls, anything else goes to the int4 factories above; act_mul_silu: the merged gate | up
+  // projection with the SiLU * mul epilogue (dense only)
+  m.def("create_column_parallel_linear",
+        [make_args](int64_t in_features, int64_t out_features, bool bias, bool gather_output,
+                    const std::string& quant_method, int rank, int world_size, torch::ScalarType dtype,
+                    int device_index, bool act_mul_silu) {
+          auto l = slm::create_column_parallel_linear(
+              in_features, out_features, bias, gather_output, make_args(quant_method, 4, 128, false, false, true),
+              slm::ParallelArgs(rank, world_size, nullptr),
+              torch::dtype(dtype).device(torch::Device(torch::kCUDA, device_index)));
+          if (act_mul_silu) {
+            auto* d = dynamic_cast<slm::LinearHipBase*>(l.get());
+            TORCH_CHECK(d != nullptr, "act_mul_silu: dense layers only");
+            d->set_act_mul_silu();
+          }
+          return l;
+        },
+        py::arg("in_features"), py::arg("out_features"), py::arg("bias"), py::arg("gather_output"),
+        py::arg("quant_method"), py::arg("rank"), py::arg("world_size"), py::arg("dtype"), py::arg("device_index"),
+        py::arg("act_mul_silu") = false);
+  m.def("create_row_parallel_linear",
+        [make_args](int64_t in_features, int64_t out_features, bool bias, bool input_is_parallelized,
+                    const std::string& quant_method, int rank, int world_size, torch::ScalarType dtype,
+                    int device_index) {
+          return slm::create_row_parallel_linear(
+              in_features, out_features, bias, input_is_parallelized,
+              make_args(quant_method, 4, 128, false, false, true), slm::ParallelArgs(rank, world_size, nullptr),
               torch::dtype(dtype).device(torch::Device(torch::kCUDA, device_index)));
         });
   // the attention layer boundary: KVCache / InputParameters / AttentionHandler / AttentionImpl

@@ -210,6 +210,12 @@ class W4Linear {
   torch::ScalarType dtype_;
 };
 
+// F::linear on unquantised f16 / bf16 weights (include/slm_hip.h section 13, slm_linear): input [.., K],
+// weight [N, K] in checkpoint layout (rows contiguous), optional bias [N] -> [M, N]; silu_mul: weight rows are
+// gate | up and the result is [M, N / 2] = silu(gate) * up.  Split-K scratch: the shim's growable buffer.
+torch::Tensor linear(const torch::Tensor& input, const torch::Tensor& weight, const std::optional<torch::Tensor>& bias,
+                     bool silu_mul = false);
+
 // The reference's abstract process group, same five virtuals with the same meaning
 // (src/model_parallel/process_group.h:10-60): whatever drives llm::ProcessGroup* -- the parallel
 // layers, Worker::process_group_test -- drives this.

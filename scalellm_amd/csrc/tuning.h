@@ -47,6 +47,9 @@ enum TuneKey : int {
   TUNE_W4_XL_MODEL,       // SLM_W4_XL_MODEL       0 = the 256 x 256 kernel only where its tiles fill whole rounds (no round-count comparison with 256 x 128 tiles)
   TUNE_W4_M128_ADMA,      // SLM_W4_M128_ADMA      activations of the 256-column form by LDS-DMA (1) or through registers (0)
   TUNE_W4_XL_SK,          // SLM_W4_XL_SK          stream-K form of the 256 x 256 kernel: 0 never, 2 wherever it applies (default 1: where the round model says it wins)
+  TUNE_LINEAR_SPLITK,     // SLM_LINEAR_SPLITK     forced K slices of the dense linear (1..16; every slice keeps >= 1 chunk)
+  TUNE_LINEAR_RT,         // SLM_LINEAR_RT         forced 32-row accumulator tiles per wave of the dense linear (1/2/4)
+  TUNE_LINEAR_NW,         // SLM_LINEAR_NW         forced waves per workgroup of the dense linear (1/2/4; raised to the row tiles)
   TUNE_COUNT
 };
 

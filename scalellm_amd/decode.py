@@ -5,7 +5,9 @@ drive the hot path the way the reference's LlamaModelImpl::forward does (src/mod
 all-reduce) -> RMSNorm -> gate_up -> SiLU*mul -> down (row-parallel, all-reduce); then final norm,
 lm_head (column-parallel, gathered) and greedy argmax.  All four linears are int4 (AWQ or GPTQ)
 -- the reference snapshot leaves fused qkv / gate_up un-quantised; here the whole
-layer is int4.  Weights are synthetic (seeded); there is no checkpoint IO on this path.
+layer is int4 -- or, with quant_method="none", all four are unquantised f16 / bf16 weights in
+checkpoint layout (layers.ColumnParallelLinear / RowParallelLinear over slm_linear).  Weights are
+synthetic (seeded); there is no checkpoint IO on this path.
 
 One process per GPU; TP shards heads (attention needs no collective) and the GEMMs' N / K.
 The step is hipGraph-capturable: static buffers, no host sync, no allocation after warm-up.
@@ -22,8 +24,8 @@ from typing import List, Optional
 import torch
 
 from . import kernels
-from .layers import (Attention, ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache, uniform_kv_hint,
-                     QuantArgs, RowParallelQLinear)
+from .layers import (Attention, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache,
+                     uniform_kv_hint, QuantArgs, RowParallelLinear, RowParallelQLinear)
 from .model_parallel import ParallelArgs
 
 
@@ -112,25 +114,27 @@ def _shard_rows(ck, fmt, k0, k1, group_size, bits=4):
 
 
 def lane_query(shape: "LlamaShape", n_heads: int, n_kv_heads: int, world_size: int, lanes_min: int,
-               n_tokens: int, n_seqs: int, q_max_seq_len: int, kv_max_seq_len: int, tp_lanes_ok: bool = False):
-    """slm_lane_query for a step of this shape (n_heads / n_kv_heads: per rank)."""
+               n_tokens: int, n_seqs: int, q_max_seq_len: int, kv_max_seq_len: int, tp_lanes_ok: bool = False,
+               weight_bits: int = 4):
+    """slm_lane_query for a step of this shape (n_heads / n_kv_heads: per rank; weight_bits: 4 for the int4
+    linears, 16 for a dense step)."""
     from ._lib import LaneQuery
     q = LaneQuery()
     q.n_tokens, q.n_seqs, q.q_max_seq_len, q.kv_max_seq_len = int(n_tokens), int(n_seqs), int(q_max_seq_len), \
         int(min(kv_max_seq_len, 2 ** 31 - 1))
     q.world_size, q.tp_lanes_ok, q.lanes_min = int(world_size), int(bool(tp_lanes_ok)), int(lanes_min)
     q.n_heads, q.n_kv_heads, q.head_dim = int(n_heads), int(n_kv_heads), int(shape.head_dim)
-    # packed int4 bytes of one decoder layer on this rank: qkv + o + gate_up + down
+    # weight bytes of one decoder layer on this rank (packed int4, or 2 bytes per dense weight): qkv + o + gate_up + down
     q.layer_weight_bytes = (shape.hidden * (n_heads + 2 * n_kv_heads) * shape.head_dim +
                             n_heads * shape.head_dim * shape.hidden +
-                            3 * shape.hidden * shape.intermediate // world_size) // 2
+                            3 * shape.hidden * shape.intermediate // world_size) * weight_bits // 8
     q.kv_elem_bytes = 2
     return q
 
 
 def two_lane_split(shape: "LlamaShape", n_heads: int, n_kv_heads: int, world_size: int, lanes_min: int,
                    n_tokens: int, n_seqs: int, q_max_seq_len: int, kv_max_seq_len: int,
-                   tp_lanes_ok: bool = False) -> int:
+                   tp_lanes_ok: bool = False, weight_bits: int = 4) -> int:
     """Rows of lane 0 when a step runs as two half-batch lanes (LlamaDecodeStep._run_two_lanes), else 0.
     Pure host logic on the step's hints; THE rule lives in the C ABI (slm_decode_lane_split,
     include/slm_hip.h section 7, csrc/capi.hip) so that this mirror and the C++ host step
@@ -157,7 +161,7 @@ def two_lane_split(shape: "LlamaShape", n_heads: int, n_kv_heads: int, world_siz
     """
     from . import _lib
     q = lane_query(shape, n_heads, n_kv_heads, world_size, lanes_min, n_tokens, n_seqs, q_max_seq_len,
-                   kv_max_seq_len, tp_lanes_ok)
+                   kv_max_seq_len, tp_lanes_ok, weight_bits)
     return int(_lib.lib().slm_decode_lane_split(q))
 
 
@@ -168,6 +172,10 @@ class LlamaDecodeStep:
                  kv_fill: str = "none", custom_allreduce=None, keep_checkpoint: bool = False,
                  gptq_sym: bool = False, fuse_silu: bool = True, desc_act: bool = False, bits: int = 4):
         pa = parallel_args or ParallelArgs()
+        # quant_method "none": unquantised weights [N, K] of `dtype` (randn * 0.02 from the common seed), the four
+        # linears are layers.{Column,Row}ParallelLinear over slm_linear; everything else of the step is shared
+        dense = quant_method == "none"
+        self.dense, self.weight_bits = dense, 16 if dense else 4
         # fuse_silu: the merged gate_up weight is packed paired and SiLU*mul runs in the GEMM
         # epilogue (identical bits; False keeps the separate kernels.silu_and_mul launch)
         fuse_silu = fuse_silu and (shape.intermediate // pa.world_size) % 32 == 0
@@ -189,13 +197,15 @@ class LlamaDecodeStep:
         # <= 4 tokens on one rank: the RMSNorm before the qkv / gate_up projections runs in the
         # GEMV's prologue (kernels.NormPrologue) -- two launches less per layer where the step is
         # launch-bound.  Identical bits either way.
-        self.fold_norm = os.environ.get("SLM_FOLD_NORM", "1") != "0"
+        # (never for dense weights: there is no norm-prologue GEMV over them)
+        self.fold_norm = os.environ.get("SLM_FOLD_NORM", "1") != "0" and not dense
         # two half-batch lanes on two streams for pure-decode batches of >= lanes_min tokens (0 = never);
         # lanes_chain: the lanes' attention launches are serialised by events (see _run_two_lanes)
         # SLM_DECODE_LANES: "auto" (default: the batch sizes where it was measured to pay, _lane_split),
         # 0 = never, N = every pure-decode batch of >= N tokens (tests, sweeps)
         _lm = os.environ.get("SLM_DECODE_LANES", "auto")
-        self.lanes_min = -1 if _lm == "auto" else int(_lm)
+        # (auto on a dense step: one lane -- the two-lane constants were measured for int4 weights only)
+        self.lanes_min = (0 if dense else -1) if _lm == "auto" else int(_lm)
         self.lanes_chain = os.environ.get("SLM_DECODE_LANES_CHAIN", "1") != "0"
         self._side_stream = None
         self._lane_bufs = {}
@@ -227,6 +237,13 @@ class LlamaDecodeStep:
         self.layers = []
         for _ in range(shape.n_layers):
             L = {}
+            if dense:
+                self._build_dense_linears(L, gen, keep_checkpoint, fuse_silu)
+                L["in_norm"] = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
+                L["post_norm"] = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
+                L["kv"] = KVCache(n_blocks, block_size, self.n_kv_heads, D, dtype, self.device)
+                self.layers.append(L)
+                continue
             L["qkv"] = ColumnParallelQLinear(H, qkv_n * tp, False, qa, False, pa, dtype, self.device)
             L["o"] = RowParallelQLinear(q_full, H, False, qa, True, pa, dtype, self.device)
             L["gate_up"] = ColumnParallelQLinear(H, 2 * inter, False, qa, False, pa, dtype, self.device,
@@ -278,6 +295,38 @@ class LlamaDecodeStep:
         if kv_fill != "none":
             self.fill_kv(kv_fill, gen)
 
+    def _build_dense_linears(self, L: dict, gen, keep_checkpoint: bool, fuse_silu: bool) -> None:
+        """The four unquantised linears of one layer: every rank draws the SAME full weights [N, K] and keeps its
+        tensor-parallel shard -- rows (dim 0) for the column-parallel qkv / gate_up, columns (dim 1) for o / down."""
+        s, pa, dtype, dev = self.shape, self.pa, self.dtype, self.device
+        tp, r, nh, nkv, D, H = pa.world_size, pa.rank, self.n_heads, self.n_kv_heads, s.head_dim, s.hidden
+        kv_head0 = (r * s.n_kv_heads) // tp
+        q_full, kv_full, inter = s.n_heads * D, s.n_kv_heads * D, s.intermediate
+        qkv_n = (nh + 2 * nkv) * D
+
+        def draw(n, k):
+            return (torch.randn(n, k, device=dev, generator=gen) * 0.02).to(dtype)
+
+        def rows(w, ranges):
+            return torch.cat([w[a:b] for a, b in ranges], dim=0).contiguous()
+        L["qkv"] = ColumnParallelLinear(H, qkv_n * tp, False, False, pa, dtype, dev)
+        L["o"] = RowParallelLinear(q_full, H, False, True, pa, dtype, dev)
+        L["gate_up"] = ColumnParallelLinear(H, 2 * inter, False, False, pa, dtype, dev,
+                                            act_mul="silu" if fuse_silu else None)
+        L["down"] = RowParallelLinear(inter, H, False, True, pa, dtype, dev)
+        shard = {"qkv": rows(draw(q_full + 2 * kv_full, H), [
+            (r * nh * D, (r + 1) * nh * D), (q_full + kv_head0 * D, q_full + (kv_head0 + nkv) * D),
+            (q_full + kv_full + kv_head0 * D, q_full + kv_full + (kv_head0 + nkv) * D)])}
+        shard["o"] = draw(H, q_full)[:, r * nh * D:(r + 1) * nh * D].contiguous()
+        shard["gate_up"] = rows(draw(2 * inter, H), [(r * inter // tp, (r + 1) * inter // tp),
+                                                     (inter + r * inter // tp, inter + (r + 1) * inter // tp)])
+        shard["down"] = draw(H, inter)[:, r * inter // tp:(r + 1) * inter // tp].contiguous()
+        if keep_checkpoint:
+            self.ckpt.append({n: {"weight": w.clone()} for n, w in shard.items()})
+        for name, w in shard.items():
+            L[name].load_shard(w)
+            L[name].verify_loaded_weights()
+
     def fill_kv(self, mode: str, gen) -> None:
         """Synthetic KV history.  'randn': every layer its own normal draw (slow for 100+ GiB);
         'tile': one 256 MiB normal block tiled over every layer's cache (fast; random enough for
@@ -321,7 +370,7 @@ class LlamaDecodeStep:
         if self.lanes_min != 0 and self._tp_lanes_ok():
             h0 = two_lane_split(s, self.n_heads, self.n_kv_heads, self.pa.world_size,
                                 self.lanes_min if self.lanes_min > 0 else 1, n_tokens, n_tokens, 1, 1 << 30,
-                                tp_lanes_ok=True)
+                                tp_lanes_ok=True, weight_bits=self.weight_bits)
         # (lane 1 of ANY batch of T <= n_tokens rows: T - h0(T) <= T / 2 -- not n_tokens - h0(n_tokens): reserve(200)
         # splits 128 / 72, a later 192-row step 96 / 96)
         for lane, rows in ((0, n_tokens), (1, (n_tokens + 1) // 2)) if 0 < h0 < n_tokens else ((0, n_tokens),):
@@ -363,7 +412,7 @@ class LlamaDecodeStep:
             lanes_min = 0 if self._pinned_lanes == 1 else 1
         return two_lane_split(self.shape, self.n_heads, self.n_kv_heads, self.pa.world_size, lanes_min, T,
                               params.q_cu_seq_lens.numel() - 1, params.q_max_seq_len, params.kv_max_seq_len,
-                              tp_lanes_ok=True)
+                              tp_lanes_ok=True, weight_bits=self.weight_bits)
 
     # ---- graph variants (ModelRunner, round 5; round-4 advisor finding) -------------------------------
     # A captured graph freezes every host-side decision of the step at the CAPTURE-time hints
@@ -377,7 +426,7 @@ class LlamaDecodeStep:
         lanes = [1]
         if self.lanes_min != 0 and self._tp_lanes_ok() and two_lane_split(
                 self.shape, self.n_heads, self.n_kv_heads, self.pa.world_size, 1, n_tokens, n_seqs,
-                q_max_seq_len, 1 << 30, tp_lanes_ok=True) > 0:
+                q_max_seq_len, 1 << 30, tp_lanes_ok=True, weight_bits=self.weight_bits) > 0:
             lanes.append(2)
         uniform = (False, True) if q_max_seq_len == 1 and n_tokens == n_seqs else (False,)
         return [(ln, u) for ln in lanes for u in uniform]
@@ -406,7 +455,7 @@ class LlamaDecodeStep:
         from . import _lib
         ar = self.custom_ar if self.pa.world_size > 1 else None
         q = lane_query(self.shape, self.n_heads, self.n_kv_heads, self.pa.world_size, 1, n_tokens, n_tokens, 1,
-                       kv_len, self._tp_lanes_ok())
+                       kv_len, self._tp_lanes_ok(), self.weight_bits)
         if ar is not None or not self._tp_lanes_ok() or int(_lib.lib().slm_decode_lane_split(q)) <= 0:
             return None   # (with the fused all-reduce the probe would need every rank in lock step: not here)
         B = self.block_size
@@ -842,6 +891,20 @@ def hf_state_dict(step: "LlamaDecodeStep") -> dict:
     sd = {"model.embed_tokens.weight": step.embed, "model.norm.weight": step.final_norm,
           "lm_head.weight": step.lm_head.t()}   # [vocab, hidden] in a checkpoint
 
+    if step.dense:   # plain *.weight tensors [out, in]: q | k | v and gate | up are row ranges of the fused shards
+        for i, ck in enumerate(step.ckpt):
+            pre = f"model.layers.{i}."
+            qkv, gu = ck["qkv"]["weight"], ck["gate_up"]["weight"]
+            sd[pre + "self_attn.q_proj.weight"] = qkv[:nq].contiguous()
+            sd[pre + "self_attn.k_proj.weight"] = qkv[nq:nq + nkv].contiguous()
+            sd[pre + "self_attn.v_proj.weight"] = qkv[nq + nkv:nq + 2 * nkv].contiguous()
+            sd[pre + "self_attn.o_proj.weight"] = ck["o"]["weight"]
+            sd[pre + "mlp.gate_proj.weight"] = gu[:inter].contiguous()
+            sd[pre + "mlp.up_proj.weight"] = gu[inter:].contiguous()
+            sd[pre + "mlp.down_proj.weight"] = ck["down"]["weight"]
+            sd[pre + "input_layernorm.weight"] = step.layers[i]["in_norm"]
+            sd[pre + "post_attention_layernorm.weight"] = step.layers[i]["post_norm"]
+        return sd
     awq = step.layers[0]["qkv"].quant_args.quant_method == "awq"   # AWQ [K, N/8] / GPTQ [K/8, N]
 
     def cols(ck, a, b):

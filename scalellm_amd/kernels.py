@@ -776,6 +776,81 @@ def w4_dequant(packed: PackedW4) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------
+# dense (unquantised) linear: slm_hip.h section 13
+# ---------------------------------------------------------------------------------------
+def _linear_args(a, weight, c, bias, defer_reduce: bool, silu_mul: bool) -> "_lib.LinearArgs":
+    _require_gpu(a, weight, c, bias)
+    if silu_mul and defer_reduce:
+        raise SlmError("silu_mul and defer_reduce cannot be combined")
+    if a.dim() != 2 or c.dim() != 2 or weight.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1 or \
+            weight.stride(1) != 1:
+        raise SlmError("A [M, K], W [N, K] and C [M, N] must be 2-D with contiguous rows")
+    N, K = weight.shape
+    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a.size(0) != c.size(0):
+        raise SlmError("linear shape mismatch")
+    if a.dtype != weight.dtype or c.dtype != weight.dtype or (bias is not None and bias.dtype != weight.dtype):
+        raise SlmError("activation / weight / bias / output dtypes must match")
+    if bias is not None and (bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous()):
+        raise SlmError("bias must be a contiguous [N] tensor")
+    g = _lib.LinearArgs()
+    g.a, g.w, g.c = a.data_ptr(), weight.data_ptr(), c.data_ptr()
+    g.bias = bias.data_ptr() if bias is not None else None
+    g.M, g.K, g.N = a.size(0), K, N
+    g.lda, g.ldw, g.ldc = a.stride(0), weight.stride(0), c.stride(0)
+    g.dtype = _dtype_code(a)
+    g.flags = _lib.SLM_LINEAR_SHARES_CHIP if _chip_flag() else 0
+    if silu_mul:
+        g.flags |= _lib.SLM_LINEAR_SILU_MUL
+    if defer_reduce:
+        g.flags |= _lib.SLM_LINEAR_DEFER_REDUCE
+    g.workspace, g.workspace_bytes = None, 0
+    return g
+
+
+def linear_plan(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                defer_reduce: bool = False, silu_mul: bool = False) -> "_lib.LinearPlanInfo":
+    """The launch linear() would give these very arguments now, under the tuning knobs in force
+    (slm_linear_plan): row tiles, waves, grid, K slices.  A host-side query: nothing runs on the GPU."""
+    g = _linear_args(a, weight, c, bias, defer_reduce, silu_mul)
+    info = _lib.LinearPlanInfo()
+    check(_lib.lib().slm_linear_plan(C.byref(g), C.byref(info)), "slm_linear_plan")
+    return info
+
+
+def linear(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Optional[torch.Tensor] = None,
+           defer_reduce: bool = False, silu_mul: bool = False) -> DeferredPartials:
+    """F::linear on unquantised weights (parallel_linear.cpp): C[M, N] = A[M, K] . W[N, K]^T (+ bias), fp32
+    accumulate, one rounding, written into the pre-allocated `c`.  `weight` is the checkpoint tensor
+    [N, K] (rows contiguous, any row stride): it is streamed as it is, never repacked.
+
+    defer_reduce / the returned handle: as gptq_gemm -- a call that is split over K leaves its fp32 slabs
+    in the deferred buffer for rms_norm / apply_rotary_pos_emb / gemma_sandwich_norm(partials=handle) and
+    does NOT write `c` (truthy handle); otherwise `c` is written and the handle is falsy.
+
+    silu_mul: rows [0, N/2) of `weight` are the gate, [N/2, N) the up projection and `c` is [M, N/2] =
+    silu(gate) * up -- the bits of linear() followed by silu_and_mul()."""
+    L = _lib.lib()
+    g = _linear_args(a, weight, c, bias, defer_reduce, silu_mul)
+    if g.M == 0:
+        return DeferredPartials()
+    deferred = L.slm_linear_deferred_splits(C.byref(g)) if defer_reduce else 0
+    need = L.slm_linear_workspace_bytes(C.byref(g))
+    ws = None
+    if need:
+        # deferred slabs live in their own buffer (gptq_gemm: nothing else's scratch may overwrite them)
+        ws = _grow(_deferred_ws, need, a.device, "deferred split-K buffer") if deferred \
+            else reserve_workspace(need, a.device)
+        g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(L.slm_linear(C.byref(g), _stream()), "slm_linear")
+    if deferred:
+        key = _dev_key(a.device)
+        gen = _deferred_gen.get((key, 0), 0) + 1
+        _deferred_gen[(key, 0)] = gen  # any older handle on this buffer is now stale
+        return DeferredPartials(g.workspace, deferred, g.M * g.N, key, gen, ws, 0)
+    return DeferredPartials()
+
+
+# ---------------------------------------------------------------------------------------
 # glue ops (next rows f1/f2)
 # ---------------------------------------------------------------------------------------
 def rms_norm(out: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, eps: float,

@@ -12,6 +12,9 @@ the reference so parity tests read like the reference's own layer tests.
                           src/layers/quantization/qlinear_awq_marlin_impl.cpp:128-366,
                           qlinear_gptq_marlin_impl.cpp:74-330 (TP sharding dims, lazy repack on
                           first forward, all-reduce then bias for row-parallel)
+  ColumnParallelLinear / RowParallelLinear
+                       <- {Column,Row}ParallelLinearImpl  src/layers/linear/parallel_linear.cpp:221-308
+                          (unquantised f16 / bf16 weights [out, in] in checkpoint layout -> slm_linear)
   LayerNorm            <- llm::LayerNormImpl          src/layers/normalization.h:68-110
   GemmaRMSNorm         <- llm::GemmaRMSNormImpl       src/layers/normalization.h:142-168
   Activation           <- llm::Activation             src/layers/activation.h:36-46, activation.cpp:80-140
@@ -350,6 +353,186 @@ class RowParallelQLinear(_QLinearBase):
             return y
         return self._gemm(x, self.bias if self.has_bias else None, out,
                           defer_splitk=defer_splitk and not self.has_bias)
+
+
+# ---------------------------------------------------------------------------------------
+# unquantised f16 / bf16 linear layers
+# ---------------------------------------------------------------------------------------
+class _LinearBase:
+    """What {Column,Row}ParallelLinearImpl share (parallel_linear.cpp:221-308): `weight` is this rank's
+    shard of the checkpoint tensor [out, in], kept in checkpoint layout and streamed as it is by
+    kernels.linear (slm_linear) -- nothing is repacked.  load_state_dict takes FULL checkpoint tensors
+    and keeps this rank's chunk (StateDict::get_sharded_tensor, weight_utils.h:60-66); tensors that a
+    dict does not hold are skipped (a checkpoint is spread over files and every file is offered to
+    every layer), a tensor that arrives twice is refused."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool, parallel_args: ParallelArgs,
+                 dtype: torch.dtype, device):
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise kernels.SlmError(f"unsupported dtype {dtype}: fp16 / bf16 only")
+        self.in_features, self.out_features = in_features, out_features
+        self.parallel_args, self.dtype, self.device = parallel_args, dtype, device
+        self.has_bias = bias
+        self.weight: Optional[torch.Tensor] = None
+        self.bias: Optional[torch.Tensor] = None
+        self._parts: Dict[str, list] = {}
+        self.paired = False  # merged [gate | up] weight with the fused SiLU*mul epilogue
+        self.deferred, self.deferred_splits = kernels.DeferredPartials(), 0
+
+    def _shard(self, t: torch.Tensor, dim: int, what: str) -> torch.Tensor:
+        pa = self.parallel_args
+        if dim < 0 or pa.world_size <= 1:
+            return t
+        if t.size(dim) % pa.world_size:
+            raise ValueError(f"can't divide {what} evenly on dim {dim} with world_size {pa.world_size}")
+        return t.chunk(pa.world_size, dim)[pa.rank]
+
+    def _set(self, name: str, t: torch.Tensor) -> None:
+        want = (self.local_out, self.local_in) if name == "weight" else (self.local_out,)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{name} size mismatch: {tuple(t.shape)} vs {want}")
+        setattr(self, name, t.to(device=self.device, dtype=self.dtype).contiguous())
+
+    def _load_one(self, sd: Dict[str, torch.Tensor], name: str, dim: int) -> None:
+        if name not in sd:
+            return
+        if getattr(self, name) is not None:
+            raise RuntimeError(f"{name} is loaded twice")
+        self._set(name, self._shard(sd[name], dim, name))
+
+    def _load_fused(self, sd: Dict[str, torch.Tensor], prefixes, name: str) -> None:
+        """WeightUtils::load_fused_weight (weight_utils.h:48-58): one shard per prefix, kept until all
+        prefixes have arrived, then concatenated on dim 0 (q | k | v, gate | up)."""
+        parts = self._parts.setdefault(name, [None] * len(prefixes))
+        for i, p in enumerate(prefixes):
+            if p + name not in sd:
+                continue
+            if parts[i] is not None or getattr(self, name) is not None:
+                raise RuntimeError(f"{p + name} is loaded twice")
+            parts[i] = self._shard(sd[p + name], 0, p + name).to(self.device)
+        if all(t is not None for t in parts):
+            self._set(name, torch.cat(parts, dim=0))
+            del self._parts[name]
+
+    def load_shard(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> None:
+        """THIS rank's shard, already cut (decode.LlamaDecodeStep shards its synthetic checkpoint itself:
+        replicated KV heads are no equal chunks)."""
+        for name, t in (("weight", weight), ("bias", bias)):
+            if t is None:
+                continue
+            if getattr(self, name) is not None:
+                raise RuntimeError(f"{name} is loaded twice")
+            self._set(name, t)
+
+    def verify_loaded_weights(self, prefix: str = "") -> None:
+        if self.weight is None:
+            raise RuntimeError(f"weight is not loaded for {prefix}weight")
+        if self.has_bias and self.bias is None:
+            raise RuntimeError(f"bias is not loaded for {prefix}bias")
+
+    def _repack(self) -> None:
+        """Nothing to do: the checkpoint layout IS the kernel's (kept for the call surface of the Q classes)."""
+
+    def norm_supported(self, n_tokens: int, defer_splitk: bool = False) -> bool:
+        return False  # no norm-prologue GEMV over dense weights
+
+    def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor],
+                defer_splitk: bool = False) -> torch.Tensor:
+        self.verify_loaded_weights()
+        x2 = x.reshape(-1, x.size(-1))
+        n_out = self.local_out // 2 if self.paired else self.local_out
+        if out is None:
+            out = torch.empty(x2.size(0), n_out, dtype=x.dtype, device=x.device)
+        # truthy: `out` was NOT written, fp32 split-K slabs wait in the deferred buffer for the consumer
+        self.deferred = kernels.linear(x2, self.weight, out, bias, defer_reduce=defer_splitk and not self.paired,
+                                       silu_mul=self.paired)
+        self.deferred_splits = int(self.deferred)
+        return out
+
+
+class ColumnParallelLinear(_LinearBase):
+    """ColumnParallelLinearImpl (parallel_linear.cpp:221-263): Y = X W^T + b, W [out, in] sharded on dim 0
+    (bias on dim 0).  in_features / out_features are the FULL sizes; this rank holds out_features /
+    world_size rows.  act_mul="silu": the weight is the MLP's merged [gate | up] projection
+    (load_state_dict(sd, prefixes=["gate_proj.", "up_proj."])) and forward returns silu(gate) * up of
+    width out_features / 2 per rank from the GEMM epilogue -- the bits of forward + kernels.silu_and_mul."""
+
+    def __init__(self, in_features, out_features, bias, gather_output, parallel_args, dtype, device,
+                 act_mul: Optional[str] = None):
+        super().__init__(in_features, out_features, bias, parallel_args, dtype, device)
+        if out_features % parallel_args.world_size:
+            raise ValueError(f"out_features {out_features} not divisible by world_size {parallel_args.world_size}")
+        self.local_in, self.local_out = in_features, out_features // parallel_args.world_size
+        self.gather_output = gather_output
+        if act_mul not in (None, "silu"):
+            raise ValueError(f"unsupported fused activation {act_mul!r}")
+        self.paired = act_mul == "silu"
+        if self.paired and gather_output:
+            raise ValueError("act_mul needs the sharded output (gather_output=False)")
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        if prefixes:
+            self._load_fused(sd, prefixes, "weight")
+            if self.has_bias:
+                self._load_fused(sd, prefixes, "bias")
+            return
+        self._load_one(sd, "weight", 0)
+        if self.has_bias:
+            self._load_one(sd, "bias", 0)
+
+    def _defers(self, defer_splitk: bool) -> bool:
+        return defer_splitk and not self.has_bias and not self.paired and \
+            not (self.parallel_args.world_size > 1 and self.gather_output)
+
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, reduce: bool = True,
+                defer_splitk: bool = False) -> torch.Tensor:
+        """defer_splitk (no bias, no gather, not act_mul): a split-K call leaves its fp32 slabs for the
+        consumer (self.deferred is truthy then and `out` is NOT written).  `reduce` is accepted for the
+        common call surface; a column-parallel linear has no reduction."""
+        y = self._linear(x, self.bias if self.has_bias else None, out, defer_splitk=self._defers(defer_splitk))
+        if self.parallel_args.world_size > 1 and self.gather_output:
+            y = gather_from_model_parallel_region(y, self.parallel_args)
+        return y
+
+
+class RowParallelLinear(_LinearBase):
+    """RowParallelLinearImpl (parallel_linear.cpp:266-308): Y = sum_ranks X_r W_r^T + b, W [out, in] sharded
+    on dim 1, the bias whole: GEMM, all-reduce, THEN bias (:299-306)."""
+
+    def __init__(self, in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device):
+        super().__init__(in_features, out_features, bias, parallel_args, dtype, device)
+        if in_features % parallel_args.world_size:
+            raise ValueError(f"in_features {in_features} not divisible by world_size {parallel_args.world_size}")
+        self.local_in, self.local_out = in_features // parallel_args.world_size, out_features
+        self.input_is_parallelized = input_is_parallelized
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        if prefixes:
+            raise ValueError("row-parallel linears are never fused (parallel_linear.h:28-33)")
+        self._load_one(sd, "weight", 1)
+        if self.has_bias:
+            self._load_one(sd, "bias", -1)  # added once, after the reduction
+
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, reduce: bool = True,
+                defer_splitk: bool = False) -> torch.Tensor:
+        """reduce=False returns this rank's PARTIAL sums (no all-reduce, no bias): the caller owns the
+        reduction.  defer_splitk (single rank, no bias): a split-K call leaves its fp32 slabs for the
+        RMSNorm that follows (self.deferred is truthy then, and the returned tensor is NOT written)."""
+        if not self.input_is_parallelized and self.parallel_args.world_size > 1:
+            from .model_parallel import scatter_to_model_parallel_region
+            x = scatter_to_model_parallel_region(x, self.parallel_args).contiguous()
+        if self.parallel_args.world_size > 1:
+            y = self._linear(x, None, out)
+            if not reduce:
+                if self.has_bias:
+                    raise ValueError("reduce=False: the bias must be added after the reduction")
+                return y
+            reduce_from_model_parallel_region(y, self.parallel_args)
+            if self.has_bias:
+                y.add_(self.bias)
+            return y
+        return self._linear(x, self.bias if self.has_bias else None, out,
+                            defer_splitk=defer_splitk and not self.has_bias)
 
 
 class LayerNorm:
