@@ -45,7 +45,7 @@ typedef enum slm_status {
 typedef enum slm_dtype {
   SLM_F16 = 0,  /* IEEE half   (torch::kHalf)     */
   SLM_BF16 = 1, /* bfloat16    (torch::kBFloat16) */
-  SLM_F32 = 2   /* IEEE float  (torch::kFloat32): the logits of section 8 only */
+  SLM_F32 = 2   /* IEEE float  (torch::kFloat32): the logits of sections 8 / 9, the rows of section 14 */
 } slm_dtype;
 
 SLM_API const char* slm_status_string(int status);
@@ -1190,6 +1190,54 @@ SLM_API size_t slm_linear_workspace_bytes(const slm_linear_args* a);
 /* number of slabs the call will leave in the workspace (>= 2), or 0 when it writes c as usual */
 SLM_API int32_t slm_linear_deferred_splits(const slm_linear_args* a);
 SLM_API int slm_linear(const slm_linear_args* a, void* stream);
+
+/* ========================================================================== */
+/* 14. MoE token permutation: tokens -> expert-major rows and back            */
+/*    replaces  llm::kernel::moe::permute_with_index_map / _with_mask_map,    */
+/*              unpermute_with_index_map / _with_mask_map                     */
+/*              src/kernels/moe/permutation_index_kernel.cu, _mask_kernel.cu  */
+/*    One map convention serves both forms: row_id_map is int32               */
+/*    [n_maps, n_tokens], entry [m, t] = the row of the permuted tensor that  */
+/*    holds token t for map slot m, or -1 for none.  n_maps = topk in the     */
+/*    index form (slot = position in the token's id list) and n_experts in    */
+/*    the mask form (slot = expert).  Permuted rows are expert-major; within  */
+/*    an expert ascending flat index t * topk + j (index form: the stable     */
+/*    sort of the flattened ids) or ascending token (mask form).              */
+/*    The map entry points are one launch each, pure functions of their       */
+/*    input (no atomic decides a position; counts use integer LDS atomics),   */
+/*    read nothing on the host and can be captured.  n_experts <= 1024 and    */
+/*    n_tokens * n_maps < 2^31 - 256, else SLM_ERR_INVALID_ARG, as a NULL     */
+/*    input / map with n_tokens > 0.  n_tokens == 0 is SLM_OK; the counts,    */
+/*    when given, are still zeroed.  Cost: every workgroup reads the whole    */
+/*    input once and each expert's wave walks it again -- sized for decode    */
+/*    and verify batches (a few thousand tokens); correct beyond.             */
+/*    Row entry points: rows are contiguous, dim * sizeof(T) % 16 == 0 (else  */
+/*    SLM_ERR_UNSUPPORTED, as any dtype but F16 / BF16 / F32); 1 <= n_maps    */
+/*    <= 1024; negative sizes or a NULL pointer SLM_ERR_INVALID_ARG; row      */
+/*    bases 16-byte aligned, else SLM_ERR_ALIGNMENT; all before any launch.   */
+/*    n_tokens == 0 is SLM_OK without a launch.  Map entries that are         */
+/*    negative or >= permuted_rows are skipped, so nothing outside            */
+/*    permuted [permuted_rows, dim] is touched whatever the map holds.        */
+/*    One wave owns 4 KiB of one token's row (csrc/permute.hip).              */
+/* ========================================================================== */
+/* topk_ids [n_tokens, topk] -> row_id_map [topk, n_tokens]; ids outside [0, n_experts) get -1 and take no row
+ * (as slm_moe_align_block drops them).  tokens_per_expert [n_experts] or NULL: rows per expert. */
+SLM_API int slm_permute_index_map(const int32_t* topk_ids, int64_t n_tokens, int32_t topk, int32_t n_experts,
+                                  int32_t* row_id_map, int32_t* tokens_per_expert, void* stream);
+/* routing_map [n_tokens, n_experts] bytes (non-zero = routed) -> row_id_map [n_experts, n_tokens].
+ * tokens_per_expert [n_experts] or NULL; n_permuted [1] or NULL: the number of mapped rows. */
+SLM_API int slm_permute_mask_map(const uint8_t* routing_map, int64_t n_tokens, int32_t n_experts,
+                                 int32_t* row_id_map, int32_t* tokens_per_expert, int32_t* n_permuted, void* stream);
+/* permuted[row_id_map[m, t]] = tokens[t] for every mapped m: a source row is read once, in 16-byte vectors.
+ * permuted_rows == 0 stores nothing (SLM_OK without a launch). */
+SLM_API int slm_permute_rows(void* permuted, const void* tokens, const int32_t* row_id_map, int64_t n_tokens,
+                             int32_t n_maps, int64_t dim, int64_t permuted_rows, int32_t dtype, void* stream);
+/* out[t] = T( sum_m probs[t, m] * permuted[row_id_map[m, t]] ): fp32 fma chain in ascending m over the mapped m,
+ * ONE rounding (slm_moe_sum's convention; the reference accumulates in T).  probs [n_tokens, n_maps]
+ * of probs_dtype = SLM_F32 or `dtype`, or NULL for 1.  A token with no mapped row gets zeros. */
+SLM_API int slm_unpermute_rows(void* out, const void* permuted, const int32_t* row_id_map, const void* probs,
+                               int32_t probs_dtype, int64_t n_tokens, int32_t n_maps, int64_t dim,
+                               int64_t permuted_rows, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

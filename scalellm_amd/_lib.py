@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libslm_hip.so")
 
 SLM_F16, SLM_BF16 = 0, 1
-SLM_F32 = 2  # logits of the sampling entry points (slm_hip.h section 8) only
+SLM_F32 = 2  # logits of the sampling entry points (slm_hip.h sections 8 / 9), token rows of section 14
 SLM_SAMPLE_MAX_TOP = 20
 SLM_REJECTION_MAX_K = 16
 SLM_W4_GPTQ, SLM_W4_AWQ = 0, 1
@@ -371,6 +371,15 @@ def lib() -> C.CDLL:
         ("slm_linear_plan", C.c_int, [C.POINTER(LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_soft_cap", C.c_int,
          [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
+        ("slm_permute_index_map", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        ("slm_permute_mask_map", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        ("slm_permute_rows", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+        ("slm_unpermute_rows", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+          C.c_int32, C.c_void_p]),
     ]:
         fn = getattr(L, name)  # AttributeError here = library/header mismatch: fail loudly
         fn.restype = restype

@@ -11,6 +11,7 @@
 #include "slm_llama_hip.h"
 #include "slm_mla_hip.h"
 #include "slm_moe_hip.h"
+#include "slm_permute_hip.h"
 #include "slm_linear_hip.h"
 #include "slm_qlinear_hip.h"
 #include "slm_rejection_sampler_hip.h"
@@ -272,6 +273,15 @@ PYBIND11_MODULE(_slm_shim, m) {
                                 row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
         }, py::arg("a"), py::arg("w"), py::arg("c"), py::arg("sorted_token_idxes"), py::arg("expert_ids"),
         py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
+  // MoE token permutation (slm_permute_hip.h): the reference's four functions
+  m.def("moe_permute_with_index_map", &llm::kernel::moe::permute_with_index_map, py::arg("tokens"),
+        py::arg("indices"));
+  m.def("moe_unpermute_with_index_map", &llm::kernel::moe::unpermute_with_index_map, py::arg("permuted_tokens"),
+        py::arg("row_id_map"), py::arg("probs"));
+  m.def("moe_permute_with_mask_map", &llm::kernel::moe::permute_with_mask_map, py::arg("tokens"),
+        py::arg("routing_map"), py::arg("topk"));
+  m.def("moe_unpermute_with_mask_map", &llm::kernel::moe::unpermute_with_mask_map, py::arg("permuted_tokens"),
+        py::arg("row_id_map"), py::arg("probs"));
   // multi-head latent attention (slm_mla_hip.h)
   m.def("mla_paged_kv",
         [](torch::Tensor out, const torch::Tensor& q, const torch::Tensor& kv_cache, const torch::Tensor& q_rope,

@@ -1562,6 +1562,169 @@ def moe_grouped_gemm(a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, sorted_t
 
 
 # ---------------------------------------------------------------------------------------
+# MoE token permutation (slm_hip.h section 14; csrc/permute.hip)
+#   permute_with_index_map / unpermute_with_index_map <- llm::kernel::moe::  (permutation_index_kernel.cu)
+#   permute_with_mask_map / unpermute_with_mask_map   <- llm::kernel::moe::  (permutation_mask_kernel.cu)
+# The four take and return what the reference's take and return; every buffer can be passed in (out= / row_id_map= /
+# tokens_per_expert=) so that a caller allocates once and captures the calls in a graph.
+# ---------------------------------------------------------------------------------------
+PERMUTE_MAX_EXPERTS = 1024
+_ROW_DTYPES = {torch.float16: SLM_F16, torch.bfloat16: SLM_BF16, torch.float32: _lib.SLM_F32}
+
+
+def _row_dtype_code(t: torch.Tensor) -> int:
+    if t.dtype not in _ROW_DTYPES:
+        raise SlmError(f"token rows must be fp16, bf16 or fp32, got {t.dtype}")
+    return _ROW_DTYPES[t.dtype]
+
+
+def _i32_buffer(t: Optional[torch.Tensor], n: int, device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(n, dtype=torch.int32, device=device)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise SlmError(f"{what} must be contiguous int32 with {n} entries")
+    return t
+
+
+def permute_index_map(topk_ids: torch.Tensor, n_experts: int = PERMUTE_MAX_EXPERTS,
+                      row_id_map: Optional[torch.Tensor] = None, tokens_per_expert: Optional[torch.Tensor] = None,
+                      count: bool = False):
+    """topk_ids [T, k] int32 -> row_id_map [k, T] int32: the permuted row of every (token, slot), expert-major and
+    within an expert by ascending t * k + j; ids outside [0, n_experts) get -1.  count=True (or a tokens_per_expert
+    buffer) also returns the rows per expert.  Returns (row_id_map, tokens_per_expert or None)."""
+    _require_gpu(topk_ids, row_id_map, tokens_per_expert)
+    if topk_ids.dim() != 2 or topk_ids.dtype != torch.int32 or not topk_ids.is_contiguous():
+        raise SlmError("topk_ids must be contiguous int32 [n_tokens, topk]")
+    T, k = topk_ids.shape
+    row_id_map = _i32_buffer(row_id_map, k * T, topk_ids.device, "row_id_map").view(k, T)
+    if count or tokens_per_expert is not None:
+        tokens_per_expert = _i32_buffer(tokens_per_expert, n_experts, topk_ids.device, "tokens_per_expert")
+    check(_lib.lib().slm_permute_index_map(topk_ids.data_ptr(), T, k, n_experts, row_id_map.data_ptr(),
+                                           _ptr(tokens_per_expert), _stream()), "slm_permute_index_map")
+    return row_id_map, tokens_per_expert
+
+
+def permute_mask_map(routing_map: torch.Tensor, row_id_map: Optional[torch.Tensor] = None,
+                     tokens_per_expert: Optional[torch.Tensor] = None, n_permuted: Optional[torch.Tensor] = None,
+                     count: bool = False):
+    """routing_map [T, E] bool (or uint8) -> row_id_map [E, T] int32: the permuted row of token t at expert e or -1,
+    expert-major and within an expert by ascending token.  Returns (row_id_map, tokens_per_expert or None);
+    n_permuted: an int32 [1] buffer that receives the number of mapped rows."""
+    _require_gpu(routing_map, row_id_map, tokens_per_expert, n_permuted)
+    if routing_map.dim() != 2 or routing_map.dtype not in (torch.bool, torch.uint8) or \
+            not routing_map.is_contiguous():
+        raise SlmError("routing_map must be contiguous bool [n_tokens, n_experts]")
+    T, E = routing_map.shape
+    row_id_map = _i32_buffer(row_id_map, E * T, routing_map.device, "row_id_map").view(E, T)
+    if count or tokens_per_expert is not None:
+        tokens_per_expert = _i32_buffer(tokens_per_expert, E, routing_map.device, "tokens_per_expert")
+    if n_permuted is not None:
+        n_permuted = _i32_buffer(n_permuted, 1, routing_map.device, "n_permuted")
+    check(_lib.lib().slm_permute_mask_map(routing_map.data_ptr(), T, E, row_id_map.data_ptr(),
+                                          _ptr(tokens_per_expert), _ptr(n_permuted), _stream()),
+          "slm_permute_mask_map")
+    return row_id_map, tokens_per_expert
+
+
+def _rows_2d(t: torch.Tensor, what: str) -> None:
+    if t.dim() != 2 or not t.is_contiguous():
+        raise SlmError(f"{what} must be a contiguous [rows, dim] tensor")
+
+
+def permute_rows(tokens: torch.Tensor, row_id_map: torch.Tensor, permuted: torch.Tensor) -> torch.Tensor:
+    """permuted[row_id_map[m, t]] = tokens[t] for every mapped m; rows of `permuted` that no entry names keep what
+    they held."""
+    _require_gpu(tokens, row_id_map, permuted)
+    _rows_2d(tokens, "tokens")
+    _rows_2d(permuted, "permuted_tokens")
+    T, dim = tokens.shape
+    if permuted.dtype != tokens.dtype or permuted.size(1) != dim:
+        raise SlmError("permuted_tokens must have the tokens' dtype and dim")
+    if row_id_map.dtype != torch.int32 or not row_id_map.is_contiguous() or T == 0 and row_id_map.numel() or \
+            T and row_id_map.numel() % T:
+        raise SlmError("row_id_map must be contiguous int32 [n_maps, n_tokens]")
+    n_maps = row_id_map.numel() // T if T else 1
+    check(_lib.lib().slm_permute_rows(permuted.data_ptr(), tokens.data_ptr(), row_id_map.data_ptr(), T, n_maps, dim,
+                                      permuted.size(0), _row_dtype_code(tokens), _stream()), "slm_permute_rows")
+    return permuted
+
+
+def unpermute_rows(permuted: torch.Tensor, row_id_map: torch.Tensor, probs: Optional[torch.Tensor], n_tokens: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[t] = sum over the mapped m of probs[t, m] * permuted[row_id_map[m, t]], fp32, one rounding; probs [T,
+    n_maps] fp32 or of the tokens' dtype, None = 1."""
+    _require_gpu(permuted, row_id_map, probs, out)
+    _rows_2d(permuted, "permuted_tokens")
+    dim = permuted.size(1)
+    if out is None:
+        out = torch.empty(n_tokens, dim, dtype=permuted.dtype, device=permuted.device)
+    _rows_2d(out, "out")
+    if out.dtype != permuted.dtype or tuple(out.shape) != (n_tokens, dim):
+        raise SlmError("out must be [n_tokens, dim] of the permuted tokens' dtype")
+    if row_id_map.dtype != torch.int32 or not row_id_map.is_contiguous() or \
+            (n_tokens and row_id_map.numel() % n_tokens) or (not n_tokens and row_id_map.numel()):
+        raise SlmError("row_id_map must be contiguous int32 [n_maps, n_tokens]")
+    n_maps = row_id_map.numel() // n_tokens if n_tokens else 1
+    pcode = _lib.SLM_F32
+    if probs is not None:
+        if probs.dtype not in (torch.float32, permuted.dtype) or not probs.is_contiguous() or \
+                probs.numel() != n_tokens * n_maps:
+            raise SlmError("probs must be contiguous [n_tokens, n_maps], fp32 or of the tokens' dtype")
+        pcode = _row_dtype_code(probs)
+    check(_lib.lib().slm_unpermute_rows(out.data_ptr(), permuted.data_ptr(), row_id_map.data_ptr(), _ptr(probs),
+                                        pcode, n_tokens, n_maps, dim, permuted.size(0), _row_dtype_code(permuted),
+                                        _stream()), "slm_unpermute_rows")
+    return out
+
+
+def _permuted_out(out: Optional[torch.Tensor], rows: int, tokens: torch.Tensor) -> torch.Tensor:
+    if out is None:
+        return torch.empty(rows, tokens.size(1), dtype=tokens.dtype, device=tokens.device)
+    if out.dim() != 2 or out.size(0) < rows:
+        raise SlmError(f"out needs at least {rows} rows")
+    return out
+
+
+def permute_with_index_map(tokens: torch.Tensor, indices: torch.Tensor, n_experts: int = PERMUTE_MAX_EXPERTS,
+                           out: Optional[torch.Tensor] = None, row_id_map: Optional[torch.Tensor] = None,
+                           tokens_per_expert: Optional[torch.Tensor] = None):
+    """llm::kernel::moe::permute_with_index_map: tokens [T, dim], indices [T, k] int32 -> (permuted_tokens
+    [T * k, dim] sorted by (expert, flat index), row_id_map [k, T]).  The reference is not told n_experts; the
+    default is the kernels' upper bound and costs nothing but idle workgroups."""
+    _require_gpu(tokens)
+    _rows_2d(tokens, "tokens")
+    row_id_map, _ = permute_index_map(indices, n_experts, row_id_map, tokens_per_expert)
+    out = _permuted_out(out, indices.numel(), tokens)
+    return permute_rows(tokens, row_id_map, out), row_id_map
+
+
+def unpermute_with_index_map(permuted_tokens: torch.Tensor, row_id_map: torch.Tensor, probs: torch.Tensor,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """llm::kernel::moe::unpermute_with_index_map: probs [T, k] -> tokens [T, dim]."""
+    return unpermute_rows(permuted_tokens, row_id_map, probs, probs.size(0), out)
+
+
+def permute_with_mask_map(tokens: torch.Tensor, routing_map: torch.Tensor, topk: int,
+                          out: Optional[torch.Tensor] = None, row_id_map: Optional[torch.Tensor] = None,
+                          tokens_per_expert: Optional[torch.Tensor] = None):
+    """llm::kernel::moe::permute_with_mask_map: tokens [T, dim], routing_map [T, E] bool with topk experts per token
+    -> (permuted_tokens [T * topk, dim] sorted by (expert, token), row_id_map [E, T])."""
+    _require_gpu(tokens)
+    _rows_2d(tokens, "tokens")
+    row_id_map, _ = permute_mask_map(routing_map, row_id_map, tokens_per_expert)
+    out = _permuted_out(out, tokens.size(0) * topk, tokens)
+    return permute_rows(tokens, row_id_map, out), row_id_map
+
+
+def unpermute_with_mask_map(permuted_tokens: torch.Tensor, row_id_map: torch.Tensor, probs: torch.Tensor,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """llm::kernel::moe::unpermute_with_mask_map: row_id_map [E, T], probs [T, E] -> tokens [T, dim]."""
+    if row_id_map.dim() != 2:
+        raise SlmError("row_id_map must be [n_experts, n_tokens]")
+    return unpermute_rows(permuted_tokens, row_id_map, probs, row_id_map.size(1), out)
+
+
+# ---------------------------------------------------------------------------------------
 # multi-head latent attention (slm_hip.h section 11; csrc/mla.hip)
 # ---------------------------------------------------------------------------------------
 def _mla_args(out, q, q_rope, kv_cache, k_rope_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens,

@@ -53,11 +53,16 @@ class ProcessGroup:
             return
         dist.all_gather_into_tensor(output, tensor.contiguous(), group=self._group)
 
-    def alltoall(self, tensor: torch.Tensor, output: torch.Tensor) -> None:
+    # alltoall along dim 0: equal parts, or input_split_sizes[r] rows to rank r and output_split_sizes[r] rows
+    # from it (both process_group.h forms)
+    def alltoall(self, tensor: torch.Tensor, output: torch.Tensor,
+                 input_split_sizes: Optional[List[int]] = None,
+                 output_split_sizes: Optional[List[int]] = None) -> None:
         if self.world_size == 1:
             output.copy_(tensor)
             return
-        dist.all_to_all_single(output, tensor.contiguous(), group=self._group)
+        dist.all_to_all_single(output, tensor.contiguous(), output_split_sizes, input_split_sizes,
+                               group=self._group)
 
     def barrier(self) -> None:
         if self.world_size > 1:
@@ -110,7 +115,7 @@ class LocalShardProcessGroup(ProcessGroup):
     def allgather_into(self, tensor, output):
         output.view(self.world_size, -1).copy_(tensor.reshape(1, -1).expand(self.world_size, -1))
 
-    def alltoall(self, tensor, output):
+    def alltoall(self, tensor, output, input_split_sizes=None, output_split_sizes=None):
         output.copy_(tensor)
 
     def barrier(self):

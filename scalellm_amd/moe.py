@@ -11,12 +11,16 @@ section 10).
 
 All buffers are sized at construction by the capacity rule (slm_moe_align_capacity) for max_tokens rows, nothing on
 the path reads a device value on the host, and a smaller batch runs in views of the same buffers: forward() can be
-captured in a graph and replayed for any routing.  Out of scope here: expert / tensor parallel sharding, shared
-experts, 8-bit and act-order experts.
+captured in a graph and replayed for any routing.
+
+Across GPUs the experts are sharded by expert parallelism: LocalTokenDispatcher / AlltoAllTokenDispatcher permute
+tokens into expert-major rows (include/slm_hip.h section 14) and ExpertParallelMoE runs the same two grouped GEMMs
+over one rank's experts between an all-to-all pair.  Out of scope here: tensor-parallel sharding of an expert,
+shared experts, 8-bit and act-order experts.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -31,7 +35,7 @@ class MoEQuantExperts:
     experts.{e}.w1|w3|w2.{qweight,qzeros,scales}; the repack is lazy, on the first forward, like the linears'."""
 
     def __init__(self, hidden: int, intermediate: int, n_experts: int, quant_args: QuantArgs,
-                 dtype: torch.dtype, device):
+                 dtype: torch.dtype, device, expert_offset: int = 0):
         if quant_args.bits != 4:
             raise SlmError("MoE experts: 4-bit weights only (8-bit planes need the column gather)")
         if quant_args.desc_act:
@@ -40,6 +44,7 @@ class MoEQuantExperts:
             raise SlmError(f"unknown quant_method {quant_args.quant_method}")
         self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
         self.quant_args, self.dtype, self.device = quant_args, dtype, device
+        self.expert_offset = expert_offset   # expert e of this holder is experts.{expert_offset + e}.* (an EP shard)
         self._ckpt: Dict[str, torch.Tensor] = {}
         self.gate_up: Optional[kernels.PackedMoeW4] = None
         self.down: Optional[kernels.PackedMoeW4] = None
@@ -48,9 +53,9 @@ class MoEQuantExperts:
         for e in range(self.n_experts):
             for w in ("w1", "w2", "w3"):
                 for name in ("qweight", "qzeros", "scales"):
-                    key = f"experts.{e}.{w}.{name}"
+                    key = f"experts.{self.expert_offset + e}.{w}.{name}"
                     if key in sd:
-                        self._ckpt[key] = sd[key].to(self.device)
+                        self._ckpt[f"experts.{e}.{w}.{name}"] = sd[key].to(self.device)
         self.gate_up = self.down = None
 
     def verify_loaded_weights(self) -> None:
@@ -93,11 +98,13 @@ class MoEDenseExperts:
     [E, 2 * intermediate, hidden] (w1 rows, then w3 rows) and `down` [E, hidden, intermediate].  load_state_dict takes
     Mixtral-style names experts.{e}.w1|w3|w2.weight; nothing is repacked, the stacking happens on the first forward."""
 
-    def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device):
+    def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device,
+                 expert_offset: int = 0):
         if dtype not in (torch.float16, torch.bfloat16):
             raise SlmError(f"MoE experts: fp16 / bf16 only, got {dtype}")
         self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
         self.dtype, self.device = dtype, device
+        self.expert_offset = expert_offset   # expert e of this holder is experts.{expert_offset + e}.* (an EP shard)
         self._ckpt: Dict[str, torch.Tensor] = {}
         self.gate_up: Optional[torch.Tensor] = None
         self.down: Optional[torch.Tensor] = None
@@ -105,9 +112,9 @@ class MoEDenseExperts:
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         for e in range(self.n_experts):
             for w in ("w1", "w2", "w3"):
-                key = f"experts.{e}.{w}.weight"
+                key = f"experts.{self.expert_offset + e}.{w}.weight"
                 if key in sd:
-                    self._ckpt[key] = sd[key].to(self.device, self.dtype)
+                    self._ckpt[f"experts.{e}.{w}.weight"] = sd[key].to(self.device, self.dtype)
         self.gate_up = self.down = None
 
     def verify_loaded_weights(self) -> None:
@@ -227,5 +234,242 @@ class FusedMoE:
         self._gemm(act, self.experts.down, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
         kernels.moe_sum(down.view(T, k, self.hidden), out.view(T, self.hidden))
         return out.view(x.shape)
+
+    __call__ = forward
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Token dispatchers (reference src/layers/moe/): tokens -> expert-major rows -> (experts) -> tokens, on one GPU
+# (LocalTokenDispatcher) or across an expert-parallel group (AlltoAllTokenDispatcher).  Both keep the row_id_map
+# and the probabilities between dispatch and combine; the probability multiply is part of the un-permute kernel.
+#   dispatch(tokens, probs [T, E], routing_map [T, E] bool)      the reference's entry (mask-map kernels)
+#   dispatch_topk(tokens, topk_weights [T, k], topk_ids [T, k])  what moe_topk_softmax produces (index-map kernels)
+# ---------------------------------------------------------------------------------------------------------------
+class AlltoAllPlan(NamedTuple):
+    input_split_sizes: List[int]             # rows this rank sends to each rank
+    output_split_sizes: List[int]            # rows it receives from each rank
+    tokens_per_local_expert: torch.Tensor    # [n_local_experts] int64 (CPU): rows per expert of this rank
+    reorder: Optional[torch.Tensor]          # [rows received] int32 (CPU): received row (rank, expert)-major ->
+    #                                          its row in (expert, rank) order; None when that is the identity
+
+
+def alltoall_plan(counts, rank: int) -> AlltoAllPlan:
+    """The bookkeeping of alltoall_token_dispatcher.cpp:148-189 as a pure function of the gathered counts
+    [ep, n_experts] (row r = rank r's tokens per expert) and this rank.  Ranks own contiguous expert ranges."""
+    counts = torch.as_tensor(counts, dtype=torch.int64, device="cpu")
+    ep, E = counts.shape
+    if E % ep:
+        raise SlmError("n_experts must be divisible by the expert-parallel size")
+    L = E // ep
+    local = counts[:, rank * L:(rank + 1) * L]                        # [ep, L]: what each rank sends here
+    plan = AlltoAllPlan(counts[rank].view(ep, L).sum(1).tolist(), local.sum(1).tolist(), local.sum(0), None)
+    if ep == 1 or L == 1:
+        return plan
+    src = local.reshape(-1)                                           # chunk sizes as received: (rank, expert)
+    src_off = src.cumsum(0) - src
+    dst = local.t().reshape(-1)                                       # ... as the grouped GEMM wants: (expert, rank)
+    dst_off = (dst.cumsum(0) - dst).view(L, ep).t().reshape(-1)       # indexed like src
+    chunk = torch.repeat_interleave(torch.arange(ep * L), src)
+    reorder = (dst_off - src_off)[chunk] + torch.arange(chunk.numel())
+    return plan._replace(reorder=reorder.to(torch.int32))
+
+
+class _TokenDispatcher:
+    """State shared by both dispatchers: the map, the probabilities and the shape to restore."""
+
+    def __init__(self, topk: int, n_experts: Optional[int] = None):
+        self.topk, self.n_experts = topk, n_experts
+        self._map = self._probs = self._shape = None
+
+    @staticmethod
+    def _check_tokens(tokens: torch.Tensor) -> None:
+        if tokens.dim() != 2 or not tokens.is_contiguous():
+            raise SlmError("tokens must be a contiguous [n_tokens, dim] tensor")
+
+    def _map_mask(self, tokens, probs, routing_map):
+        self._check_tokens(tokens)
+        if tuple(probs.shape) != tuple(routing_map.shape) or routing_map.size(0) != tokens.size(0):
+            raise SlmError("probs and routing_map must be [n_tokens, n_experts]")
+        if self.n_experts is not None and routing_map.size(1) != self.n_experts:
+            raise SlmError(f"routing_map has {routing_map.size(1)} experts, the dispatcher {self.n_experts}")
+        self._map, counts = kernels.permute_mask_map(routing_map, count=True)
+        self._probs, self._shape = probs.contiguous(), tokens.shape
+        return counts
+
+    def _map_index(self, tokens, topk_weights, topk_ids):
+        self._check_tokens(tokens)
+        if self.n_experts is None:
+            raise SlmError("dispatch_topk needs the dispatcher built with n_experts")
+        if tuple(topk_ids.shape) != (tokens.size(0), self.topk) or tuple(topk_weights.shape) != tuple(topk_ids.shape):
+            raise SlmError("topk_weights and topk_ids must be [n_tokens, topk]")
+        self._map, counts = kernels.permute_index_map(topk_ids, self.n_experts, count=True)
+        self._probs, self._shape = topk_weights.contiguous(), tokens.shape
+        return counts
+
+    def _permute(self, tokens: torch.Tensor) -> torch.Tensor:
+        out = torch.empty(tokens.size(0) * self.topk, tokens.size(1), dtype=tokens.dtype, device=tokens.device)
+        return kernels.permute_rows(tokens, self._map, out)
+
+    def _unpermute(self, permuted: torch.Tensor) -> torch.Tensor:
+        if self._map is None:
+            raise SlmError("combine() without a dispatch before it")
+        return kernels.unpermute_rows(permuted, self._map, self._probs, self._shape[0]).view(self._shape)
+
+
+class LocalTokenDispatcher(_TokenDispatcher):
+    """llm::LocalTokenDispatcher: every expert lives on this GPU.  dispatch returns (permuted_tokens [T * topk, dim]
+    sorted by expert, tokens_per_expert [E] int32 from the map kernel); combine(permuted) returns the tokens'
+    weighted sums in their first order (bias is accepted and unused, as in the reference).  T * topk is known on
+    the host, so nothing is read back and dispatch -> experts -> combine can be captured in a graph.  Rows past the
+    mapped count (a routing_map row with fewer than topk experts, an id outside [0, n_experts)) are not written."""
+
+    def dispatch(self, tokens, probs, routing_map):
+        counts = self._map_mask(tokens, probs, routing_map)
+        return self._permute(tokens), counts
+
+    def dispatch_topk(self, tokens, topk_weights, topk_ids):
+        counts = self._map_index(tokens, topk_weights, topk_ids)
+        return self._permute(tokens), counts
+
+    def combine(self, permuted_tokens, bias=None):
+        return self._unpermute(permuted_tokens)
+
+
+class AlltoAllTokenDispatcher(_TokenDispatcher):
+    """llm::AlltoAllTokenDispatcher (alltoall_token_dispatcher.cpp:126-253): rank r of the expert-parallel group owns
+    experts [r * L, (r + 1) * L), L = n_experts / ep.  dispatch: per-expert counts from the map kernel -> all-gather
+    -> split sizes -> permute -> all-to-all -> (rank, expert) to (expert, rank) chunk reorder when L > 1; returns
+    (the rows of this rank's experts sorted by expert, tokens_per_local_expert [L] int32).  combine is the inverse,
+    ending in the probability-weighted un-permute.
+
+    The gathered counts are copied to the host once per dispatch (the split sizes of the all-to-all are host
+    integers; the reference does the same), so this class canNOT be captured in a graph.  That copy is its only
+    device-to-host transfer.  With ep == 1 nothing is gathered or copied."""
+
+    def __init__(self, n_experts: int, topk: int, process_group):
+        super().__init__(topk, n_experts)
+        self.pg = process_group
+        self.ep_size, self.ep_rank = process_group.world_size, process_group.rank
+        if n_experts % self.ep_size:
+            raise SlmError("n_experts must be divisible by the expert-parallel size")
+        self.n_local_experts = n_experts // self.ep_size
+        self._plan: Optional[AlltoAllPlan] = None
+        self._reorder = None
+
+    def _gather_plan(self, counts: torch.Tensor) -> AlltoAllPlan:
+        """all-gather this rank's per-expert counts and plan the exchange from every rank's"""
+        gathered = torch.empty(self.ep_size * self.n_experts, dtype=torch.int32, device=counts.device)
+        self.pg.allgather_into(counts, gathered)
+        return alltoall_plan(gathered.cpu().view(self.ep_size, -1), self.ep_rank)   # THE device-to-host copy
+
+    def _exchange(self, tokens: torch.Tensor, counts: torch.Tensor):
+        permuted = self._permute(tokens)
+        if self.ep_size == 1:
+            return permuted, counts
+        plan = self._plan = self._gather_plan(counts)
+        n_send, n_recv = sum(plan.input_split_sizes), sum(plan.output_split_sizes)
+        recv = torch.empty(n_recv, tokens.size(1), dtype=tokens.dtype, device=tokens.device)
+        self.pg.alltoall(permuted[:n_send], recv, plan.input_split_sizes, plan.output_split_sizes)
+        self._reorder = None
+        if plan.reorder is not None and n_recv:
+            self._reorder = plan.reorder.to(tokens.device)
+            recv = kernels.permute_rows(recv, self._reorder, torch.empty_like(recv))
+        return recv, plan.tokens_per_local_expert.to(device=tokens.device, dtype=torch.int32)
+
+    def dispatch(self, tokens, probs, routing_map):
+        return self._exchange(tokens, self._map_mask(tokens, probs, routing_map))
+
+    def dispatch_topk(self, tokens, topk_weights, topk_ids):
+        return self._exchange(tokens, self._map_index(tokens, topk_weights, topk_ids))
+
+    def combine(self, permuted_tokens, bias=None):
+        if self.ep_size == 1:
+            return self._unpermute(permuted_tokens)
+        plan = self._plan
+        if plan is None:
+            raise SlmError("combine() without a dispatch before it")
+        if self._reorder is not None:   # back to (rank, expert) order: row i comes from row reorder[i]
+            permuted_tokens = kernels.unpermute_rows(permuted_tokens, self._reorder, None, permuted_tokens.size(0))
+        back = torch.empty(sum(plan.input_split_sizes), permuted_tokens.size(1), dtype=permuted_tokens.dtype,
+                           device=permuted_tokens.device)
+        self.pg.alltoall(permuted_tokens, back, plan.output_split_sizes, plan.input_split_sizes)
+        return self._unpermute(back)
+
+
+class ExpertParallelMoE:
+    """FusedMoE's block with the experts sharded over an expert-parallel group: every rank routes its own tokens
+    (the router weight is replicated), AlltoAllTokenDispatcher.dispatch_topk sends each (token, expert) row to the
+    expert's rank, the two grouped GEMMs run over this rank's experts [rank * L, (rank + 1) * L), and combine
+    brings the rows home and takes the weighted sum.  Rounding points: after SiLU * mul, after the down GEMM (the
+    rows travel in T), after the weighted sum (fp32, one rounding) -- the weights are applied at the source rank,
+    not on the down GEMM's accumulator as in FusedMoE.  Not capturable (the dispatcher's copy of the counts)."""
+
+    def __init__(self, hidden: int, intermediate: int, n_experts: int, topk: int, process_group,
+                 quant_args: Optional[QuantArgs] = None, scoring: str = "softmax", renormalize: bool = True,
+                 n_expert_groups: int = 1, topk_group: int = 1, scaling_factor: float = 1.0,
+                 dtype: torch.dtype = torch.bfloat16, device="cuda"):
+        if scoring not in ("softmax", "grouped_sigmoid"):
+            raise SlmError(f"unknown scoring {scoring}")
+        if not 1 <= topk <= n_experts:
+            raise SlmError(f"topk = {topk} must be in 1 .. n_experts = {n_experts}")
+        self.dispatcher = AlltoAllTokenDispatcher(n_experts, topk, process_group)
+        L = self.n_local_experts = self.dispatcher.n_local_experts
+        self.hidden, self.intermediate, self.n_experts, self.topk = hidden, intermediate, n_experts, topk
+        self.scoring, self.renormalize = scoring, renormalize
+        self.n_expert_groups, self.topk_group, self.scaling_factor = n_expert_groups, topk_group, scaling_factor
+        self.dtype, self.device = dtype, device
+        offset = process_group.rank * L
+        self.experts = MoEDenseExperts(hidden, intermediate, L, dtype, device, expert_offset=offset) \
+            if quant_args is None else \
+            MoEQuantExperts(hidden, intermediate, L, quant_args, dtype, device, expert_offset=offset)
+        self._gemm = kernels.moe_grouped_gemm if quant_args is None else kernels.moe_w4_grouped_gemm
+        self.gate_weight: Optional[torch.Tensor] = None
+        self.correction_bias: Optional[torch.Tensor] = None
+        self._gate_f32_t: Optional[torch.Tensor] = None
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        if "gate.weight" in sd:
+            self.gate_weight = sd["gate.weight"].to(self.device)
+            self._gate_f32_t = None
+        if "gate.e_score_correction_bias" in sd:
+            self.correction_bias = sd["gate.e_score_correction_bias"].to(self.device, torch.float32).contiguous()
+        self.experts.load_state_dict(sd)
+
+    def _experts_forward(self, rows: torch.Tensor, tokens_per_local_expert: torch.Tensor) -> torch.Tensor:
+        n, L, dev, i32 = rows.size(0), self.n_local_experts, rows.device, torch.int32
+        down = torch.empty(n, self.hidden, dtype=rows.dtype, device=dev)
+        if n == 0:
+            return down
+        # the expert of every row (the rows are sorted by expert), aligned to the GEMM's blocks as topk = 1 ids
+        row_expert = torch.repeat_interleave(torch.arange(L, dtype=i32, device=dev), tokens_per_local_expert,
+                                             output_size=n).to(i32).view(n, 1).contiguous()
+        max_padded, max_blocks = kernels.moe_align_capacity(n, L, kernels.MOE_GEMM_BLOCK)
+        srt = torch.empty(max_padded, dtype=i32, device=dev)
+        eids = torch.empty(max_blocks, dtype=i32, device=dev)
+        n_padded = torch.zeros(1, dtype=i32, device=dev)
+        kernels.moe_align_block(row_expert, L, kernels.MOE_GEMM_BLOCK, srt, eids, n_padded)
+        act = torch.empty(n, self.intermediate, dtype=rows.dtype, device=dev)
+        self._gemm(rows, self.experts.gate_up, act, srt, eids, n_padded, a_div=1, silu_mul=True)
+        self._gemm(act, self.experts.down, down, srt, eids, n_padded, a_div=1)
+        return down
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.experts.gate_up is None:
+            self.experts.repack()
+        if self.gate_weight is None:
+            raise SlmError("gate.weight is not loaded")
+        x2 = x.reshape(-1, self.hidden).contiguous()
+        if self._gate_f32_t is None:
+            self._gate_f32_t = self.gate_weight.float().t().contiguous()
+        logits = x2.float() @ self._gate_f32_t
+        if self.scoring == "softmax":
+            weights, ids = kernels.moe_topk_softmax(logits, self.topk, self.renormalize)
+        else:
+            if self.correction_bias is None:
+                raise SlmError("gate.e_score_correction_bias is not loaded")
+            weights, ids = kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups,
+                                                            self.topk_group, self.topk, self.scaling_factor)
+        rows, tokens_per_local_expert = self.dispatcher.dispatch_topk(x2, weights, ids)
+        return self.dispatcher.combine(self._experts_forward(rows, tokens_per_local_expert)).view(x.shape)
 
     __call__ = forward
