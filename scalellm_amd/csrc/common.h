@@ -191,7 +191,7 @@ __device__ __forceinline__ u32x4 silu_mul8(const u32x4 g, const u32x4 u) {
 }
 
 // sum over split-K partial slabs of 4 consecutive columns, in THE order of the split-K reduce
-// kernel (w4.hip) -- shared with the RMSNorm that can absorb the reduction (glue.hip), so that
+// kernel (below) -- shared with the RMSNorm that can absorb the reduction (glue.hip), so that
 // "GEMM -> reduce -> norm" and "GEMM (deferred) -> norm" give identical bits
 __device__ __forceinline__ f32x4 splitk_sum4(const float* __restrict__ src, const int64_t slab,
                                              const int split_k) {
@@ -211,6 +211,46 @@ __device__ __forceinline__ f32x4 splitk_sum4(const float* __restrict__ src, cons
   }
   if (k < split_k) s += *reinterpret_cast<const f32x4*>(src + k * slab);
   return s;
+}
+
+// C[m, n] = T( sum_s part[s][m][n] + bias[n] ): THE split-K reduce (w4.hip, dense.hip).  A deferred consumer
+// (splitk_sum4, the same order) and this launch give identical bits
+template <typename T>
+__global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restrict__ part,
+                                                            const void* __restrict__ bias,
+                                                            void* __restrict__ c, int64_t M,
+                                                            int64_t N, int64_t ldc, int split_k) {
+  const int64_t idx4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 4 columns per thread
+  if (idx4 * 4 >= M * N) return;
+  const int64_t m = (idx4 * 4) / N, n = (idx4 * 4) % N;
+  f32x4 s = splitk_sum4(part + m * N + n, M * N, split_k);
+  if (bias) {
+    const u32x2 b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(bias) + n);
+    s.x += lo_f32<T>(b.x); s.y += hi_f32<T>(b.x);
+    s.z += lo_f32<T>(b.y); s.w += hi_f32<T>(b.y);
+  }
+  u32x2 r;
+  r.x = pack2<T>(s.x, s.y);
+  r.y = pack2<T>(s.z, s.w);
+  *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(c) + m * ldc + n) = r;
+}
+template <typename T>
+inline void launch_splitk_reduce(const float* part, const void* bias, void* c, int64_t M, int64_t N, int64_t ldc,
+                                 int split_k, hipStream_t st) {
+  const int64_t n4 = M * N / 4;
+  hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, bias, c, M,
+                     N, ldc, split_k);
+}
+
+// byte offset of (row, 16-B slot) in a [rows][128 k] stage buffer of the weight-stream loops (w4_stream32.h,
+// dense.hip, moe_gemm.hip); the XOR swizzle makes the MFMA fragments conflict-free ds_read_b128
+__device__ __forceinline__ int stage_swz(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
+
+// ---- what the unquantised GEMMs' hosts share (dense.hip, moe_gemm.hip) ----
+constexpr int MI355X_CUS = 256;
+// Workgroups per row block: NW adjacent 32-column tiles each, or NW / 2 (gate, up) pairs under SiLU * mul
+inline int64_t gemm_col_groups(int64_t n_tiles, int nw, bool silu) {
+  return silu ? (n_tiles / 2 + nw / 2 - 1) / (nw / 2) : (n_tiles + nw - 1) / nw;
 }
 
 // RMSNorm row arithmetic shared by rms_norm_kernel (glue.hip) and the fused all-reduce

@@ -41,7 +41,6 @@ namespace slm {
 constexpr int LIN_RING = 3;   // weight / A register rings (chunks)
 constexpr int LIN_KC = 128;   // k per chunk
 constexpr int LIN_MAX_SPLIT = 16;
-constexpr int LIN_CUS = 256;  // MI355X
 
 struct LinearKParams {
   const char* a;
@@ -57,9 +56,6 @@ struct LinearKParams {
   int silu;
   int slice_chunk[LIN_MAX_SPLIT + 1];
 };
-
-// byte offset of (row, 16-B slot) in a stage buffer (w4_stream32.h's swizzle)
-__device__ __forceinline__ int lin_a_dst(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
 
 template <typename T, int RT, int NW>
 __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) {
@@ -110,7 +106,7 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
     int gr = row0 + row;
     gr = gr < p.M ? gr : p.M - 1;
     a_src[i] = p.a + 2 * ((int64_t)gr * p.lda + slot * 8) + kbase;
-    a_dst[i] = lin_a_dst(row, slot);
+    a_dst[i] = stage_swz(row, slot);
   }
   const char* wlane = p.w + 2 * (((int64_t)nt * 32 + mrow) * p.ldw) + kbase;
   const int a_row = mrow * 256;
@@ -297,27 +293,6 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
   }
 }
 
-// C[m, n] = T( sum_s part[s][m][n] + bias[n] ): w4_splitk_reduce_kernel's arithmetic (w4.hip), so that a
-// deferred consumer (splitk_sum4, the same order) and this launch give identical bits
-template <typename T>
-__global__ void __launch_bounds__(256) linear_splitk_reduce_kernel(const float* __restrict__ part,
-                                                                   const void* __restrict__ bias, void* __restrict__ c,
-                                                                   int64_t M, int64_t N, int64_t ldc, int split_k) {
-  const int64_t idx4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 4 columns per thread
-  if (idx4 * 4 >= M * N) return;
-  const int64_t m = (idx4 * 4) / N, n = (idx4 * 4) % N;
-  f32x4 s = splitk_sum4(part + m * N + n, M * N, split_k);
-  if (bias) {
-    const u32x2 b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(bias) + n);
-    s.x += lo_f32<T>(b.x); s.y += hi_f32<T>(b.x);
-    s.z += lo_f32<T>(b.y); s.w += hi_f32<T>(b.y);
-  }
-  u32x2 r;
-  r.x = pack2<T>(s.x, s.y);
-  r.y = pack2<T>(s.z, s.w);
-  *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(c) + m * ldc + n) = r;
-}
-
 // ---- the plan: a pure host function of (M, N, K, dtype, flags, bias != NULL, tuning table) ----
 struct LinearPlan {
   int rt, nw;
@@ -326,10 +301,6 @@ struct LinearPlan {
   int slice_chunk[LIN_MAX_SPLIT + 1];
   uint64_t lds_bytes, ws_bytes;
 };
-
-static int64_t lin_col_groups(int64_t n_tiles, int nw, bool silu) {
-  return silu ? (n_tiles / 2 + nw / 2 - 1) / (nw / 2) : (n_tiles + nw - 1) / nw;
-}
 
 static int plan_linear(const slm_linear_args* a, LinearPlan* pl) {
   if (!a) return SLM_ERR_INVALID_ARG;
@@ -359,16 +330,16 @@ static int plan_linear(const slm_linear_args* a, LinearPlan* pl) {
   // four-wave workgroups on a deeper K split by 15-25 %: fewer slabs, and more workgroups to place per CU
   const int narrowest = rt > (silu ? 2 : 1) ? rt : (silu ? 2 : 1);
   int nw = narrowest;
-  while (nw < 4 && row_blocks * lin_col_groups(n_tiles, nw, silu) > 2 * LIN_CUS) nw <<= 1;
+  while (nw < 4 && row_blocks * gemm_col_groups(n_tiles, nw, silu) > 2 * MI355X_CUS) nw <<= 1;
   const int nw_knob = tune_get(TUNE_LINEAR_NW, 0);
   if (nw_knob == 1 || nw_knob == 2 || nw_knob == 4) nw = nw_knob > narrowest ? nw_knob : narrowest;
-  const int64_t col_groups = lin_col_groups(n_tiles, nw, silu);
+  const int64_t col_groups = gemm_col_groups(n_tiles, nw, silu);
   if (col_groups >= ((int64_t)1 << 31)) return SLM_ERR_UNSUPPORTED;
 
   // K split: the largest that keeps the grid within the CUs and >= 4 chunks per slice; SiLU never splits
   int split = 1;
   if (!silu) {
-    const int64_t by_grid = LIN_CUS / (row_blocks * col_groups);
+    const int64_t by_grid = MI355X_CUS / (row_blocks * col_groups);
     split = (int)(by_grid < by_depth ? by_grid : by_depth);
     if (split < 1) split = 1;
     const int sk_knob = tune_get(TUNE_LINEAR_SPLITK, 0);
@@ -472,10 +443,8 @@ SLM_API int slm_linear(const slm_linear_args* a, void* stream) {
   dispatch_dtype(a->dtype, [&](auto t) { launch_linear_form<decltype(t)>(kp, pl.rt, pl.nw, grid, st); });
   int lrc = hip_check_launch();
   if (lrc != SLM_OK || pl.split_k == 1 || defer) return lrc;
-  const int64_t n4 = a->M * a->N / 4;
   dispatch_dtype(a->dtype, [&](auto t) {
-    hipLaunchKernelGGL(linear_splitk_reduce_kernel<decltype(t)>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                       kp.part, a->bias, a->c, a->M, a->N, a->ldc, pl.split_k);
+    launch_splitk_reduce<decltype(t)>(kp.part, a->bias, a->c, a->M, a->N, a->ldc, pl.split_k, st);
   });
   return hip_check_launch();
 }

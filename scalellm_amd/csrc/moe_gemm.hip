@@ -61,9 +61,6 @@ struct MoeDenseKParams {
   int silu;
 };
 
-// byte offset of (row, 16-B slot) in a stage buffer (w4_stream32.h's swizzle)
-__device__ __forceinline__ int mg_a_dst(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
-
 template <typename T, int NW>
 __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseKParams p) {
   typedef typename Mfma<T>::frag frag_t;
@@ -111,7 +108,7 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
     const int fi = blk[row];
     const int64_t ar = (unsigned)fi < (unsigned)p.n_flat ? fi / p.a_div : 0;  // padding: a clamped row
     a_src[i] = abase + 2 * (ar * p.lda + slot * 8);
-    a_dst[i] = mg_a_dst(row, slot);
+    a_dst[i] = stage_swz(row, slot);
   }
   // the expert base is a 64-bit pointer, offsets inside an expert 32-bit
   const char* wlane = p.w + (int64_t)e * p.w_stride + 2 * (((int64_t)nt * 32 + mrow) * p.ldw);
@@ -259,12 +256,9 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
 // per CU, otherwise the narrowest.  SiLU * mul pairs waves, so it never goes below 2.  Decided from the
 // arguments alone: the same call always launches the same shape.
 static int moe_gemm_waves(int64_t max_blocks, int64_t n_tiles, bool silu) {
-  constexpr int64_t CUS = 256;  // MI355X
   const int narrowest = silu ? 2 : 1;
-  for (int nw = 4; nw > narrowest; nw >>= 1) {
-    const int64_t per_block = silu ? (n_tiles / 2 + nw / 2 - 1) / (nw / 2) : (n_tiles + nw - 1) / nw;
-    if (max_blocks * per_block >= CUS) return nw;
-  }
+  for (int nw = 4; nw > narrowest; nw >>= 1)
+    if (max_blocks * gemm_col_groups(n_tiles, nw, silu) >= MI355X_CUS) return nw;
   return narrowest;
 }
 
@@ -308,7 +302,7 @@ SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) {
   if (a->N * a->ldw * 2 >= ((int64_t)1 << 32)) return SLM_ERR_UNSUPPORTED;  // a strided expert: still < 4 GiB
   const int64_t n_tiles = a->N / 32;
   const int nw = moe_gemm_waves(a->max_blocks, n_tiles, silu);
-  const int64_t n_nblocks = silu ? (n_tiles / 2 + nw / 2 - 1) / (nw / 2) : (n_tiles + nw - 1) / nw;
+  const int64_t n_nblocks = gemm_col_groups(n_tiles, nw, silu);
   const int64_t grid = (int64_t)a->max_blocks * n_nblocks;
   if (grid >= ((int64_t)1 << 31)) return SLM_ERR_UNSUPPORTED;
 

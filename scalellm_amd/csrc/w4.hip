@@ -141,28 +141,7 @@ __global__ void __launch_bounds__(256) w4_permute_cols_kernel(const uint16_t* __
     out[m * K + k] = perm[k] >= 0 ? a[m * lda + perm[k]] : (uint16_t)0;  // < 0: padding column (+0.0)
 }
 
-// C[m, n] = T( sum_s part[s][m][n] + bias[n] )
-template <typename T>
-__global__ void __launch_bounds__(256) w4_splitk_reduce_kernel(const float* __restrict__ part,
-                                                               const void* __restrict__ bias,
-                                                               void* __restrict__ c, int64_t M,
-                                                               int64_t N, int64_t ldc, int split_k) {
-  const int64_t idx4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 4 columns per thread
-  if (idx4 * 4 >= M * N) return;
-  const int64_t m = (idx4 * 4) / N, n = (idx4 * 4) % N;
-  f32x4 s = splitk_sum4(part + m * N + n, M * N, split_k);
-  if (bias) {
-    const u32x2 b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(bias) + n);
-    s.x += lo_f32<T>(b.x); s.y += hi_f32<T>(b.x);
-    s.z += lo_f32<T>(b.y); s.w += hi_f32<T>(b.y);
-  }
-  u32x2 r;
-  r.x = pack2<T>(s.x, s.y);
-  r.y = pack2<T>(s.z, s.w);
-  *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(c) + m * ldc + n) = r;
-}
-
-// SLM_W4_SILU_MUL with split-K: C[m, i] = T( silu(g) * u ), g / u = T( sum_s part[s][m][col] + bias )
+// the plain split-K reduce is common.h's splitk_reduce_kernel.  SLM_W4_SILU_MUL with split-K: C[m, i] = T( silu(g) * u ), g / u = T( sum_s part[s][m][col] + bias )
 // at the gate / up columns of output column i (packed tile pair 2j, 2j+1; N = packed width)
 template <typename T>
 __global__ void __launch_bounds__(256) w4_splitk_reduce_silu_kernel(
@@ -366,16 +345,15 @@ static int gemm_impl(const slm_w4_gemm_args* a, const slm_w4_norm_prologue* np, 
   rc = hip_check_launch();
   if (rc != SLM_OK) return rc;
   if (pl.split_k > 1 && !((a->flags & SLM_W4_DEFER_REDUCE) && !a->bias)) {
-    const int64_t n4 = a->M * (silu ? a->N / 2 : a->N) / 4;
-    const dim3 grid((unsigned)((n4 + 255) / 256)), blk(256);
     dispatch_dtype(a->dtype, [&](auto t) {
       using T = decltype(t);
-      if (silu)
-        hipLaunchKernelGGL(w4_splitk_reduce_silu_kernel<T>, grid, blk, 0, st, kp.part, a->bias, a->c, a->M, a->N,
-                           a->ldc, pl.split_k);
-      else
-        hipLaunchKernelGGL(w4_splitk_reduce_kernel<T>, grid, blk, 0, st, kp.part, a->bias, a->c, a->M, a->N, a->ldc,
-                           pl.split_k);
+      if (silu) {
+        const int64_t n4 = a->M * (a->N / 2) / 4;
+        hipLaunchKernelGGL(w4_splitk_reduce_silu_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                           kp.part, a->bias, a->c, a->M, a->N, a->ldc, pl.split_k);
+      } else {
+        launch_splitk_reduce<T>(kp.part, a->bias, a->c, a->M, a->N, a->ldc, pl.split_k, st);
+      }
     });
     rc = hip_check_launch();
   }

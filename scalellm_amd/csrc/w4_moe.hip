@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256, 2) w4a16_moe_gemm_kernel(const MoeGemmKPa
     const int fi = blk[row];
     const int64_t ar = (unsigned)fi < (unsigned)p.n_flat ? fi / p.a_div : 0;  // padding: a clamped row
     a_src[i] = abase + 2 * (ar * p.lda + slot * 8);
-    a_dst[i] = s32_a_dst(row, slot);
+    a_dst[i] = stage_swz(row, slot);
   }
 
   // the expert base is a 64-bit pointer, offsets inside an expert 32-bit

@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(256, 2) w4a16_gemm_small_kernel(const GemmKPar
     const int64_t m = m0 + row;
     const int64_t mc = m < p.M ? m : p.M - 1;
     a_src[i] = abase + 2 * (mc * p.lda + slot * 8);
-    a_dst[i] = s32_a_dst(row, slot);
+    a_dst[i] = stage_swz(row, slot);
   }
   const char* wlane = reinterpret_cast<const char*>(p.wq + (nt * 64 + lane) * 4);
   const char* szlane = reinterpret_cast<const char*>(p.sz + nt * 32 + (lane & 31));

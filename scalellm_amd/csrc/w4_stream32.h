@@ -19,13 +19,13 @@ constexpr size_t S32_LDS_BYTES = S32_STAGES * S32_STAGE_BYTES;
 
 // A chunk's A tile is 32 rows x 16 slots of 16 B (8 k-values); thread tid stages the two (row, slot) pairs
 // idx = tid + 256 * i, row = idx >> 4, slot = idx & 15: the caller turns the row into a source pointer and
-// takes the byte offset inside a stage buffer from here (XOR swizzle: conflict-free ds_read_b128 fragments)
-__device__ __forceinline__ int s32_a_dst(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
-
+// takes the byte offset inside a stage buffer from common.h's stage_swz (XOR swizzle: conflict-free
+// ds_read_b128 fragments).
+//
 // Streams chunks [c0, c1) (c1 > c0) and returns the wave's 32 x 32 accumulator tile in the C/D layout of
 // the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
 //   a_src[i]  this thread's two A source pointers at chunk 0 (16 B each per chunk, + 256 B per chunk)
-//   a_dst[i]  s32_a_dst of the same two (row, slot) pairs
+//   a_dst[i]  stage_swz of the same two (row, slot) pairs
 //   smem      S32_LDS_BYTES of dynamic LDS; free for the caller's epilogue after the return (the last
 //             iteration ends in a barrier)
 //   wlane / szlane  per-lane bases of the wave's column tile in the packed weights / the scale table
