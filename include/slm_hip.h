@@ -1239,6 +1239,60 @@ SLM_API int slm_unpermute_rows(void* out, const void* permuted, const int32_t* r
                                int32_t probs_dtype, int64_t n_tokens, int32_t n_maps, int64_t dim,
                                int64_t permuted_rows, int32_t dtype, void* stream);
 
+/* ========================================================================== */
+/* 15. fp8 (e4m3) weight-only linear: W8A16 over checkpoint-layout weights    */
+/*    replaces  marlin::fp8_gemm  src/kernels/quantization/marlin.h:39-43     */
+/*    (which reads a Marlin-repacked B; this entry reads the checkpoint       */
+/*    tensor as it is, like section 13)                                       */
+/*      acc_s[m, n] = sum over k in K slice s of A[m, k] * e4m3(W[n, k])      */
+/*                    (e4m3 -> T is exact; fp32 MFMA accumulation, the order  */
+/*                    of section 13 under the same plan)                      */
+/*      y_s[m, n]   = acc_s[m, n] * w_scale[n]     ONE fp32 multiply, never   */
+/*                    contracted into the bias add                            */
+/*      C[m, n]     = T( y_0 + y_1 + ... (slice order) + bias[n] )   ONE      */
+/*                    rounding to T                                           */
+/*    W is [N, K] BYTES in OCP e4m3fn (torch.float8_e4m3fn; not the fnuz      */
+/*    form), k-contiguous, never prepacked; row stride ldw in elements =      */
+/*    bytes, ldw >= K, ldw % 16 == 0, base 16-byte aligned.  w_scale is fp32  */
+/*    [N] (16-byte aligned), NULL = 1.0: one scale per output channel; the    */
+/*    host expands a per-tensor scale (the q | k | v or gate | up shards of a */
+/*    fused layer each bring their own).  No group / block scale and no       */
+/*    activation scale (a checkpoint's input_scale is not used: W8A16).       */
+/*    The two NaN codes 0x7F / 0xFF convert to NaN of T (the hardware         */
+/*    converter propagates them) and poison their output column like a NaN    */
+/*    weight of section 13 would; checkpoints do not hold them.               */
+/*    A, bias, C are T (f16 / bf16), lda / ldc as in section 13.  Shapes,     */
+/*    error codes, "all validation before any launch", M == 0, the launch     */
+/*    shape, the K slices (whole 128-deep chunks, the K % 128 tail with the   */
+/*    last), the workspace ([split_k][M][N] fp32 slabs, here ALREADY scaled,  */
+/*    so the reduce launch and every deferred consumer of section 13 work     */
+/*    unchanged) and the flags (SLM_LINEAR_*, the same bits) are section      */
+/*    13's.  With SLM_LINEAR_SILU_MUL  g = T(y + bias), u = T(y' + bias'):    */
+/*    the bits of the plain call followed by slm_silu_mul.                    */
+/*    Knobs: SLM_LINEAR_SPLITK / _RT / _NW force the form of this entry too;  */
+/*    it has none of its own (csrc/dense_fp8.hip).                            */
+/* ========================================================================== */
+typedef struct slm_fp8_linear_args {
+  const void* a;        /* [M, K] T, row stride lda                           */
+  const void* w;        /* [N, K] e4m3fn bytes, row stride ldw                */
+  const void* bias;     /* [N] T or NULL                                      */
+  void* c;              /* [M, N] T ([M, N/2] with SLM_LINEAR_SILU_MUL), row stride ldc */
+  int64_t M, K, N;
+  int64_t lda, ldw, ldc;
+  int32_t dtype;        /* of a, bias and c                                   */
+  int32_t flags;        /* SLM_LINEAR_* bits, 0 = none                        */
+  void* workspace;      /* split-K slabs                                      */
+  size_t workspace_bytes;
+  const float* w_scale; /* [N] fp32 or NULL (= 1.0); everything above is slm_linear_args, field for field */
+} slm_fp8_linear_args;
+
+/* As slm_linear_plan / _workspace_bytes / _deferred_splits / slm_linear (section 13) for the fp8 entry; the plan is
+ * a pure host function and works without a GPU. */
+SLM_API int slm_fp8_linear_plan(const slm_fp8_linear_args* a, slm_linear_plan_info* out);
+SLM_API size_t slm_fp8_linear_workspace_bytes(const slm_fp8_linear_args* a);
+SLM_API int32_t slm_fp8_linear_deferred_splits(const slm_fp8_linear_args* a);
+SLM_API int slm_fp8_linear(const slm_fp8_linear_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,11 @@ class LinearArgs(C.Structure):
     ]
 
 
+class Fp8LinearArgs(C.Structure):
+    """struct slm_fp8_linear_args (include/slm_hip.h section 15): slm_linear_args, field for field, plus w_scale."""
+    _fields_ = LinearArgs._fields_ + [("w_scale", C.c_void_p)]
+
+
 class LinearPlanInfo(C.Structure):
     """struct slm_linear_plan_info (include/slm_hip.h section 13)."""
     _fields_ = [
@@ -369,6 +374,10 @@ def lib() -> C.CDLL:
         ("slm_linear_workspace_bytes", C.c_size_t, [C.POINTER(LinearArgs)]),
         ("slm_linear_deferred_splits", C.c_int32, [C.POINTER(LinearArgs)]),
         ("slm_linear_plan", C.c_int, [C.POINTER(LinearArgs), C.POINTER(LinearPlanInfo)]),
+        ("slm_fp8_linear", C.c_int, [C.POINTER(Fp8LinearArgs), C.c_void_p]),
+        ("slm_fp8_linear_workspace_bytes", C.c_size_t, [C.POINTER(Fp8LinearArgs)]),
+        ("slm_fp8_linear_deferred_splits", C.c_int32, [C.POINTER(Fp8LinearArgs)]),
+        ("slm_fp8_linear_plan", C.c_int, [C.POINTER(Fp8LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_soft_cap", C.c_int,
          [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
         ("slm_permute_index_map", C.c_int,

@@ -742,6 +742,44 @@ torch::Tensor linear(const torch::Tensor& input, const torch::Tensor& weight, co
   return c;
 }
 
+torch::Tensor fp8_linear(const torch::Tensor& input, const torch::Tensor& weight, const torch::Tensor& w_scale,
+                         const std::optional<torch::Tensor>& bias, bool silu_mul) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  const auto a = input.reshape({-1, input.size(-1)});
+  TORCH_CHECK(weight.dim() == 2 && weight.stride(1) == 1 && a.size(1) == weight.size(1) && a.stride(1) == 1 &&
+              weight.scalar_type() == torch::kFloat8_e4m3fn,
+              "slm::fp8_linear: input [.., K] and a float8_e4m3fn weight [N, K]");
+  const int64_t N = weight.size(0);
+  torch::Tensor c = torch::empty({a.size(0), silu_mul ? N / 2 : N}, a.options());
+  slm_fp8_linear_args g{};
+  g.a = a.const_data_ptr();
+  g.w = weight.const_data_ptr();
+  if (w_scale.defined()) {
+    TORCH_CHECK(w_scale.numel() == N && w_scale.is_contiguous() && w_scale.scalar_type() == torch::kFloat,
+                "slm::fp8_linear: w_scale must be a contiguous fp32 [N] tensor");
+    g.w_scale = w_scale.const_data_ptr<float>();
+  }
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->numel() == N && bias->is_contiguous() && bias->scalar_type() == a.scalar_type());
+    g.bias = bias->const_data_ptr();
+  }
+  g.c = c.mutable_data_ptr();
+  g.M = a.size(0); g.K = a.size(1); g.N = N;
+  g.lda = a.stride(0); g.ldw = weight.stride(0); g.ldc = c.stride(0);
+  g.dtype = dtype_code(a);
+  g.flags = silu_mul ? SLM_LINEAR_SILU_MUL : 0;
+  if (g.M == 0) return c;
+  const size_t need = slm_fp8_linear_workspace_bytes(&g);
+  torch::Tensor ws;
+  if (need > 0) {
+    ws = workspace_for(a, need);
+    g.workspace = ws.mutable_data_ptr();
+    g.workspace_bytes = ws.nbytes();
+  }
+  check(slm_fp8_linear(&g, current_stream(a)), "slm_fp8_linear");
+  return c;
+}
+
 torch::Tensor W4Linear::forward(const torch::Tensor& input, const std::optional<torch::Tensor>& bias,
                                 std::optional<torch::Tensor> out) const {
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());

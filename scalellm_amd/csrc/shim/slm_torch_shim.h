@@ -216,6 +216,11 @@ class W4Linear {
 torch::Tensor linear(const torch::Tensor& input, const torch::Tensor& weight, const std::optional<torch::Tensor>& bias,
                      bool silu_mul = false);
 
+// W8A16 on fp8 weights (include/slm_hip.h section 15, slm_fp8_linear): weight [N, K] float8_e4m3fn in checkpoint
+// layout, streamed as bytes; w_scale fp32 [N] (undefined = 1.0) multiplies the fp32 sums; the rest as linear().
+torch::Tensor fp8_linear(const torch::Tensor& input, const torch::Tensor& weight, const torch::Tensor& w_scale,
+                         const std::optional<torch::Tensor>& bias, bool silu_mul = false);
+
 // The reference's abstract process group, same five virtuals with the same meaning
 // (src/model_parallel/process_group.h:10-60): whatever drives llm::ProcessGroup* -- the parallel
 // layers, Worker::process_group_test -- drives this.

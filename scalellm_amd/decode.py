@@ -6,7 +6,9 @@ all-reduce) -> RMSNorm -> gate_up -> SiLU*mul -> down (row-parallel, all-reduce)
 lm_head (column-parallel, gathered) and greedy argmax.  All four linears are int4 (AWQ or GPTQ)
 -- the reference snapshot leaves fused qkv / gate_up un-quantised; here the whole
 layer is int4 -- or, with quant_method="none", all four are unquantised f16 / bf16 weights in
-checkpoint layout (layers.ColumnParallelLinear / RowParallelLinear over slm_linear).  Weights are
+checkpoint layout (layers.ColumnParallelLinear / RowParallelLinear over slm_linear), or, with
+quant_method="fp8", those weights quantised per output channel to e4m3 (layers.ColumnParallelFp8Linear /
+RowParallelFp8Linear over slm_fp8_linear: W8A16).  Weights are
 synthetic (seeded); there is no checkpoint IO on this path.
 
 One process per GPU; TP shards heads (attention needs no collective) and the GEMMs' N / K.
@@ -24,8 +26,9 @@ from typing import List, Optional
 import torch
 
 from . import kernels
-from .layers import (Attention, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache,
-                     uniform_kv_hint, QuantArgs, RowParallelLinear, RowParallelQLinear)
+from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler,
+                     InputParameters, KVCache, uniform_kv_hint, QuantArgs, RowParallelFp8Linear, RowParallelLinear,
+                     RowParallelQLinear)
 from .model_parallel import ParallelArgs
 
 
@@ -174,8 +177,11 @@ class LlamaDecodeStep:
         pa = parallel_args or ParallelArgs()
         # quant_method "none": unquantised weights [N, K] of `dtype` (randn * 0.02 from the common seed), the four
         # linears are layers.{Column,Row}ParallelLinear over slm_linear; everything else of the step is shared
-        dense = quant_method == "none"
-        self.dense, self.weight_bits = dense, 16 if dense else 4
+        # quant_method "fp8": that same checkpoint quantised per output channel to e4m3 (kernels.quantize_fp8_weight),
+        # the four linears are layers.{Column,Row}ParallelFp8Linear over slm_fp8_linear; the rest is the dense path
+        self.fp8 = quant_method == "fp8"
+        dense = quant_method in ("none", "fp8")
+        self.dense, self.weight_bits = dense, 8 if self.fp8 else 16 if dense else 4
         # fuse_silu: the merged gate_up weight is packed paired and SiLU*mul runs in the GEMM
         # epilogue (identical bits; False keeps the separate kernels.silu_and_mul launch)
         fuse_silu = fuse_silu and (shape.intermediate // pa.world_size) % 32 == 0
@@ -309,18 +315,39 @@ class LlamaDecodeStep:
 
         def rows(w, ranges):
             return torch.cat([w[a:b] for a, b in ranges], dim=0).contiguous()
-        L["qkv"] = ColumnParallelLinear(H, qkv_n * tp, False, False, pa, dtype, dev)
-        L["o"] = RowParallelLinear(q_full, H, False, True, pa, dtype, dev)
-        L["gate_up"] = ColumnParallelLinear(H, 2 * inter, False, False, pa, dtype, dev,
-                                            act_mul="silu" if fuse_silu else None)
-        L["down"] = RowParallelLinear(inter, H, False, True, pa, dtype, dev)
-        shard = {"qkv": rows(draw(q_full + 2 * kv_full, H), [
-            (r * nh * D, (r + 1) * nh * D), (q_full + kv_head0 * D, q_full + (kv_head0 + nkv) * D),
-            (q_full + kv_full + kv_head0 * D, q_full + kv_full + (kv_head0 + nkv) * D)])}
-        shard["o"] = draw(H, q_full)[:, r * nh * D:(r + 1) * nh * D].contiguous()
-        shard["gate_up"] = rows(draw(2 * inter, H), [(r * inter // tp, (r + 1) * inter // tp),
-                                                     (inter + r * inter // tp, inter + (r + 1) * inter // tp)])
-        shard["down"] = draw(H, inter)[:, r * inter // tp:(r + 1) * inter // tp].contiguous()
+        Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if self.fp8 else \
+            (ColumnParallelLinear, RowParallelLinear)
+        L["qkv"] = Col(H, qkv_n * tp, False, False, pa, dtype, dev)
+        L["o"] = Row(q_full, H, False, True, pa, dtype, dev)
+        L["gate_up"] = Col(H, 2 * inter, False, False, pa, dtype, dev, act_mul="silu" if fuse_silu else None)
+        L["down"] = Row(inter, H, False, True, pa, dtype, dev)
+        qkv_rows = [(r * nh * D, (r + 1) * nh * D), (q_full + kv_head0 * D, q_full + (kv_head0 + nkv) * D),
+                    (q_full + kv_full + kv_head0 * D, q_full + kv_full + (kv_head0 + nkv) * D)]
+        gu_rows = [(r * inter // tp, (r + 1) * inter // tp), (inter + r * inter // tp, inter + (r + 1) * inter // tp)]
+        o_cols, down_cols = slice(r * nh * D, (r + 1) * nh * D), slice(r * inter // tp, (r + 1) * inter // tp)
+        if self.fp8:
+            # the FULL weights are quantised per output channel and cut afterwards (rows with their scales, columns
+            # under the whole scale), so every rank's shard is a slice of the one-rank model
+            def q(n, k):
+                return kernels.quantize_fp8_weight(draw(n, k))
+            w8, sc = q(q_full + 2 * kv_full, H)
+            q8 = {"qkv": (rows(w8.view(torch.uint8), qkv_rows).view(torch.float8_e4m3fn), rows(sc, qkv_rows))}
+            w8, sc = q(H, q_full)
+            q8["o"] = (w8[:, o_cols].contiguous(), sc)
+            w8, sc = q(2 * inter, H)
+            q8["gate_up"] = (rows(w8.view(torch.uint8), gu_rows).view(torch.float8_e4m3fn), rows(sc, gu_rows))
+            w8, sc = q(H, inter)
+            q8["down"] = (w8[:, down_cols].contiguous(), sc)
+            if keep_checkpoint:
+                self.ckpt.append({n: {"weight": w.clone(), "weight_scale": c.clone()} for n, (w, c) in q8.items()})
+            for name, (w, c) in q8.items():
+                L[name].load_shard(w, c)
+                L[name].verify_loaded_weights()
+            return
+        shard = {"qkv": rows(draw(q_full + 2 * kv_full, H), qkv_rows)}
+        shard["o"] = draw(H, q_full)[:, o_cols].contiguous()
+        shard["gate_up"] = rows(draw(2 * inter, H), gu_rows)
+        shard["down"] = draw(H, inter)[:, down_cols].contiguous()
         if keep_checkpoint:
             self.ckpt.append({n: {"weight": w.clone()} for n, w in shard.items()})
         for name, w in shard.items():
@@ -892,16 +919,18 @@ def hf_state_dict(step: "LlamaDecodeStep") -> dict:
           "lm_head.weight": step.lm_head.t()}   # [vocab, hidden] in a checkpoint
 
     if step.dense:   # plain *.weight tensors [out, in]: q | k | v and gate | up are row ranges of the fused shards
+        # (an fp8 step: float8_e4m3fn *.weight plus the fp32 per-channel *.weight_scale, cut by the same rows)
         for i, ck in enumerate(step.ckpt):
             pre = f"model.layers.{i}."
-            qkv, gu = ck["qkv"]["weight"], ck["gate_up"]["weight"]
-            sd[pre + "self_attn.q_proj.weight"] = qkv[:nq].contiguous()
-            sd[pre + "self_attn.k_proj.weight"] = qkv[nq:nq + nkv].contiguous()
-            sd[pre + "self_attn.v_proj.weight"] = qkv[nq + nkv:nq + 2 * nkv].contiguous()
-            sd[pre + "self_attn.o_proj.weight"] = ck["o"]["weight"]
-            sd[pre + "mlp.gate_proj.weight"] = gu[:inter].contiguous()
-            sd[pre + "mlp.up_proj.weight"] = gu[inter:].contiguous()
-            sd[pre + "mlp.down_proj.weight"] = ck["down"]["weight"]
+            for key in ck["qkv"]:   # "weight" (, "weight_scale")
+                qkv, gu = ck["qkv"][key], ck["gate_up"][key]
+                sd[pre + "self_attn.q_proj." + key] = qkv[:nq].contiguous()
+                sd[pre + "self_attn.k_proj." + key] = qkv[nq:nq + nkv].contiguous()
+                sd[pre + "self_attn.v_proj." + key] = qkv[nq + nkv:nq + 2 * nkv].contiguous()
+                sd[pre + "self_attn.o_proj." + key] = ck["o"][key]
+                sd[pre + "mlp.gate_proj." + key] = gu[:inter].contiguous()
+                sd[pre + "mlp.up_proj." + key] = gu[inter:].contiguous()
+                sd[pre + "mlp.down_proj." + key] = ck["down"][key]
             sd[pre + "input_layernorm.weight"] = step.layers[i]["in_norm"]
             sd[pre + "post_attention_layernorm.weight"] = step.layers[i]["post_norm"]
         return sd

@@ -817,6 +817,28 @@ def linear_plan(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Op
     return info
 
 
+def _run_linear(entry: str, g, dev: torch.device, defer_reduce: bool) -> DeferredPartials:
+    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear (`entry`) over the argument block g"""
+    L = _lib.lib()
+    if g.M == 0:
+        return DeferredPartials()
+    deferred = getattr(L, entry + "_deferred_splits")(C.byref(g)) if defer_reduce else 0
+    need = getattr(L, entry + "_workspace_bytes")(C.byref(g))
+    ws = None
+    if need:
+        # deferred slabs live in their own buffer (gptq_gemm: nothing else's scratch may overwrite them)
+        ws = _grow(_deferred_ws, need, dev, "deferred split-K buffer") if deferred \
+            else reserve_workspace(need, dev)
+        g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(getattr(L, entry)(C.byref(g), _stream()), entry)
+    if deferred:
+        key = _dev_key(dev)
+        gen = _deferred_gen.get((key, 0), 0) + 1
+        _deferred_gen[(key, 0)] = gen  # any older handle on this buffer is now stale
+        return DeferredPartials(g.workspace, deferred, g.M * g.N, key, gen, ws, 0)
+    return DeferredPartials()
+
+
 def linear(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Optional[torch.Tensor] = None,
            defer_reduce: bool = False, silu_mul: bool = False) -> DeferredPartials:
     """F::linear on unquantised weights (parallel_linear.cpp): C[M, N] = A[M, K] . W[N, K]^T (+ bias), fp32
@@ -829,25 +851,83 @@ def linear(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Optiona
 
     silu_mul: rows [0, N/2) of `weight` are the gate, [N/2, N) the up projection and `c` is [M, N/2] =
     silu(gate) * up -- the bits of linear() followed by silu_and_mul()."""
-    L = _lib.lib()
-    g = _linear_args(a, weight, c, bias, defer_reduce, silu_mul)
-    if g.M == 0:
-        return DeferredPartials()
-    deferred = L.slm_linear_deferred_splits(C.byref(g)) if defer_reduce else 0
-    need = L.slm_linear_workspace_bytes(C.byref(g))
-    ws = None
-    if need:
-        # deferred slabs live in their own buffer (gptq_gemm: nothing else's scratch may overwrite them)
-        ws = _grow(_deferred_ws, need, a.device, "deferred split-K buffer") if deferred \
-            else reserve_workspace(need, a.device)
-        g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(L.slm_linear(C.byref(g), _stream()), "slm_linear")
-    if deferred:
-        key = _dev_key(a.device)
-        gen = _deferred_gen.get((key, 0), 0) + 1
-        _deferred_gen[(key, 0)] = gen  # any older handle on this buffer is now stale
-        return DeferredPartials(g.workspace, deferred, g.M * g.N, key, gen, ws, 0)
-    return DeferredPartials()
+    return _run_linear("slm_linear", _linear_args(a, weight, c, bias, defer_reduce, silu_mul), a.device, defer_reduce)
+
+
+# ---------------------------------------------------------------------------------------
+# fp8 (e4m3) weight-only linear: slm_hip.h section 15
+# ---------------------------------------------------------------------------------------
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_fp8_weight(w: torch.Tensor, per: str = "channel"):
+    """Load-time quantisation of a weight [N, K] to OCP e4m3fn (torch ops; nothing on the hot path):
+    (w8 [N, K] float8_e4m3fn, scale fp32 [N]) with scale = amax / 448 per output channel ("channel") or of the
+    whole tensor, repeated ("tensor"); an all-zero row (tensor) gets scale 1.  w ~ w8.float() * scale[:, None]."""
+    if per not in ("channel", "tensor"):
+        raise ValueError(f"per must be 'channel' or 'tensor', not {per!r}")
+    if w.dim() != 2:
+        raise ValueError("quantize_fp8_weight takes a 2-D weight [N, K]")
+    wf = w.float()
+    amax = wf.abs().amax(dim=1) if per == "channel" else wf.abs().amax().expand(w.size(0))
+    scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax)).contiguous()
+    w8 = (wf / scale[:, None]).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    return w8, scale
+
+
+def _fp8_linear_args(a, w8, w_scale, c, bias, defer_reduce: bool, silu_mul: bool) -> "_lib.Fp8LinearArgs":
+    _require_gpu(a, w8, w_scale, c, bias)
+    if silu_mul and defer_reduce:
+        raise SlmError("silu_mul and defer_reduce cannot be combined")
+    if w8.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise SlmError(f"fp8_linear takes float8_e4m3fn weights (or their bytes), not {w8.dtype}")
+    if a.dim() != 2 or c.dim() != 2 or w8.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1 or w8.stride(1) != 1:
+        raise SlmError("A [M, K], W [N, K] and C [M, N] must be 2-D with contiguous rows")
+    N, K = w8.shape
+    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a.size(0) != c.size(0):
+        raise SlmError("fp8_linear shape mismatch")
+    if c.dtype != a.dtype or (bias is not None and bias.dtype != a.dtype):
+        raise SlmError("activation / bias / output dtypes must match")
+    if bias is not None and (bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous()):
+        raise SlmError("bias must be a contiguous [N] tensor")
+    if w_scale is not None and (w_scale.dtype != torch.float32 or w_scale.dim() != 1 or w_scale.numel() != N or
+                                not w_scale.is_contiguous()):
+        raise SlmError("w_scale must be a contiguous fp32 [N] tensor (expand a per-tensor scale on the host)")
+    g = _lib.Fp8LinearArgs()
+    g.a, g.w, g.c = a.data_ptr(), w8.data_ptr(), c.data_ptr()
+    g.bias = bias.data_ptr() if bias is not None else None
+    g.w_scale = w_scale.data_ptr() if w_scale is not None else None
+    g.M, g.K, g.N = a.size(0), K, N
+    g.lda, g.ldw, g.ldc = a.stride(0), w8.stride(0), c.stride(0)
+    g.dtype = _dtype_code(a)
+    g.flags = _lib.SLM_LINEAR_SHARES_CHIP if _chip_flag() else 0
+    if silu_mul:
+        g.flags |= _lib.SLM_LINEAR_SILU_MUL
+    if defer_reduce:
+        g.flags |= _lib.SLM_LINEAR_DEFER_REDUCE
+    g.workspace, g.workspace_bytes = None, 0
+    return g
+
+
+def fp8_linear_plan(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None, defer_reduce: bool = False,
+                    silu_mul: bool = False) -> "_lib.LinearPlanInfo":
+    """The launch fp8_linear() would give these very arguments now (slm_fp8_linear_plan); a host-side query."""
+    g = _fp8_linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul)
+    info = _lib.LinearPlanInfo()
+    check(_lib.lib().slm_fp8_linear_plan(C.byref(g), C.byref(info)), "slm_fp8_linear_plan")
+    return info
+
+
+def fp8_linear(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
+               bias: Optional[torch.Tensor] = None, defer_reduce: bool = False,
+               silu_mul: bool = False) -> DeferredPartials:
+    """W8A16 linear (marlin::fp8_gemm's job over the checkpoint tensor): C[M, N] = T((A[M, K] . e4m3(W8[N, K])^T) *
+    w_scale[N] + bias), fp32 accumulate, the scale applied to the fp32 sum, one rounding.  `w8` is the checkpoint's
+    float8_e4m3fn weight [N, K] (rows contiguous, row stride a multiple of 16), streamed as bytes and converted in
+    registers; `w_scale` fp32 [N] or None (1.0).  defer_reduce, silu_mul and the returned handle: as linear()."""
+    return _run_linear("slm_fp8_linear", _fp8_linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul), a.device,
+                       defer_reduce)
 
 
 # ---------------------------------------------------------------------------------------

@@ -535,6 +535,131 @@ class RowParallelLinear(_LinearBase):
                             defer_splitk=defer_splitk and not self.has_bias)
 
 
+# ---------------------------------------------------------------------------------------
+# fp8 (e4m3) weight-only linear layers: W8A16 over slm_fp8_linear
+# ---------------------------------------------------------------------------------------
+class _Fp8LinearMixin:
+    """What the two fp8 classes add to _LinearBase: `weight` is the checkpoint's float8_e4m3fn tensor, kept as bytes
+    and never converted (kernels.fp8_linear streams it as it is); `weight_scale` arrives 0-d, [1], [N] or [N, 1]
+    in any float dtype and is kept as fp32 [local_out], one scale per output channel (a per-tensor scale is
+    expanded, in a fused load per shard).  An `input_scale` key is ignored: activations stay f16 / bf16.  A weight
+    of any other dtype is an error -- quantising is the checkpoint's job (kernels.quantize_fp8_weight), not a
+    side effect of loading."""
+
+    weight_scale: Optional[torch.Tensor] = None
+
+    def _set(self, name: str, t: torch.Tensor) -> None:
+        if name == "weight":
+            if t.dtype != torch.float8_e4m3fn:
+                raise TypeError(f"fp8 linear: weight must be float8_e4m3fn, not {t.dtype} (quantize_fp8_weight "
+                                "makes one; nothing is quantised on load)")
+            if tuple(t.shape) != (self.local_out, self.local_in):
+                raise ValueError(f"weight size mismatch: {tuple(t.shape)} vs {(self.local_out, self.local_in)}")
+            self.weight = t.to(self.device).contiguous()
+        elif name == "weight_scale":
+            if tuple(t.shape) != (self.local_out,):
+                raise ValueError(f"weight_scale size mismatch: {tuple(t.shape)} vs {(self.local_out,)}")
+            self.weight_scale = t.to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            super()._set(name, t)
+
+    @staticmethod
+    def _channel_scale(t: torch.Tensor, rows: int, what: str) -> torch.Tensor:
+        """0-d / [1] (per tensor) or [rows] / [rows, 1] (per channel) -> fp32 [rows]"""
+        if not t.is_floating_point():
+            raise TypeError(f"{what} must be a float tensor, not {t.dtype}")
+        flat = t.reshape(-1).to(torch.float32)
+        if flat.numel() == 1:
+            return flat.expand(rows)
+        if flat.numel() != rows or t.dim() > 2 or (t.dim() == 2 and t.size(1) != 1):
+            raise ValueError(f"{what} size mismatch: {tuple(t.shape)} for {rows} output channels")
+        return flat
+
+    def _load_scale(self, sd: Dict[str, torch.Tensor], full_rows: int, dim: int) -> None:
+        if "weight_scale" not in sd:
+            return
+        if self.weight_scale is not None:
+            raise RuntimeError("weight_scale is loaded twice")
+        full = self._channel_scale(sd["weight_scale"], full_rows, "weight_scale")
+        self._set("weight_scale", self._shard(full, dim, "weight_scale"))
+
+    def load_shard(self, weight: torch.Tensor, weight_scale: torch.Tensor,  # noqa: D401
+                   bias: Optional[torch.Tensor] = None) -> None:
+        """THIS rank's shard, already cut: float8_e4m3fn weight [local_out, local_in] and its scale
+        (per tensor or [local_out])."""
+        if self.weight_scale is not None:
+            raise RuntimeError("weight_scale is loaded twice")
+        super().load_shard(weight, bias)
+        self._set("weight_scale", self._channel_scale(weight_scale, self.local_out, "weight_scale"))
+
+    def verify_loaded_weights(self, prefix: str = "") -> None:
+        super().verify_loaded_weights(prefix)
+        if self.weight_scale is None:
+            raise RuntimeError(f"weight_scale is not loaded for {prefix}weight_scale")
+
+    def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor],
+                defer_splitk: bool = False) -> torch.Tensor:
+        self.verify_loaded_weights()
+        x2 = x.reshape(-1, x.size(-1))
+        n_out = self.local_out // 2 if self.paired else self.local_out
+        if out is None:
+            out = torch.empty(x2.size(0), n_out, dtype=x.dtype, device=x.device)
+        self.deferred = kernels.fp8_linear(x2, self.weight, self.weight_scale, out, bias,
+                                           defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
+        self.deferred_splits = int(self.deferred)
+        return out
+
+
+class ColumnParallelFp8Linear(_Fp8LinearMixin, ColumnParallelLinear):
+    """ColumnParallelLinear over an fp8 checkpoint: weight AND weight_scale are sharded on dim 0.  A fused load
+    (prefixes=[...]) concatenates the shards and expands each shard's own scale over its rows, so q | k | v and
+    gate | up keep their per-tensor scales."""
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        if not prefixes:
+            self._load_one(sd, "weight", 0)
+            self._load_scale(sd, self.out_features, 0)
+            if self.has_bias:
+                self._load_one(sd, "bias", 0)
+            return
+        # per prefix: (weight shard as bytes, scale over the shard's rows); both tensors of a prefix come together
+        parts = self._parts.setdefault("weight", [None] * len(prefixes))
+        for i, p in enumerate(prefixes):
+            if p + "weight" not in sd:
+                if p + "weight_scale" in sd:
+                    raise RuntimeError(f"{p}weight_scale arrives without {p}weight")
+                continue
+            if parts[i] is not None or self.weight is not None:
+                raise RuntimeError(f"{p}weight is loaded twice")
+            w = sd[p + "weight"]
+            if w.dtype != torch.float8_e4m3fn:
+                raise TypeError(f"fp8 linear: {p}weight must be float8_e4m3fn, not {w.dtype}")
+            if p + "weight_scale" not in sd:
+                raise RuntimeError(f"{p}weight arrives without {p}weight_scale")
+            scale = self._channel_scale(sd[p + "weight_scale"], w.size(0), p + "weight_scale")
+            parts[i] = (self._shard(w, 0, p + "weight").to(self.device).view(torch.uint8),
+                        self._shard(scale, 0, p + "weight_scale").to(self.device))
+        if "weight" in self._parts and all(t is not None for t in parts):
+            self._set("weight", torch.cat([w for w, _ in parts], dim=0).view(torch.float8_e4m3fn))
+            self._set("weight_scale", torch.cat([s for _, s in parts], dim=0))
+            del self._parts["weight"]
+        if self.has_bias:
+            self._load_fused(sd, prefixes, "bias")
+
+
+class RowParallelFp8Linear(_Fp8LinearMixin, RowParallelLinear):
+    """RowParallelLinear over an fp8 checkpoint: the weight is sharded on dim 1, the scale is whole on every rank.
+    With world_size > 1 the GEMM applies the scale to this rank's partial sums, then the all-reduce, then the bias."""
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        if prefixes:
+            raise ValueError("row-parallel linears are never fused (parallel_linear.h:28-33)")
+        self._load_one(sd, "weight", 1)
+        self._load_scale(sd, self.out_features, -1)
+        if self.has_bias:
+            self._load_one(sd, "bias", -1)
+
+
 class LayerNorm:
     """llm::LayerNormImpl (normalization.h:68-110): LayerNormImpl(dim, eps, bias, options);
     forward = kernel::layer_norm on the GPU (normalization.h:86-91) -> slm_layer_norm."""
