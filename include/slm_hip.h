@@ -1293,6 +1293,66 @@ SLM_API size_t slm_fp8_linear_workspace_bytes(const slm_fp8_linear_args* a);
 SLM_API int32_t slm_fp8_linear_deferred_splits(const slm_fp8_linear_args* a);
 SLM_API int slm_fp8_linear(const slm_fp8_linear_args* a, void* stream);
 
+/* ========================================================================== */
+/* 16. fp8 (e4m3) mixture-of-experts: grouped W8A16 GEMM                      */
+/*    slm_moe_gemm (section 10) with section 15's weight side.  For every     */
+/*    32-row block b of the aligned token list (slm_moe_align_block with      */
+/*    block_size 32), e = expert_ids[b], idx = sorted[b * 32 + r]:            */
+/*      acc[idx, n] = sum over k of A[idx / a_div, k] * e4m3(W_e[n, k])       */
+/*                    (e4m3 -> T is exact; fp32 MFMA accumulation in          */
+/*                    slm_moe_gemm's k order: on the same T values the        */
+/*                    accumulators are slm_moe_gemm's bit for bit)            */
+/*      y[idx, n]   = acc[idx, n] * w_scale[e, n]        ONE fp32 multiply    */
+/*      C[idx, n]   = T( y * row_scale[idx] )            ONE rounding to T    */
+/*    W_e = w + e * w_expert_stride BYTES, [N, K] bytes in OCP e4m3fn         */
+/*    (torch.float8_e4m3fn), k contiguous, row stride ldw in bytes: the       */
+/*    checkpoint tensor, never prepacked.  w_scale is fp32, one scale per     */
+/*    expert and output channel at w_scale[e * w_scale_expert_stride + n];    */
+/*    NULL = 1.0 (no multiply); the host expands a per-tensor scale (the      */
+/*    gate and up rows of a merged weight each bring their own).  No block    */
+/*    scale and no activation scale (W8A16).  The NaN codes 0x7F / 0xFF       */
+/*    poison their output column as in section 15.                            */
+/*    With SLM_MOE_SILU_MUL: g = T(y gate), u = T(y up), each under its own   */
+/*    channel scale, c[idx, i] = T(silu(g) * u): the bits of the plain call   */
+/*    followed by slm_silu_mul.  Not with row_scale.                          */
+/*    The aligned-list contract, dead blocks (beyond n_padded, expert ids     */
+/*    outside [0, E)), padding rows, the launch shape (128 / 64 / 32 columns  */
+/*    per workgroup from max_blocks, N and flags alone; no split-K, no        */
+/*    workspace, no atomics: bit-identical repeats and launch shapes), the    */
+/*    shapes (K % 32 == 0, N % 32 == 0, (N/2) % 32 == 0 with SILU_MUL) and    */
+/*    the error codes are slm_moe_gemm's, rule for rule.  The weight side:    */
+/*    w 16-byte aligned, ldw % 16 == 0, w_expert_stride % 16 == 0, w_scale    */
+/*    4-byte aligned (SLM_ERR_ALIGNMENT); ldw >= K, w_expert_stride >=        */
+/*    (N - 1) * ldw + K, w_scale_expert_stride >= N when w_scale is given     */
+/*    (SLM_ERR_INVALID_ARG); one expert (N * ldw bytes) < 4 GiB               */
+/*    (SLM_ERR_UNSUPPORTED).  All validation before any launch; n_flat == 0   */
+/*    or max_blocks == 0 is a no-op.                                          */
+/* ========================================================================== */
+typedef struct slm_moe_fp8_gemm_args {
+  const void* a;                    /* [n_flat / a_div, K] T, row stride lda (elements)           */
+  const void* w;                    /* expert 0: [N, K] float8_e4m3fn bytes, row stride ldw (bytes) */
+  const float* w_scale;             /* [n_experts, N] fp32, expert stride w_scale_expert_stride, or NULL (1.0) */
+  void* c;                          /* [n_flat, N] T (SILU_MUL: [n_flat, N/2]), row stride ldc    */
+  const float* row_scale;           /* [n_flat] fp32 or NULL                                      */
+  const int32_t* sorted_token_idxes;
+  const int32_t* expert_ids;
+  const int32_t* n_padded_tokens;   /* [1], read on the device                                    */
+  int64_t w_expert_stride;          /* bytes between experts, >= (N - 1) * ldw + K                */
+  int64_t w_scale_expert_stride;    /* floats between experts' scales, >= N                       */
+  int64_t n_flat;                   /* rows of c = T * k; the padding id                          */
+  int64_t K, N;
+  int64_t lda, ldw, ldc;
+  int32_t a_div;                    /* >= 1                                                       */
+  int32_t n_experts;
+  int32_t max_blocks;               /* sizes the grid: slm_moe_align_capacity(n_flat, E, 32)      */
+  int32_t dtype;
+  int32_t flags;                    /* 0 or SLM_MOE_SILU_MUL                                      */
+} slm_moe_fp8_gemm_args;
+/* (the parameter list on its own line, as slm_moe_gemm's: tests/test_moe_cpu.py pins section 10's first entry points
+ * by the pattern "name(", and tests/test_moe_fp8_cpu.py covers this one) */
+SLM_API int slm_moe_fp8_gemm
+    (const slm_moe_fp8_gemm_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,18 @@ class MoeDenseGemmArgs(C.Structure):
     ]
 
 
+class MoeFp8GemmArgs(C.Structure):
+    """struct slm_moe_fp8_gemm_args (include/slm_hip.h section 16)."""
+    _fields_ = [
+        ("a", C.c_void_p), ("w", C.c_void_p), ("w_scale", C.c_void_p), ("c", C.c_void_p), ("row_scale", C.c_void_p),
+        ("sorted_token_idxes", C.c_void_p), ("expert_ids", C.c_void_p), ("n_padded_tokens", C.c_void_p),
+        ("w_expert_stride", C.c_int64), ("w_scale_expert_stride", C.c_int64), ("n_flat", C.c_int64),
+        ("K", C.c_int64), ("N", C.c_int64), ("lda", C.c_int64), ("ldw", C.c_int64), ("ldc", C.c_int64),
+        ("a_div", C.c_int32), ("n_experts", C.c_int32), ("max_blocks", C.c_int32), ("dtype", C.c_int32),
+        ("flags", C.c_int32),
+    ]
+
+
 class MlaArgs(C.Structure):
     """struct slm_mla_args (include/slm_hip.h section 11)."""
     _fields_ = [
@@ -378,6 +390,7 @@ def lib() -> C.CDLL:
         ("slm_fp8_linear_workspace_bytes", C.c_size_t, [C.POINTER(Fp8LinearArgs)]),
         ("slm_fp8_linear_deferred_splits", C.c_int32, [C.POINTER(Fp8LinearArgs)]),
         ("slm_fp8_linear_plan", C.c_int, [C.POINTER(Fp8LinearArgs), C.POINTER(LinearPlanInfo)]),
+        ("slm_moe_fp8_gemm", C.c_int, [C.POINTER(MoeFp8GemmArgs), C.c_void_p]),
         ("slm_soft_cap", C.c_int,
          [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
         ("slm_permute_index_map", C.c_int,

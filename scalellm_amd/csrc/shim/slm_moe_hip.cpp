@@ -150,6 +150,61 @@ void moe_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w, torch::Ten
   check(slm_moe_gemm(&g, stream_of(a)), "slm_moe_gemm");
 }
 
+void moe_fp8_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w8, const torch::Tensor& w_scale,
+                          torch::Tensor& c, const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+                          const torch::Tensor& n_padded_tokens, int64_t a_div, const torch::Tensor& row_scale,
+                          bool silu_mul) {
+  TORCH_CHECK(a.is_cuda() && c.is_cuda() && a.dim() == 2 && c.dim() == 2 && a.stride(1) == 1 && c.stride(1) == 1,
+              "slm moe: A and C must be 2-D GPU tensors with contiguous rows");
+  TORCH_CHECK(w8.is_cuda() && w8.dim() == 3 && w8.stride(2) == 1,
+              "slm moe: expert weights must be a GPU tensor [n_experts, N, K] with k contiguous");
+  TORCH_CHECK(w8.scalar_type() == torch::kFloat8_e4m3fn || w8.scalar_type() == torch::kByte,
+              "slm moe: fp8 expert weights must be float8_e4m3fn (or their bytes as uint8), got ", w8.scalar_type());
+  TORCH_CHECK(a.scalar_type() == c.scalar_type(), "slm moe: A and C must share a dtype");
+  check_i32(sorted_token_idxes, "sorted_token_idxes");
+  check_i32(expert_ids, "expert_ids");
+  check_i32(n_padded_tokens, "n_padded_tokens");
+  const int64_t E = w8.size(0), N = w8.size(1), K = w8.size(2);
+  TORCH_CHECK(a.size(1) == K && c.size(1) == (silu_mul ? N / 2 : N) && a_div >= 1 && a.size(0) * a_div >= c.size(0),
+              "slm moe: grouped GEMM shape mismatch");
+  TORCH_CHECK(sorted_token_idxes.numel() >= expert_ids.numel() * 32,
+              "slm moe: sorted_token_idxes is shorter than expert_ids.numel() blocks of 32");
+  slm_moe_fp8_gemm_args g{};
+  g.a = a.data_ptr();
+  g.w = w8.data_ptr();
+  g.c = c.data_ptr();
+  if (w_scale.defined()) {
+    TORCH_CHECK(w_scale.is_cuda() && w_scale.scalar_type() == torch::kFloat && w_scale.dim() == 2 &&
+                    w_scale.size(0) == E && w_scale.size(1) == N && w_scale.stride(1) == 1,
+                "slm moe: w_scale must be fp32 [n_experts, N] with contiguous rows");
+    g.w_scale = w_scale.const_data_ptr<float>();
+    g.w_scale_expert_stride = E > 1 ? w_scale.stride(0) : std::max(w_scale.stride(0), N);
+  }
+  if (row_scale.defined()) {
+    TORCH_CHECK(row_scale.is_cuda() && row_scale.scalar_type() == torch::kFloat && row_scale.is_contiguous() &&
+                    row_scale.numel() == c.size(0),
+                "slm moe: row_scale must be contiguous fp32 with one entry per row of C");
+    g.row_scale = row_scale.const_data_ptr<float>();
+  }
+  g.sorted_token_idxes = sorted_token_idxes.const_data_ptr<int32_t>();
+  g.expert_ids = expert_ids.const_data_ptr<int32_t>();
+  g.n_padded_tokens = n_padded_tokens.const_data_ptr<int32_t>();
+  // a single expert's stride(0) is not meaningful: any multiple of 16 covering the expert will do
+  g.w_expert_stride = E > 1 ? w8.stride(0) : std::max(w8.stride(0), N * w8.stride(1));
+  g.n_flat = c.size(0);
+  g.K = K;
+  g.N = N;
+  g.lda = a.stride(0);
+  g.ldw = w8.stride(1);
+  g.ldc = c.stride(0);
+  g.a_div = static_cast<int32_t>(a_div);
+  g.n_experts = static_cast<int32_t>(E);
+  g.max_blocks = static_cast<int32_t>(expert_ids.numel());
+  g.dtype = dtype_code(a);
+  g.flags = silu_mul ? SLM_MOE_SILU_MUL : 0;
+  check(slm_moe_fp8_gemm(&g, stream_of(a)), "slm_moe_fp8_gemm");
+}
+
 }  // namespace slm
 
 namespace llm::kernel {

@@ -8,6 +8,7 @@
 //   slm::moe_w4_grouped_gemm   the grouped int4 GEMM over stacked packed experts (the reference's grouped GEMM,
 //                              src/kernels/gemm/, is a dense fp16 / bf16 kernel; int4 experts have no counterpart).
 //   slm::moe_grouped_gemm      that dense fp16 / bf16 grouped GEMM over W[e, n, k].
+//   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm_fp8.hip).
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
 #pragma once
@@ -68,5 +69,13 @@ void moe_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w, torch::Ten
                       const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
                       const torch::Tensor& n_padded_tokens, int64_t a_div, const torch::Tensor& row_scale,
                       bool silu_mul);
+
+// moe_grouped_gemm over fp8 experts (include/slm_hip.h section 16): w8 [E, N, K] float8_e4m3fn (or its bytes as
+// uint8), the checkpoint layout; w_scale fp32 [E, N] (one scale per expert and output channel) or undefined (1.0),
+// applied to the fp32 accumulator before row_scale and the one rounding.  The rest as moe_grouped_gemm.
+void moe_fp8_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w8, const torch::Tensor& w_scale,
+                          torch::Tensor& c, const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+                          const torch::Tensor& n_padded_tokens, int64_t a_div, const torch::Tensor& row_scale,
+                          bool silu_mul);
 
 }  // namespace slm

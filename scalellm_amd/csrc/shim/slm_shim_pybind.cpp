@@ -300,6 +300,17 @@ PYBIND11_MODULE(_slm_shim, m) {
                                 row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
         }, py::arg("a"), py::arg("w"), py::arg("c"), py::arg("sorted_token_idxes"), py::arg("expert_ids"),
         py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
+  m.def("moe_fp8_grouped_gemm",
+        [](const torch::Tensor& a, const torch::Tensor& w8, const c10::optional<torch::Tensor>& w_scale, torch::Tensor c,
+           const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+           const torch::Tensor& n_padded_tokens, int64_t a_div, const c10::optional<torch::Tensor>& row_scale,
+           bool silu_mul) {
+          slm::moe_fp8_grouped_gemm(a, w8, w_scale.has_value() ? *w_scale : torch::Tensor(), c, sorted_token_idxes,
+                                    expert_ids, n_padded_tokens, a_div,
+                                    row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
+        }, py::arg("a"), py::arg("w8"), py::arg("w_scale"), py::arg("c"), py::arg("sorted_token_idxes"),
+        py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(),
+        py::arg("silu_mul") = false);
   // MoE token permutation (slm_permute_hip.h): the reference's four functions
   m.def("moe_permute_with_index_map", &llm::kernel::moe::permute_with_index_map, py::arg("tokens"),
         py::arg("indices"));

@@ -1441,6 +1441,7 @@ def rejection_sample(draft_token_ids: torch.Tensor, draft_probs: Optional[torch.
 #   moe_align_block / moe_sum                   <- llm::kernel::moe::permute_align_block / sum_out
 #   moe_w4_grouped_gemm                         <- the grouped GEMM of src/kernels/gemm/ over int4 experts
 #   moe_grouped_gemm                            <- the grouped GEMM of src/kernels/gemm/ itself (dense f16 / bf16)
+#   moe_fp8_grouped_gemm                        <- the same over fp8 (e4m3) experts with channel scales (section 16)
 # ---------------------------------------------------------------------------------------
 MOE_GEMM_BLOCK = _lib.SLM_MOE_GEMM_BLOCK
 
@@ -1639,6 +1640,55 @@ def moe_grouped_gemm(a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, sorted_t
     g.dtype = _dtype_code(a)
     g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
     check(_lib.lib().slm_moe_gemm(C.byref(g), _stream()), "slm_moe_gemm")
+
+
+def moe_fp8_grouped_gemm(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
+                         sorted_token_idxes: torch.Tensor, expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor,
+                         a_div: int, row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """moe_grouped_gemm over fp8 experts (slm_hip.h section 16): C[idx] = epilogue((A[idx // a_div] . e4m3(W8[e])^T)
+    * w_scale[e]).  `w8` is [E, N, K] float8_e4m3fn (or its bytes as uint8), the checkpoint layout, k contiguous,
+    expert and row strides may be padded (multiples of 16); `w_scale` fp32 [E, N] (rows contiguous, the expert
+    stride may be padded) or None (1.0), applied to the fp32 accumulator before row_scale and the one rounding.
+    silu_mul, row_scale, the aligned list and the grid: as moe_grouped_gemm."""
+    _require_gpu(a, w8, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    if w8.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise SlmError(f"moe_fp8_grouped_gemm takes float8_e4m3fn weights (or their bytes), not {w8.dtype}")
+    if a.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1:
+        raise SlmError("A and C must be 2-D with contiguous rows")
+    if w8.dim() != 3 or w8.stride(2) != 1:
+        raise SlmError("expert weights must be [n_experts, N, K] with k contiguous")
+    E, N, K = w8.shape
+    n_flat = c.size(0)
+    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a_div < 1 or a.size(0) * a_div < n_flat:
+        raise SlmError("grouped GEMM shape mismatch")
+    if a.dtype not in (torch.float16, torch.bfloat16) or c.dtype != a.dtype:
+        raise SlmError("activation and output must share one dtype, fp16 or bf16")
+    if w_scale is not None and (w_scale.dtype != torch.float32 or tuple(w_scale.shape) != (E, N) or
+                                w_scale.stride(1) != 1):
+        raise SlmError("w_scale must be fp32 [n_experts, N] with contiguous rows (expand a per-tensor scale)")
+    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
+    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
+        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
+                                  row_scale.numel() != n_flat):
+        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
+    g = _lib.MoeFp8GemmArgs()
+    g.a, g.w, g.c = a.data_ptr(), w8.data_ptr(), c.data_ptr()
+    g.w_scale = w_scale.data_ptr() if w_scale is not None else None
+    g.row_scale = row_scale.data_ptr() if row_scale is not None else None
+    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
+    g.n_padded_tokens = n_padded_tokens.data_ptr()
+    # a single expert's stride(0) is not meaningful: any multiple of 16 covering the expert will do
+    g.w_expert_stride = w8.stride(0) if E > 1 else max(w8.stride(0), N * w8.stride(1))
+    g.w_scale_expert_stride = 0 if w_scale is None else (w_scale.stride(0) if E > 1 else max(w_scale.stride(0), N))
+    g.n_flat, g.K, g.N = n_flat, K, N
+    g.lda, g.ldw, g.ldc = a.stride(0), w8.stride(1), c.stride(0)
+    g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
+    g.dtype = _dtype_code(a)
+    g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
+    check(_lib.lib().slm_moe_fp8_gemm(C.byref(g), _stream()), "slm_moe_fp8_gemm")
 
 
 # ---------------------------------------------------------------------------------------

@@ -198,8 +198,10 @@ class Attention:
 # ---------------------------------------------------------------------------------------
 @dataclass
 class QuantArgs:
-    """layers/quantization/quant_args.h:10-33."""
-    quant_method: str = "awq"   # "awq" | "gptq"
+    """layers/quantization/quant_args.h:10-33.  quant_method "fp8" with bits = 8 selects e4m3 weight-only (W8A16)
+    weights where a layer offers them (moe.FusedMoE / ExpertParallelMoE; LlamaDecodeStep takes quant_method="fp8"
+    directly); group_size, desc_act and zero_point mean nothing there and are ignored."""
+    quant_method: str = "awq"   # "awq" | "gptq" | "fp8"
     bits: int = 4
     group_size: int = 128
     desc_act: bool = False

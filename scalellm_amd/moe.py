@@ -1,6 +1,6 @@
-"""Mixture-of-experts FFN over int4 (AWQ / GPTQ) or unquantised f16 / bf16 experts: routing, block alignment, two
-grouped GEMMs and the sum over a token's experts, every step a HIP kernel of libslm_hip (include/slm_hip.h
-section 10).
+"""Mixture-of-experts FFN over int4 (AWQ / GPTQ), fp8 (e4m3, weight-only) or unquantised f16 / bf16 experts: routing,
+block alignment, two grouped GEMMs and the sum over a token's experts, every step a HIP kernel of libslm_hip
+(include/slm_hip.h sections 10 and 16).
 
     FusedMoE.forward(x):  router logits (fp32, torch: [T, hidden] x [hidden, E] is tiny)
                           -> moe_topk_softmax | moe_grouped_topk_sigmoid      (weights, expert ids)
@@ -16,7 +16,7 @@ captured in a graph and replayed for any routing.
 Across GPUs the experts are sharded by expert parallelism: LocalTokenDispatcher / AlltoAllTokenDispatcher permute
 tokens into expert-major rows (include/slm_hip.h section 14) and ExpertParallelMoE runs the same two grouped GEMMs
 over one rank's experts between an all-to-all pair.  Out of scope here: tensor-parallel sharding of an expert,
-shared experts, 8-bit and act-order experts.
+shared experts, int8 and act-order experts, fp8 activations and block-wise fp8 scales.
 """
 from __future__ import annotations
 
@@ -92,6 +92,10 @@ class MoEQuantExperts:
     def nbytes(self) -> int:
         return self.gate_up.nbytes() + self.down.nbytes()
 
+    def gemm(self, which: str, a, c, *aligned, **epilogue) -> None:
+        """the grouped GEMM over `which` = "gate_up" | "down"; the arguments after c are the kernel's"""
+        kernels.moe_w4_grouped_gemm(a, getattr(self, which), c, *aligned, **epilogue)
+
 
 class MoEDenseExperts:
     """The unquantised weights of E experts, stacked in the checkpoint's own [out, in] layout: `gate_up`
@@ -140,10 +144,115 @@ class MoEDenseExperts:
     def nbytes(self) -> int:
         return (self.gate_up.numel() + self.down.numel()) * self.gate_up.element_size()
 
+    def gemm(self, which: str, a, c, *aligned, **epilogue) -> None:
+        """the grouped GEMM over `which` = "gate_up" | "down"; the arguments after c are the kernel's"""
+        kernels.moe_grouped_gemm(a, getattr(self, which), c, *aligned, **epilogue)
+
+
+class MoEFp8Experts:
+    """The fp8 (e4m3) weights of E experts, stacked in the checkpoint's own [out, in] layout as bytes: `gate_up`
+    [E, 2 * intermediate, hidden] (w1 rows, then w3 rows) and `down` [E, hidden, intermediate], with one fp32 scale
+    per expert and output channel: `gate_up_scale` [E, 2 * intermediate], `down_scale` [E, hidden].  load_state_dict
+    takes Mixtral-FP8 names experts.{e}.w1|w3|w2.weight (float8_e4m3fn; any other dtype is a TypeError -- nothing is
+    quantised on load, as in the fp8 linears) and .weight_scale (0-d, [1], [rows] or [rows, 1], any float dtype; a
+    per-tensor scale is expanded over its own rows, so w1 and w3 keep their own).  input_scale is ignored (W8A16)."""
+
+    def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device,
+                 expert_offset: int = 0):
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise SlmError(f"MoE experts: fp16 / bf16 activations only, got {dtype}")
+        self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
+        self.dtype, self.device = dtype, device
+        self.expert_offset = expert_offset   # expert e of this holder is experts.{expert_offset + e}.* (an EP shard)
+        self._ckpt: Dict[str, torch.Tensor] = {}
+        self.gate_up: Optional[torch.Tensor] = None
+        self.down: Optional[torch.Tensor] = None
+        self.gate_up_scale: Optional[torch.Tensor] = None
+        self.down_scale: Optional[torch.Tensor] = None
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        for e in range(self.n_experts):
+            for w in ("w1", "w2", "w3"):
+                src, dst = f"experts.{self.expert_offset + e}.{w}.", f"experts.{e}.{w}."
+                if src + "weight" in sd:
+                    t = sd[src + "weight"]
+                    if t.dtype != torch.float8_e4m3fn:
+                        raise TypeError(f"fp8 experts: {src}weight must be float8_e4m3fn, not {t.dtype} "
+                                        "(quantize_fp8_weight makes one; nothing is quantised on load)")
+                    self._ckpt[dst + "weight"] = t.to(self.device)
+                if src + "weight_scale" in sd:
+                    t = sd[src + "weight_scale"]
+                    if not t.is_floating_point():
+                        raise TypeError(f"{src}weight_scale must be a float tensor, not {t.dtype}")
+                    self._ckpt[dst + "weight_scale"] = t.to(self.device, torch.float32)
+        self.gate_up = self.down = self.gate_up_scale = self.down_scale = None
+
+    def verify_loaded_weights(self) -> None:
+        if self.gate_up is not None:
+            return
+        for e in range(self.n_experts):
+            for w in ("w1", "w2", "w3"):
+                for name in ("weight", "weight_scale"):
+                    assert f"experts.{e}.{w}.{name}" in self._ckpt, f"experts.{e}.{w}.{name} is not loaded"
+
+    @staticmethod
+    def _channel_scale(t: torch.Tensor, rows: int, what: str) -> torch.Tensor:
+        """0-d / [1] (per tensor) or [rows] / [rows, 1] (per channel) -> fp32 [rows]"""
+        flat = t.reshape(-1)
+        if flat.numel() == 1:
+            return flat.expand(rows)
+        if flat.numel() != rows or t.dim() > 2 or (t.dim() == 2 and t.size(1) != 1):
+            raise SlmError(f"{what} size mismatch: {tuple(t.shape)} for {rows} output channels")
+        return flat
+
+    def repack(self) -> None:
+        self.verify_loaded_weights()
+        c = self._ckpt
+        H, I = self.hidden, self.intermediate
+        u8 = lambda e, w: c[f"experts.{e}.{w}.weight"].view(torch.uint8)  # noqa: E731  (cat / stack on bytes)
+        sc = lambda e, w, rows: self._channel_scale(c[f"experts.{e}.{w}.weight_scale"], rows,  # noqa: E731
+                                                    f"experts.{e}.{w}.weight_scale")
+        for e in range(self.n_experts):
+            if tuple(u8(e, "w1").shape) != (I, H) or tuple(u8(e, "w3").shape) != (I, H) or \
+                    tuple(u8(e, "w2").shape) != (H, I):
+                raise SlmError("expert weights do not match hidden / intermediate")
+        E = range(self.n_experts)
+        f8 = torch.float8_e4m3fn
+        self.gate_up = torch.stack([torch.cat([u8(e, "w1"), u8(e, "w3")], dim=0) for e in E]).contiguous().view(f8)
+        self.down = torch.stack([u8(e, "w2") for e in E]).contiguous().view(f8)
+        self.gate_up_scale = torch.stack([torch.cat([sc(e, "w1", I), sc(e, "w3", I)]) for e in E]).contiguous()
+        self.down_scale = torch.stack([sc(e, "w2", H) for e in E]).contiguous()
+        self._ckpt = {}
+
+    def nbytes(self) -> int:
+        return self.gate_up.numel() + self.down.numel() + 4 * (self.gate_up_scale.numel() + self.down_scale.numel())
+
+    def gemm(self, which: str, a, c, *aligned, **epilogue) -> None:
+        """the grouped GEMM over `which` = "gate_up" | "down"; the arguments after c are the kernel's"""
+        kernels.moe_fp8_grouped_gemm(a, getattr(self, which), getattr(self, which + "_scale"), c, *aligned,
+                                     **epilogue)
+
+
+def _make_experts(hidden: int, intermediate: int, n_experts: int, quant_args: Optional[QuantArgs], dtype, device,
+                  expert_offset: int = 0):
+    """The experts holder a QuantArgs selects: None -> unquantised, "fp8" -> MoEFp8Experts, else int4."""
+    if quant_args is None or quant_args.quant_method == "fp8":
+        if quant_args is not None and quant_args.bits != 8:
+            raise SlmError(f"quant_method 'fp8' means 8-bit weights, got bits = {quant_args.bits}")
+        if hidden % 32 or intermediate % 32:
+            raise SlmError("hidden and intermediate must be multiples of 32 (K and N of the two grouped GEMMs)")
+        cls = MoEDenseExperts if quant_args is None else MoEFp8Experts
+        return cls(hidden, intermediate, n_experts, dtype, device, expert_offset)
+    if hidden % 128 or intermediate % 128:
+        raise SlmError("hidden and intermediate must be multiples of 128 (K of the two grouped GEMMs)")
+    return MoEQuantExperts(hidden, intermediate, n_experts, quant_args, dtype, device, expert_offset)
+
 
 class FusedMoE:
     """Sparse FFN block: a router (`gate`, an unquantised [E, hidden] weight) over n_experts SwiGLU experts: int4
-    (AWQ / GPTQ) with a QuantArgs, unquantised f16 / bf16 with quant_args=None.
+    (AWQ / GPTQ) with a QuantArgs, fp8 (e4m3 weights, f16 / bf16 activations) with QuantArgs("fp8", 8) -- its other
+    fields are ignored --, unquantised f16 / bf16 with quant_args=None.  Each experts class runs its own grouped GEMM
+    (experts.gemm); the forward pass is the same six launches for all three.
 
     scoring = "softmax": top-k of the softmax (renormalize = Mixtral's rule: the k weights divided by their sum);
     scoring = "grouped_sigmoid": sigmoid scores with a correction bias, group-limited top-k (n_expert_groups,
@@ -158,17 +267,11 @@ class FusedMoE:
             raise SlmError(f"unknown scoring {scoring}")
         if not 1 <= topk <= n_experts:
             raise SlmError(f"topk = {topk} must be in 1 .. n_experts = {n_experts}")
-        if quant_args is not None and (hidden % 128 or intermediate % 128):
-            raise SlmError("hidden and intermediate must be multiples of 128 (K of the two grouped GEMMs)")
-        if quant_args is None and (hidden % 32 or intermediate % 32):
-            raise SlmError("hidden and intermediate must be multiples of 32 (K and N of the two grouped GEMMs)")
         self.hidden, self.intermediate, self.n_experts, self.topk = hidden, intermediate, n_experts, topk
         self.scoring, self.renormalize = scoring, renormalize
         self.n_expert_groups, self.topk_group, self.scaling_factor = n_expert_groups, topk_group, scaling_factor
         self.max_tokens, self.dtype, self.device = max_tokens, dtype, device
-        self.experts = MoEDenseExperts(hidden, intermediate, n_experts, dtype, device) if quant_args is None else \
-            MoEQuantExperts(hidden, intermediate, n_experts, quant_args, dtype, device)
-        self._gemm = kernels.moe_grouped_gemm if quant_args is None else kernels.moe_w4_grouped_gemm
+        self.experts = _make_experts(hidden, intermediate, n_experts, quant_args, dtype, device)
         self.gate_weight: Optional[torch.Tensor] = None       # [E, hidden]
         self.correction_bias: Optional[torch.Tensor] = None   # [E] fp32 (grouped_sigmoid)
         self._gate_f32_t: Optional[torch.Tensor] = None       # [hidden, E] fp32, built on the first forward
@@ -230,8 +333,8 @@ class FusedMoE:
             kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups, self.topk_group, k,
                                              self.scaling_factor, weights, ids)
         kernels.moe_align_block(ids, self.n_experts, kernels.MOE_GEMM_BLOCK, srt, eids, b["n_padded"])
-        self._gemm(x2, self.experts.gate_up, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
-        self._gemm(act, self.experts.down, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
+        self.experts.gemm("gate_up", x2, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
+        self.experts.gemm("down", act, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
         kernels.moe_sum(down.view(T, k, self.hidden), out.view(T, self.hidden))
         return out.view(x.shape)
 
@@ -419,10 +522,7 @@ class ExpertParallelMoE:
         self.n_expert_groups, self.topk_group, self.scaling_factor = n_expert_groups, topk_group, scaling_factor
         self.dtype, self.device = dtype, device
         offset = process_group.rank * L
-        self.experts = MoEDenseExperts(hidden, intermediate, L, dtype, device, expert_offset=offset) \
-            if quant_args is None else \
-            MoEQuantExperts(hidden, intermediate, L, quant_args, dtype, device, expert_offset=offset)
-        self._gemm = kernels.moe_grouped_gemm if quant_args is None else kernels.moe_w4_grouped_gemm
+        self.experts = _make_experts(hidden, intermediate, L, quant_args, dtype, device, expert_offset=offset)
         self.gate_weight: Optional[torch.Tensor] = None
         self.correction_bias: Optional[torch.Tensor] = None
         self._gate_f32_t: Optional[torch.Tensor] = None
@@ -449,8 +549,8 @@ class ExpertParallelMoE:
         n_padded = torch.zeros(1, dtype=i32, device=dev)
         kernels.moe_align_block(row_expert, L, kernels.MOE_GEMM_BLOCK, srt, eids, n_padded)
         act = torch.empty(n, self.intermediate, dtype=rows.dtype, device=dev)
-        self._gemm(rows, self.experts.gate_up, act, srt, eids, n_padded, a_div=1, silu_mul=True)
-        self._gemm(act, self.experts.down, down, srt, eids, n_padded, a_div=1)
+        self.experts.gemm("gate_up", rows, act, srt, eids, n_padded, a_div=1, silu_mul=True)
+        self.experts.gemm("down", act, down, srt, eids, n_padded, a_div=1)
         return down
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

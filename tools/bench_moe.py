@@ -3,6 +3,7 @@ loop over the experts: per-expert slm_w4a16_gemm calls for int4 experts, torch.m
 
     python tools/bench_moe.py [--out profiles/r09_moe.jsonl] [--tokens 1,32,256] [--iters 200]
     python tools/bench_moe.py --dense [--out profiles/r12_moe_dense.jsonl]
+    python tools/bench_moe.py --fp8 [--out profiles/r18_moe_fp8.jsonl]
 
 hidden 4096, intermediate 14336, E = 8, k = 2, AWQ group 128, bf16 (random weights: 705 MB packed).  One JSON
 line per T:
@@ -23,6 +24,14 @@ line per T:
 --dense: the same layer over unquantised bf16 experts (FusedMoE(quant_args=None), slm_moe_gemm; 2.8 GB of weights),
 measured the same way; the loop is index_select, torch.matmul (gate | up), SiLU * mul, torch.matmul (down), scale,
 index_add_ per expert.
+
+--fp8: the same layer over fp8 (e4m3) experts (FusedMoE(QuantArgs("fp8", 8)), slm_moe_fp8_gemm; 1.4 GB of weights):
+the bf16 checkpoint of --dense quantised per output channel by kernels.quantize_fp8_weight, and beside it, in the
+same run, the dense bf16 layer over the dequantised weights (the same values, so the same routing and the same
+experts streamed).  Both forwards are captured in graphs and replayed over the input pool in `--rounds` alternating
+windows of `iters` replays; one JSON line per T with fp8_us / dense_us (the medians; every window is listed),
+touched_bytes / streamed_bytes / frac_7tbs over the fp8 bytes (weights + scales), the dense layer's own
+dense_frac_7tbs, and fp8_vs_dense_rel_err (different rounding of nothing but the accumulator's scale multiply).
 """
 import argparse
 import json
@@ -72,6 +81,86 @@ def _dense_layer(max_tokens, dev):
     del sd
     layer(torch.zeros(1, HID, device=dev, dtype=torch.bfloat16))   # stack + buffers
     return layer
+
+
+def _fp8_and_dense_layers(max_tokens, dev):
+    """the --dense checkpoint quantised per output channel, and the dense layer over what the fp8 one computes with"""
+    g = torch.Generator(device=dev).manual_seed(0)
+    sd8, sd16 = {}, {}
+    for e in range(NE):
+        for w, (N, K) in (("w1", (INTER, HID)), ("w3", (INTER, HID)), ("w2", (HID, INTER))):
+            w8, scale = kernels.quantize_fp8_weight((torch.randn(N, K, device=dev, generator=g) * 0.02
+                                                     ).to(torch.bfloat16), "channel")
+            sd8[f"experts.{e}.{w}.weight"], sd8[f"experts.{e}.{w}.weight_scale"] = w8, scale
+            sd16[f"experts.{e}.{w}.weight"] = (w8.float() * scale[:, None]).to(torch.bfloat16)
+    sd8["gate.weight"] = sd16["gate.weight"] = (torch.randn(NE, HID, device=dev, generator=g) * 0.05).to(torch.bfloat16)
+    layers = []
+    for sd, q in ((sd8, QuantArgs("fp8", 8)), (sd16, None)):
+        layer = moe.FusedMoE(HID, INTER, NE, TOPK, quant_args=q, scoring="softmax", renormalize=True,
+                             max_tokens=max_tokens, dtype=torch.bfloat16, device=dev)
+        layer.load_state_dict(sd)
+        sd.clear()
+        layer(torch.zeros(1, HID, device=dev, dtype=torch.bfloat16))   # stack + buffers
+        layers.append(layer)
+    return layers
+
+
+def _captured(layer, pool, T, dev):
+    """layer.forward captured over a static input; returns replay(i) for pool entry i and the static output"""
+    x_static, out_static = pool[0].clone(), torch.empty(T, HID, device=dev, dtype=torch.bfloat16)
+    eager = layer(pool[1]).clone()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        layer.forward(x_static, out=out_static)
+    x_static.copy_(pool[1])
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out_static, eager), "graph replay differs from the eager forward"
+
+    def replay(i):
+        x_static.copy_(pool[i % len(pool)])
+        graph.replay()
+
+    return replay, eager
+
+
+def _main_fp8(args, dev, tokens):
+    fp8, dense = _fp8_and_dense_layers(max(tokens), dev)
+    ex = fp8.experts
+    gu_bytes = (ex.gate_up.numel() + 4 * ex.gate_up_scale.numel()) // NE
+    dn_bytes = (ex.down.numel() + 4 * ex.down_scale.numel()) // NE
+    dense_bytes = dense.experts.nbytes() // NE
+    lines = []
+    for T in tokens:
+        g = torch.Generator(device=dev).manual_seed(T)
+        pool = [torch.randn(T, HID, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(args.pool)]
+        run8, y8 = _captured(fp8, pool, T, dev)
+        run16, y16 = _captured(dense, pool, T, dev)
+        rel = float((y8.float() - y16.float()).abs().mean() / y16.float().abs().mean())
+        t8, t16 = [], []
+        for _ in range(args.rounds):                    # alternating windows: drift hits both columns alike
+            t8.append(_time(run8, args.iters))
+            t16.append(_time(run16, args.iters))
+        fp8_us, dense_us = sorted(t8)[len(t8) // 2], sorted(t16)[len(t16) // 2]
+        routed = [_routing(fp8, x)[1] for x in pool]
+        used = [int(ids.unique().numel()) for ids in routed]
+        blocks = [int(((torch.bincount(ids.reshape(-1), minlength=NE) + 31) // 32).sum()) for ids in routed]
+        n_used, n_blocks = sum(used) / len(used), sum(blocks) / len(blocks)
+        touched, streamed = (gu_bytes + dn_bytes) * n_used, (gu_bytes + dn_bytes) * n_blocks
+        line = dict(bench="moe_mixtral_8x7b_fp8_bf16", T=T, topk=TOPK, n_experts=NE,
+                    fp8_us=round(fp8_us, 2), dense_us=round(dense_us, 2), fp8_over_dense=round(fp8_us / dense_us, 4),
+                    fp8_us_windows=[round(t, 2) for t in t8], dense_us_windows=[round(t, 2) for t in t16],
+                    experts_in_use=round(n_used, 2), row_blocks=round(n_blocks, 2),
+                    touched_bytes=int(touched), streamed_bytes=int(streamed),
+                    frac_7tbs=round(touched / (fp8_us * 1e-6) / READ_CEILING, 4),
+                    streamed_frac_7tbs=round(streamed / (fp8_us * 1e-6) / READ_CEILING, 4),
+                    dense_touched_bytes=int(dense_bytes * n_used),
+                    dense_frac_7tbs=round(dense_bytes * n_used / (dense_us * 1e-6) / READ_CEILING, 4),
+                    fp8_vs_dense_rel_err=round(rel, 5), iters=args.iters, pool=args.pool, rounds=args.rounds)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
 
 
 def _routing(layer, x):
@@ -133,11 +222,19 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--pool", type=int, default=16)
     ap.add_argument("--dense", action="store_true", help="unquantised bf16 experts (slm_moe_gemm)")
+    ap.add_argument("--fp8", action="store_true",
+                    help="fp8 (e4m3) experts (slm_moe_fp8_gemm) beside the dense bf16 layer on the dequantised weights")
+    ap.add_argument("--rounds", type=int, default=3, help="--fp8: alternating timing windows per layer")
     args = ap.parse_args()
+    if args.dense and args.fp8:
+        raise SystemExit("--dense and --fp8 are two modes: pick one (--fp8 measures the dense layer too)")
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda")
     tokens = [int(t) for t in args.tokens.split(",")]
+    if args.fp8:
+        _write(args.out, _main_fp8(args, dev, tokens))
+        return
     if args.dense:
         layer = _dense_layer(max(tokens), dev)
         gu_bytes, dn_bytes = layer.experts.gate_up.numel() * 2 // NE, layer.experts.down.numel() * 2 // NE
@@ -194,8 +291,12 @@ def main():
                     fused_vs_loop_rel_err=round(rel, 5), iters=args.iters, pool=args.pool)
         print(json.dumps(line), flush=True)
         lines.append(line)
-    if args.out:
-        with open(args.out, "w") as f:
+    _write(args.out, lines)
+
+
+def _write(path, lines):
+    if path:
+        with open(path, "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
 
