@@ -1353,6 +1353,77 @@ typedef struct slm_moe_fp8_gemm_args {
 SLM_API int slm_moe_fp8_gemm
     (const slm_moe_fp8_gemm_args* a, void* stream);
 
+/* ========================================================================== */
+/* 17. Fused MoE router: gate GEMM + routing in one launch                    */
+/*    For every token t:                                                      */
+/*      logit[t, e] = sum over h of x[t, h] * gate_w[e, h]                    */
+/*                    (a product of two T values is exact in fp32; fp32 MFMA  */
+/*                    accumulation, never rounded to T)                       */
+/*      weights[t, :k], indices[t, :k] = section 10's routing of logit[t, :]  */
+/*                    scoring 0: slm_moe_topk_softmax (renormalize),          */
+/*                    scoring 1: slm_moe_grouped_topk_sigmoid                 */
+/*                    (correction_bias, n_expert_groups, topk_group,          */
+/*                    scaling_factor)                                         */
+/*      logits_out[t, :E] = logit[t, :] (fp32, contiguous) when not NULL.     */
+/*    x is [T, hidden] T with row stride ldx, gate_w is gate.weight as the    */
+/*    checkpoint holds it, [E, hidden] T with row stride ldw: no transpose,   */
+/*    no fp32 copy.  The routing is section 10's own device code, so weights  */
+/*    and indices are bit-identical to the section 10 entry run on            */
+/*    logits_out, ties by the lower expert id included.                       */
+/*    Batch invariance: the K split, the order of the additions and the tile  */
+/*    position of a row depend on (hidden, E, dtype) alone, never on T, the   */
+/*    row's index or the other rows: row t routed alone gives the bits it     */
+/*    gives inside any batch; repeats are bit-identical; no float atomics.    */
+/*    One launch on the given stream, no host sync, no allocation, no         */
+/*    workgroup waits for another: capture-safe.  One workgroup owns 32       */
+/*    token rows and all E columns; rows at or beyond T and experts at or     */
+/*    beyond E inside a tile are loaded clamped and never stored.             */
+/*    slm_moe_router_splits: the number of K slices a row tile is spread      */
+/*    over, a pure function of (E, hidden, dtype) -- not of T.  This version  */
+/*    always plans 1, which needs no workspace                                */
+/*    (slm_moe_router_workspace_bytes gives 0); workspace / workspace_bytes   */
+/*    are checked against that size.  Both helpers are host functions and     */
+/*    launch nothing.                                                         */
+/*    Limits: E a power of two <= 256, 1 <= k <= E, the grouped form under    */
+/*    section 10's conditions; hidden % 32 == 0; f16 / bf16; ldx, ldw         */
+/*    multiples of 8 and x, gate_w 16-byte aligned (16-byte loads).           */
+/*    Before any launch: SLM_ERR_INVALID_ARG on NULL or negative arguments,   */
+/*    an unknown scoring, a stride below hidden, correction_bias missing for  */
+/*    scoring 1, the grouped conditions; SLM_ERR_UNSUPPORTED on other dtypes, */
+/*    E or hidden outside the limits; SLM_ERR_ALIGNMENT on misaligned         */
+/*    pointers or strides; SLM_ERR_WORKSPACE when the workspace is missing or */
+/*    smaller than slm_moe_router_workspace_bytes; n_tokens == 0 is a no-op.  */
+/* ========================================================================== */
+typedef struct slm_moe_router_args {
+  const void* x;                    /* [n_tokens, hidden] T, row stride ldx (elements)            */
+  const void* gate_w;               /* [n_experts, hidden] T, row stride ldw (elements)           */
+  const float* correction_bias;     /* [n_experts] fp32; NULL with scoring 0                      */
+  float* weights;                   /* [n_tokens, topk] fp32, contiguous                          */
+  int32_t* indices;                 /* [n_tokens, topk] int32, contiguous                         */
+  float* logits_out;                /* [n_tokens, n_experts] fp32, contiguous, or NULL            */
+  void* workspace;                  /* slm_moe_router_workspace_bytes, or NULL when that is 0     */
+  int64_t workspace_bytes;
+  int64_t n_tokens;
+  int64_t hidden;
+  int64_t ldx, ldw;
+  int32_t n_experts;
+  int32_t topk;
+  int32_t dtype;
+  int32_t scoring;                  /* 0 = softmax, 1 = grouped sigmoid                           */
+  int32_t renormalize;              /* scoring 0                                                  */
+  int32_t n_expert_groups;          /* scoring 1                                                  */
+  int32_t topk_group;               /* scoring 1                                                  */
+  float scaling_factor;             /* scoring 1                                                  */
+} slm_moe_router_args;
+/* (the parameter lists on their own lines, as slm_moe_gemm's: tests/test_moe_cpu.py pins section 10's first entry
+ * points by the pattern "name(", and tests/test_moe_router_cpu.py covers these) */
+SLM_API int slm_moe_router_splits
+    (int32_t n_experts, int64_t hidden, int32_t dtype, int32_t* splits);
+SLM_API int slm_moe_router_workspace_bytes
+    (int64_t n_tokens, int32_t n_experts, int64_t hidden, int32_t dtype, size_t* bytes);
+SLM_API int slm_moe_router
+    (const slm_moe_router_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

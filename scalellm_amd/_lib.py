@@ -188,6 +188,22 @@ class MoeFp8GemmArgs(C.Structure):
     ]
 
 
+class MoeRouterArgs(C.Structure):
+    """struct slm_moe_router_args (include/slm_hip.h section 17)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("gate_w", C.c_void_p), ("correction_bias", C.c_void_p), ("weights", C.c_void_p),
+        ("indices", C.c_void_p), ("logits_out", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64), ("n_tokens", C.c_int64), ("hidden", C.c_int64),
+        ("ldx", C.c_int64), ("ldw", C.c_int64),
+        ("n_experts", C.c_int32), ("topk", C.c_int32), ("dtype", C.c_int32), ("scoring", C.c_int32),
+        ("renormalize", C.c_int32), ("n_expert_groups", C.c_int32), ("topk_group", C.c_int32),
+        ("scaling_factor", C.c_float),
+    ]
+
+
+SLM_ROUTER_SOFTMAX, SLM_ROUTER_GROUPED_SIGMOID = 0, 1   # slm_moe_router_args.scoring
+
+
 class MlaArgs(C.Structure):
     """struct slm_mla_args (include/slm_hip.h section 11)."""
     _fields_ = [
@@ -391,6 +407,10 @@ def lib() -> C.CDLL:
         ("slm_fp8_linear_deferred_splits", C.c_int32, [C.POINTER(Fp8LinearArgs)]),
         ("slm_fp8_linear_plan", C.c_int, [C.POINTER(Fp8LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_fp8_gemm", C.c_int, [C.POINTER(MoeFp8GemmArgs), C.c_void_p]),
+        ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
+        ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+        ("slm_moe_router_workspace_bytes", C.c_int,
+         [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
         ("slm_soft_cap", C.c_int,
          [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
         ("slm_permute_index_map", C.c_int,

@@ -5,110 +5,23 @@
 //   slm_moe_sum                  <- llm::kernel::moe::sum_out             (moe/align_block_kernel.cu:242)
 // Small kernels: one launch each, no float atomics, fixed reduction orders (bit-identical repeats).
 // The grouped GEMM that consumes the aligned blocks is w4_moe.hip.
-#include <math.h>
-
 #include "common.h"
+#include "moe_route.h"
 
 namespace slm {
 namespace {
 
-constexpr int kMaxRouteExperts = 256;  // the reference's own limit for both routing kernels
-constexpr int kRouteWaves = 4;         // tokens (waves) per routing workgroup
-constexpr int kEpl = kMaxRouteExperts / 64;  // experts per lane: lane l holds l, l + 64, ...
 constexpr int kMaxAlignExperts = 1024;
-constexpr int kNoIdx = 0x7fffffff;
 
-// (value, index) candidates: higher value first, then the lower index (-0 == +0: a tie)
-__device__ __forceinline__ bool ranks_before(float v, int i, float w, int j) {
-  return v > w || (v == w && i < j);
-}
-
-// the best remaining candidate of the wave's E values: every lane returns the same (v, idx)
-__device__ __forceinline__ void wave_best(const float (&val)[kEpl], const unsigned taken, const int lane,
-                                          const int E, float& bv, int& bi) {
-  bv = -INFINITY;
-  bi = kNoIdx;
-#pragma unroll
-  for (int s = 0; s < kEpl; ++s) {
-    const int e = lane + 64 * s;
-    if (e < E && !((taken >> s) & 1u) && ranks_before(val[s], e, bv, bi)) { bv = val[s]; bi = e; }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float ov = __shfl_xor(bv, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-// butterfly sum: every lane adds the same pairs in the same order
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// one wave per token
+// one wave per token; the per-token bodies are moe_route.h's (shared with moe_router.hip)
 __global__ void __launch_bounds__(64 * kRouteWaves)
 topk_softmax_kernel(const float* __restrict__ logits, float* __restrict__ weights, int* __restrict__ indices,
                     const int64_t T, const int E, const int k, const int renorm) {
   const int lane = threadIdx.x & 63;
   const int64_t t = (int64_t)blockIdx.x * kRouteWaves + (threadIdx.x >> 6);
   if (t >= T) return;  // no workgroup barrier below
-  const float* x = logits + t * E;
-  float val[kEpl];
-  float m = -INFINITY;
-#pragma unroll
-  for (int s = 0; s < kEpl; ++s) {
-    const int e = lane + 64 * s;
-    val[s] = e < E ? x[e] : -INFINITY;
-    m = fmaxf(m, val[s]);
-  }
-  m = wave_max(m);
-  float sum = 0.f;
-#pragma unroll
-  for (int s = 0; s < kEpl; ++s)
-    if (lane + 64 * s < E) sum += expf(val[s] - m);
-  sum = wave_sum(sum);
-
-  // lane j & 63 keeps output j (slot j >> 6) until the sum of the k weights is known
-  float pj[kEpl] = {};
-  int ij[kEpl] = {};
-  unsigned taken = 0;
-  float wsum = 0.f;
-  for (int j = 0; j < k; ++j) {
-    float bv;
-    int bi;
-    wave_best(val, taken, lane, E, bv, bi);
-    if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
-    const float p = expf(bv - m) / sum;
-    wsum += p;  // in order j = 0 .. k - 1, the same in every lane
-    if ((j & 63) == lane) {
-#pragma unroll
-      for (int s = 0; s < kEpl; ++s)
-        if ((j >> 6) == s) { pj[s] = p; ij[s] = bi; }
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < kEpl; ++s) {
-    const int j = lane + 64 * s;
-    if (j < k) {
-      weights[t * k + j] = renorm ? pj[s] / wsum : pj[s];
-      indices[t * k + j] = ij[s];
-    }
-  }
+  route_topk_softmax_wave(logits + t * E, weights + t * k, indices + t * k, lane, E, k, renorm);
 }
-
-struct GroupedSmem {
-  float c[kRouteWaves][kMaxRouteExperts];      // biased scores
-  float gscore[kRouteWaves][kMaxRouteExperts / 2];
-  int gkeep[kRouteWaves][kMaxRouteExperts / 2];
-};
 
 __global__ void __launch_bounds__(64 * kRouteWaves)
 grouped_topk_sigmoid_kernel(const float* __restrict__ logits, const float* __restrict__ bias,
@@ -120,63 +33,8 @@ grouped_topk_sigmoid_kernel(const float* __restrict__ logits, const float* __res
   int64_t t = (int64_t)blockIdx.x * kRouteWaves + wv;
   const bool live = t < T;
   if (!live) t = T - 1;  // duplicate work, never stored: every wave reaches the barriers
-  const float* x = logits + t * E;
-  const int gsz = E / n_groups;
-  float s[kEpl], val[kEpl];
-#pragma unroll
-  for (int q = 0; q < kEpl; ++q) {
-    const int e = lane + 64 * q;
-    s[q] = 0.f;
-    val[q] = -INFINITY;
-    if (e < E) {
-      s[q] = 1.0f / (1.0f + expf(-x[e]));
-      val[q] = s[q] + bias[e];
-      sm.c[wv][e] = val[q];
-    }
-  }
-  __syncthreads();
-  // group score: the sum of the group's two largest biased scores
-  for (int g = lane; g < n_groups; g += 64) {
-    float a = -INFINITY, b = -INFINITY;  // a >= b
-    for (int i = 0; i < gsz; ++i) {
-      const float v = sm.c[wv][g * gsz + i];
-      if (v > a) { b = a; a = v; }
-      else if (v > b) b = v;
-    }
-    sm.gscore[wv][g] = a + b;
-  }
-  __syncthreads();
-  // a group is kept when fewer than topk_group groups rank before it (ties: the lower group first)
-  for (int g = lane; g < n_groups; g += 64) {
-    const float me = sm.gscore[wv][g];
-    int before = 0;
-    for (int h = 0; h < n_groups; ++h) before += ranks_before(sm.gscore[wv][h], h, me, g) ? 1 : 0;
-    sm.gkeep[wv][g] = before < topk_group ? 1 : 0;
-  }
-  __syncthreads();
-  unsigned taken = 0;
-#pragma unroll
-  for (int q = 0; q < kEpl; ++q) {
-    const int e = lane + 64 * q;
-    if (e >= E || !sm.gkeep[wv][e / gsz]) taken |= 1u << q;  // masked out: never a candidate
-  }
-  for (int j = 0; j < k; ++j) {
-    float bv;
-    int bi;
-    wave_best(val, taken, lane, E, bv, bi);
-    if (bi == kNoIdx) break;  // k <= kept experts is checked on the host
-    if ((bi & 63) == lane) {
-      taken |= 1u << (bi >> 6);
-      if (live) {
-        float sv = 0.f;
-#pragma unroll
-        for (int q = 0; q < kEpl; ++q)
-          if ((bi >> 6) == q) sv = s[q];
-        weights[t * k + j] = sv * scaling;
-        indices[t * k + j] = bi;
-      }
-    }
-  }
+  route_grouped_sigmoid_wave(logits + t * E, bias, sm, wv, weights + t * k, indices + t * k, live, lane, E, n_groups,
+                             topk_group, k, scaling);
 }
 
 // ---- align ------------------------------------------------------------------------------------
@@ -280,8 +138,8 @@ moe_sum_kernel(uint16_t* __restrict__ out, const uint16_t* __restrict__ in, cons
 }
 
 int route_check(const float* logits, const float* weights, const int32_t* indices, int64_t T, int32_t E, int32_t k) {
-  if (T < 0 || E < 1 || k < 1 || k > E) return SLM_ERR_INVALID_ARG;
-  if (!is_pow2(E) || E > kMaxRouteExperts) return SLM_ERR_UNSUPPORTED;
+  const int rc = route_shape_check(T, E, k);
+  if (rc != SLM_OK) return rc;
   if (T > 0 && (!logits || !weights || !indices)) return SLM_ERR_INVALID_ARG;
   return SLM_OK;
 }
@@ -315,9 +173,7 @@ SLM_API int slm_moe_grouped_topk_sigmoid(const float* logits, const float* corre
   using namespace slm;
   const int rc = route_check(logits, weights, indices, n_tokens, n_experts, topk);
   if (rc != SLM_OK) return rc;
-  if (n_expert_groups < 1 || n_experts % n_expert_groups || n_experts / n_expert_groups < 2 || topk_group < 1 ||
-      topk_group > n_expert_groups || (int64_t)topk > (int64_t)topk_group * (n_experts / n_expert_groups))
-    return SLM_ERR_INVALID_ARG;
+  if (route_groups_check(n_experts, n_expert_groups, topk_group, topk) != SLM_OK) return SLM_ERR_INVALID_ARG;
   if (n_tokens == 0) return SLM_OK;
   if (!correction_bias) return SLM_ERR_INVALID_ARG;
   hip_clear_error();

@@ -205,6 +205,57 @@ void moe_fp8_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w8, const
   check(slm_moe_fp8_gemm(&g, stream_of(a)), "slm_moe_fp8_gemm");
 }
 
+void moe_router(const torch::Tensor& x, const torch::Tensor& gate_weight, torch::Tensor& topk_weights,
+                torch::Tensor& topk_indices, const std::string& scoring, bool renormalize,
+                const torch::Tensor& correction_bias, int64_t n_expert_groups, int64_t topk_group,
+                double scaling_factor, const torch::Tensor& logits_out) {
+  TORCH_CHECK(scoring == "softmax" || scoring == "grouped_sigmoid", "slm moe: unknown scoring ", scoring);
+  TORCH_CHECK(x.is_cuda() && gate_weight.is_cuda() && x.dim() == 2 && gate_weight.dim() == 2 && x.stride(1) == 1 &&
+                  gate_weight.stride(1) == 1 && x.size(1) == gate_weight.size(1),
+              "slm moe: router takes GPU x [n_tokens, hidden] and gate_weight [n_experts, hidden], contiguous rows");
+  TORCH_CHECK(x.scalar_type() == gate_weight.scalar_type(), "slm moe: x and gate_weight must share a dtype");
+  const int64_t T = x.size(0), H = x.size(1), E = gate_weight.size(0);
+  TORCH_CHECK(topk_weights.is_cuda() && topk_weights.scalar_type() == torch::kFloat && topk_weights.is_contiguous() &&
+                  topk_weights.dim() == 2 && topk_weights.size(0) == T,
+              "slm moe: topk_weights must be contiguous fp32 [n_tokens, topk]");
+  check_i32(topk_indices, "topk_indices");
+  TORCH_CHECK(topk_indices.sizes() == topk_weights.sizes(),
+              "slm moe: topk_indices must have the shape of topk_weights");
+  slm_moe_router_args a{};
+  a.x = x.data_ptr();
+  a.gate_w = gate_weight.data_ptr();
+  if (correction_bias.defined()) {
+    TORCH_CHECK(correction_bias.is_cuda() && correction_bias.scalar_type() == torch::kFloat &&
+                    correction_bias.is_contiguous() && correction_bias.numel() == E,
+                "slm moe: correction_bias must be contiguous fp32 [n_experts]");
+    a.correction_bias = correction_bias.const_data_ptr<float>();
+  }
+  a.weights = topk_weights.data_ptr<float>();
+  a.indices = topk_indices.data_ptr<int32_t>();
+  if (logits_out.defined()) {
+    TORCH_CHECK(logits_out.is_cuda() && logits_out.scalar_type() == torch::kFloat && logits_out.is_contiguous() &&
+                    logits_out.dim() == 2 && logits_out.size(0) == T && logits_out.size(1) == E,
+                "slm moe: logits_out must be contiguous fp32 [n_tokens, n_experts]");
+    a.logits_out = logits_out.data_ptr<float>();
+  }
+  a.n_tokens = T;
+  a.hidden = H;
+  a.ldx = T > 1 ? x.stride(0) : std::max(x.stride(0), H);
+  a.ldw = E > 1 ? gate_weight.stride(0) : std::max(gate_weight.stride(0), H);
+  a.n_experts = static_cast<int32_t>(E);
+  a.topk = static_cast<int32_t>(topk_weights.size(1));
+  a.dtype = dtype_code(x);
+  a.scoring = scoring == "softmax" ? 0 : 1;
+  a.renormalize = renormalize ? 1 : 0;
+  a.n_expert_groups = static_cast<int32_t>(n_expert_groups);
+  a.topk_group = static_cast<int32_t>(topk_group);
+  a.scaling_factor = static_cast<float>(scaling_factor);
+  size_t need = 0;
+  check(slm_moe_router_workspace_bytes(T, a.n_experts, H, a.dtype, &need), "slm_moe_router_workspace_bytes");
+  TORCH_CHECK(need == 0, "slm moe: the router plans a workspace this shim does not hold");
+  check(slm_moe_router(&a, stream_of(x)), "slm_moe_router");
+}
+
 }  // namespace slm
 
 namespace llm::kernel {

@@ -9,6 +9,7 @@
 //                              src/kernels/gemm/, is a dense fp16 / bf16 kernel; int4 experts have no counterpart).
 //   slm::moe_grouped_gemm      that dense fp16 / bf16 grouped GEMM over W[e, n, k].
 //   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm_fp8.hip).
+//   slm::moe_router            the fused router: gate GEMM + routing in one launch (section 17, csrc/moe_router.hip).
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
 #pragma once
@@ -77,5 +78,13 @@ void moe_fp8_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w8, const
                           torch::Tensor& c, const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
                           const torch::Tensor& n_padded_tokens, int64_t a_div, const torch::Tensor& row_scale,
                           bool silu_mul);
+
+// logits = x [T, hidden] . gate_weight [E, hidden]^T in fp32 and their routing, in one launch: scoring "softmax"
+// (renormalize) or "grouped_sigmoid" (correction_bias, n_expert_groups, topk_group, scaling_factor); topk is
+// topk_weights.size(1).  correction_bias / logits_out (fp32 [T, E]) may be undefined tensors.
+void moe_router(const torch::Tensor& x, const torch::Tensor& gate_weight, torch::Tensor& topk_weights,
+                torch::Tensor& topk_indices, const std::string& scoring, bool renormalize,
+                const torch::Tensor& correction_bias, int64_t n_expert_groups, int64_t topk_group,
+                double scaling_factor, const torch::Tensor& logits_out);
 
 }  // namespace slm

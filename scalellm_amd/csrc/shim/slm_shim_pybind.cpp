@@ -311,6 +311,18 @@ PYBIND11_MODULE(_slm_shim, m) {
         }, py::arg("a"), py::arg("w8"), py::arg("w_scale"), py::arg("c"), py::arg("sorted_token_idxes"),
         py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(),
         py::arg("silu_mul") = false);
+  m.def("moe_router",
+        [](const torch::Tensor& x, const torch::Tensor& gate_weight, torch::Tensor topk_weights,
+           torch::Tensor topk_indices, const std::string& scoring, bool renormalize,
+           const c10::optional<torch::Tensor>& correction_bias, int64_t n_expert_groups, int64_t topk_group,
+           double scaling_factor, const c10::optional<torch::Tensor>& logits_out) {
+          slm::moe_router(x, gate_weight, topk_weights, topk_indices, scoring, renormalize,
+                          correction_bias.has_value() ? *correction_bias : torch::Tensor(), n_expert_groups,
+                          topk_group, scaling_factor, logits_out.has_value() ? *logits_out : torch::Tensor());
+        }, py::arg("x"), py::arg("gate_weight"), py::arg("topk_weights"), py::arg("topk_indices"),
+        py::arg("scoring") = "softmax", py::arg("renormalize") = true, py::arg("correction_bias") = py::none(),
+        py::arg("n_expert_groups") = 1, py::arg("topk_group") = 1, py::arg("scaling_factor") = 1.0,
+        py::arg("logits_out") = py::none());
   // MoE token permutation (slm_permute_hip.h): the reference's four functions
   m.def("moe_permute_with_index_map", &llm::kernel::moe::permute_with_index_map, py::arg("tokens"),
         py::arg("indices"));

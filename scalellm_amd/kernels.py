@@ -1520,6 +1520,68 @@ def moe_grouped_topk_sigmoid(logits: torch.Tensor, correction_bias: torch.Tensor
     return weights, indices
 
 
+def moe_router_splits(n_experts: int, hidden: int, dtype: torch.dtype) -> int:
+    """The K slices slm_moe_router spreads a row tile over: a function of (E, hidden, dtype), never of T."""
+    s = C.c_int32(0)
+    code = SLM_BF16 if dtype == torch.bfloat16 else SLM_F16 if dtype == torch.float16 else _lib.SLM_F32
+    check(_lib.lib().slm_moe_router_splits(n_experts, hidden, code, C.byref(s)), "slm_moe_router_splits")
+    return s.value
+
+
+def moe_router(x: torch.Tensor, gate_weight: torch.Tensor, topk: int, *, scoring: str = "softmax",
+               renormalize: bool = True, correction_bias: Optional[torch.Tensor] = None, n_expert_groups: int = 1,
+               topk_group: int = 1, scaling_factor: float = 1.0, weights: Optional[torch.Tensor] = None,
+               indices: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None):
+    """The fused router (slm_hip.h section 17): logits = x [T, hidden] . gate_weight [E, hidden]^T in fp32 and the
+    routing of moe_topk_softmax (scoring = "softmax") or moe_grouped_topk_sigmoid ("grouped_sigmoid") on them, in
+    one launch.  x and gate_weight are f16 / bf16 with contiguous rows (row strides may be padded; gate_weight is
+    the checkpoint tensor, no transpose, no fp32 copy).  logits_out: optional contiguous fp32 [T, E] that receives
+    the logits.  A token's result depends on that token alone.  Returns (weights, indices)."""
+    _require_gpu(x, gate_weight, correction_bias, weights, indices, logits_out)
+    if scoring not in ("softmax", "grouped_sigmoid"):
+        raise SlmError(f"unknown scoring {scoring}")
+    if x.dim() != 2 or gate_weight.dim() != 2 or x.stride(1) != 1 or gate_weight.stride(1) != 1 or \
+            x.size(1) != gate_weight.size(1):
+        raise SlmError("moe_router: x [T, hidden] and gate_weight [E, hidden] with contiguous rows")
+    if x.dtype != gate_weight.dtype:
+        raise SlmError("moe_router: x and gate_weight must share one dtype")
+    T, H = x.shape
+    E = gate_weight.size(0)
+    if weights is None:
+        weights = torch.empty(T, topk, dtype=torch.float32, device=x.device)
+    if indices is None:
+        indices = torch.empty(T, topk, dtype=torch.int32, device=x.device)
+    for t, dt, shape, name in ((weights, torch.float32, (T, topk), "weights"),
+                               (indices, torch.int32, (T, topk), "indices"),
+                               (logits_out, torch.float32, (T, E), "logits_out")):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise SlmError(f"moe_router: {name} must be contiguous {dt} {list(shape)}")
+    if correction_bias is not None and (correction_bias.dtype != torch.float32 or
+                                        not correction_bias.is_contiguous() or correction_bias.numel() != E):
+        raise SlmError("correction_bias must be contiguous fp32 [n_experts]")
+    if scoring == "grouped_sigmoid" and correction_bias is None:
+        raise SlmError("moe_router: grouped_sigmoid needs correction_bias")
+    a = _lib.MoeRouterArgs()
+    a.x, a.gate_w = x.data_ptr(), gate_weight.data_ptr()
+    a.correction_bias = correction_bias.data_ptr() if correction_bias is not None else None
+    a.weights, a.indices = weights.data_ptr(), indices.data_ptr()
+    a.logits_out = logits_out.data_ptr() if logits_out is not None else None
+    a.n_tokens, a.hidden = T, H
+    a.ldx = x.stride(0) if T > 1 else max(x.stride(0), H)
+    a.ldw = gate_weight.stride(0) if E > 1 else max(gate_weight.stride(0), H)
+    a.n_experts, a.topk, a.dtype = E, topk, _dtype_code(x)
+    a.scoring = _lib.SLM_ROUTER_SOFTMAX if scoring == "softmax" else _lib.SLM_ROUTER_GROUPED_SIGMOID
+    a.renormalize = 1 if renormalize else 0
+    a.n_expert_groups, a.topk_group, a.scaling_factor = n_expert_groups, topk_group, float(scaling_factor)
+    need = C.c_size_t(0)
+    check(_lib.lib().slm_moe_router_workspace_bytes(T, E, H, a.dtype, C.byref(need)), "slm_moe_router_workspace_bytes")
+    if need.value:
+        ws = reserve_workspace(need.value, x.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(_lib.lib().slm_moe_router(C.byref(a), _stream()), "slm_moe_router")
+    return weights, indices
+
+
 def moe_align_capacity(n_flat: int, n_experts: int, block_size: int):
     """(max_padded, max_blocks): the worst case of moe_align_block's outputs for n_flat = T * k assignments."""
     mp, mb = C.c_int64(0), C.c_int64(0)

@@ -4,6 +4,7 @@ block alignment, two grouped GEMMs and the sum over a token's experts, every ste
 
     FusedMoE.forward(x):  router logits (fp32, torch: [T, hidden] x [hidden, E] is tiny)
                           -> moe_topk_softmax | moe_grouped_topk_sigmoid      (weights, expert ids)
+                             (router="fused": both in ONE launch, kernels.moe_router, slm_hip.h section 17)
                           -> moe_align_block (32-row blocks per expert)
                           -> grouped GEMM gate_up, SiLU * mul epilogue        [T * k, intermediate]
                           -> grouped GEMM down, routing weight on the fp32 accumulator [T * k, hidden]
@@ -262,9 +263,12 @@ class FusedMoE:
                  quant_args: Optional[QuantArgs] = None,
                  scoring: str = "softmax", renormalize: bool = True, n_expert_groups: int = 1, topk_group: int = 1,
                  scaling_factor: float = 1.0, max_tokens: int = 256, dtype: torch.dtype = torch.bfloat16,
-                 device="cuda"):
+                 device="cuda", router: str = "torch"):
         if scoring not in ("softmax", "grouped_sigmoid"):
             raise SlmError(f"unknown scoring {scoring}")
+        if router not in ("torch", "fused"):
+            raise SlmError(f"unknown router {router}: 'torch' or 'fused'")
+        self.router = router
         if not 1 <= topk <= n_experts:
             raise SlmError(f"topk = {topk} must be in 1 .. n_experts = {n_experts}")
         self.hidden, self.intermediate, self.n_experts, self.topk = hidden, intermediate, n_experts, topk
@@ -301,7 +305,11 @@ class FusedMoE:
             )
         return self._buf
 
-    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
+                router_logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """router_logits_out (router="fused" only): contiguous fp32 [T, n_experts] that receives the router logits"""
+        if router_logits_out is not None and self.router != "fused":
+            raise SlmError("router_logits_out needs router='fused'")
         if self.experts.gate_up is None:
             self.experts.repack()
         if self.gate_weight is None:
@@ -315,8 +323,6 @@ class FusedMoE:
         if T == 0:
             return out.view(x.shape)
         b = self._buffers()
-        if self._gate_f32_t is None:
-            self._gate_f32_t = self.gate_weight.float().t().contiguous()
         n_flat = T * k
         # the worst case for THIS batch: views of the buffers sized for max_tokens
         max_padded, max_blocks = kernels.moe_align_capacity(n_flat, self.n_experts, kernels.MOE_GEMM_BLOCK)
@@ -324,14 +330,23 @@ class FusedMoE:
         srt, eids = b["sorted"][:max_padded], b["expert_ids"][:max_blocks]
         act, down = b["act"][:n_flat], b["down"][:n_flat]
 
-        logits = x2.float() @ self._gate_f32_t
-        if self.scoring == "softmax":
-            kernels.moe_topk_softmax(logits, k, self.renormalize, weights, ids)
+        if self.scoring != "softmax" and self.correction_bias is None:
+            raise SlmError("gate.e_score_correction_bias is not loaded")
+        if self.router == "fused":   # gate GEMM + routing: one launch, no fp32 copy of the gate
+            kernels.moe_router(x2, self.gate_weight, k, scoring=self.scoring, renormalize=self.renormalize,
+                               correction_bias=self.correction_bias if self.scoring != "softmax" else None,
+                               n_expert_groups=self.n_expert_groups, topk_group=self.topk_group,
+                               scaling_factor=self.scaling_factor, weights=weights, indices=ids,
+                               logits_out=router_logits_out)
         else:
-            if self.correction_bias is None:
-                raise SlmError("gate.e_score_correction_bias is not loaded")
-            kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups, self.topk_group, k,
-                                             self.scaling_factor, weights, ids)
+            if self._gate_f32_t is None:
+                self._gate_f32_t = self.gate_weight.float().t().contiguous()
+            logits = x2.float() @ self._gate_f32_t
+            if self.scoring == "softmax":
+                kernels.moe_topk_softmax(logits, k, self.renormalize, weights, ids)
+            else:
+                kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups, self.topk_group,
+                                                 k, self.scaling_factor, weights, ids)
         kernels.moe_align_block(ids, self.n_experts, kernels.MOE_GEMM_BLOCK, srt, eids, b["n_padded"])
         self.experts.gemm("gate_up", x2, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
         self.experts.gemm("down", act, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
@@ -510,9 +525,12 @@ class ExpertParallelMoE:
     def __init__(self, hidden: int, intermediate: int, n_experts: int, topk: int, process_group,
                  quant_args: Optional[QuantArgs] = None, scoring: str = "softmax", renormalize: bool = True,
                  n_expert_groups: int = 1, topk_group: int = 1, scaling_factor: float = 1.0,
-                 dtype: torch.dtype = torch.bfloat16, device="cuda"):
+                 dtype: torch.dtype = torch.bfloat16, device="cuda", router: str = "torch"):
         if scoring not in ("softmax", "grouped_sigmoid"):
             raise SlmError(f"unknown scoring {scoring}")
+        if router not in ("torch", "fused"):
+            raise SlmError(f"unknown router {router}: 'torch' or 'fused'")
+        self.router = router
         if not 1 <= topk <= n_experts:
             raise SlmError(f"topk = {topk} must be in 1 .. n_experts = {n_experts}")
         self.dispatcher = AlltoAllTokenDispatcher(n_experts, topk, process_group)
@@ -559,16 +577,22 @@ class ExpertParallelMoE:
         if self.gate_weight is None:
             raise SlmError("gate.weight is not loaded")
         x2 = x.reshape(-1, self.hidden).contiguous()
-        if self._gate_f32_t is None:
-            self._gate_f32_t = self.gate_weight.float().t().contiguous()
-        logits = x2.float() @ self._gate_f32_t
-        if self.scoring == "softmax":
-            weights, ids = kernels.moe_topk_softmax(logits, self.topk, self.renormalize)
+        if self.scoring != "softmax" and self.correction_bias is None:
+            raise SlmError("gate.e_score_correction_bias is not loaded")
+        if self.router == "fused":
+            weights, ids = kernels.moe_router(
+                x2, self.gate_weight, self.topk, scoring=self.scoring, renormalize=self.renormalize,
+                correction_bias=self.correction_bias if self.scoring != "softmax" else None,
+                n_expert_groups=self.n_expert_groups, topk_group=self.topk_group, scaling_factor=self.scaling_factor)
         else:
-            if self.correction_bias is None:
-                raise SlmError("gate.e_score_correction_bias is not loaded")
-            weights, ids = kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups,
-                                                            self.topk_group, self.topk, self.scaling_factor)
+            if self._gate_f32_t is None:
+                self._gate_f32_t = self.gate_weight.float().t().contiguous()
+            logits = x2.float() @ self._gate_f32_t
+            if self.scoring == "softmax":
+                weights, ids = kernels.moe_topk_softmax(logits, self.topk, self.renormalize)
+            else:
+                weights, ids = kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups,
+                                                                self.topk_group, self.topk, self.scaling_factor)
         rows, tokens_per_local_expert = self.dispatcher.dispatch_topk(x2, weights, ids)
         return self.dispatcher.combine(self._experts_forward(rows, tokens_per_local_expert)).view(x.shape)
 
