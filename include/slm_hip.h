@@ -1270,7 +1270,7 @@ SLM_API int slm_unpermute_rows(void* out, const void* permuted, const int32_t* r
 /*    13's.  With SLM_LINEAR_SILU_MUL  g = T(y + bias), u = T(y' + bias'):    */
 /*    the bits of the plain call followed by slm_silu_mul.                    */
 /*    Knobs: SLM_LINEAR_SPLITK / _RT / _NW force the form of this entry too;  */
-/*    it has none of its own (csrc/dense_fp8.hip).                            */
+/*    it has none of its own (csrc/dense.hip).                                */
 /* ========================================================================== */
 typedef struct slm_fp8_linear_args {
   const void* a;        /* [M, K] T, row stride lda                           */

@@ -1,16 +1,21 @@
-// dense.hip -- unquantised f16 / bf16 linear over checkpoint-layout weights (include/slm_hip.h section 13,
-// slm_linear; the reference's {Column,Row}ParallelLinearImpl::forward = F::linear, src/layers/linear/
-// parallel_linear.cpp):   C[M, N] = T( A[M, K] . W[N, K]^T + bias[N] ).
+// dense.hip -- the weight-stream linears over checkpoint-layout weights, one kernel for both weight sides:
+//  * slm_linear (include/slm_hip.h section 13): unquantised f16 / bf16 weights; the reference's
+//    {Column,Row}ParallelLinearImpl::forward = F::linear, src/layers/linear/parallel_linear.cpp:
+//      C[M, N] = T( A[M, K] . W[N, K]^T + bias[N] )
+//  * slm_fp8_linear (section 15): fp8 (e4m3fn) weight-only; the reference's marlin::fp8_gemm,
+//    src/kernels/quantization/marlin.h:39-43, which reads a Marlin-repacked B -- this kernel reads the checkpoint
+//    tensor as it is:
+//      C[M, N] = T( (A[M, K] . e4m3(W[N, K])^T) * w_scale[N] + bias[N] )
 //
 // The weight stream is moe_gemm.hip's: W[n, :] is k-contiguous and that IS an operand of the 32x32x16 MFMA
 // (lane (n = lane & 31, h = lane >> 5) holds 8 consecutive k of row n), so the weights go from global memory
 // to the MFMA in 16-B loads: no LDS stage, no transpose, no prepack.  K is streamed in 128-deep chunks, lane
-// half h takes k = [64 h, 64 h + 64) of the chunk (128 contiguous bytes of row n); A's fragments come from a
+// half h takes k = [64 h, 64 h + 64) of the chunk (contiguous bytes of row n); A's fragments come from a
 // [rows][128 k] LDS image of the chunk in natural k order with w4_stream32.h's XOR swizzle.  A K that is no
 // multiple of 128 ends in up to three 32-deep units in natural order.
 //
 // What differs from the grouped kernel:
-//  * RT = 1 / 2 / 4 accumulator tiles of 32 rows per wave: every 16-B weight fragment feeds RT MFMAs, so the
+//  * RT = 1 / 2 / 4 accumulator tiles of 32 rows per wave: every weight fragment feeds RT MFMAs, so the
 //    weights are streamed once for M <= 32 RT.  More rows go to further row blocks of the grid (blockIdx.z),
 //    which stream the weights again: correct, not tuned (prefill is not this kernel's job).
 //  * the operands are swapped (weights = MFMA A, activations = MFMA B): the accumulator tile is C^T, lane
@@ -33,8 +38,30 @@
 // 3-chunk register ring, written to the other LDS buffer one iteration before its use.  VMEM completes in
 // order, so the A chunk that is waited for is two iterations old and the wait leaves two weight chunks in
 // flight.  Loads past the slice's last chunk are clamped to it and never used.
+//
+// The weight side is the kernel parameter struct's compile-time choice (KP::FP8); it sets three things:
+//  * T weights: a lane's 64 k of a chunk are 128 bytes of row n, eight 16-B loads; load q IS the weight fragment
+//    of MFMA step q.  A tail unit is two loads per lane half.
+//  * e4m3 weights: the 64 k are 64 BYTES, four 16-B loads.  Load j holds k = 64 h + 16 j .. + 16, the fragments of
+//    the two steps 2 j (dwords 0, 1) and 2 j + 1 (dwords 2, 3); a dword's low half is its lower k pair.  e4m3 -> T
+//    is exact, two weights per v_cvt_scalef32_pk_{bf16,f16}_fp8 with scale 1.0 (fp8_cvt.h): step q sees exactly
+//    the k -- and the T values -- it sees on T(W), so under the same (RT, NW, split) the accumulators are the T
+//    side's bit for bit.  A tail unit is one load per lane half.
+//  * e4m3 only: y = acc * w_scale[n] in front of the epilogue (never the converter's scale operand), one fp32
+//    multiply kept out of any contraction with the bias add; a K slice stores y into its slab, so the reduce kernel
+//    and the deferred consumers see what a T call leaves.
+//
+// Ring depth: LIN_RING = 3 chunks for both weight sides, although a chunk of e4m3 is half the bytes in flight.  It
+// is the depth of BOTH register rings, and the A ring costs 4 P VGPRs a chunk (P = 8 RT / NW 16-B pieces per thread)
+// beside the weight ring's 32 or 16.  A six-chunk ring was built for the e4m3 forms with NW >= 2 RT (P <= 4; 264
+// VGPRs at RT 1 x NW 2, one wave per SIMD) and measured on gate_up: 33.8 / 38.4 us at M = 1 / 32 against 29.6 / 35.6
+// for three chunks (profiles/r17_fp8_ring_ab.jsonl), so it is not in the tree.  No result bit depends on the depth:
+// a wave's MFMAs run in chunk order at any depth.
+#include <type_traits>
+
 #include "common.h"
 #include "dense_plan.h"
+#include "fp8_cvt.h"
 #include "tuning.h"
 
 namespace slm {
@@ -42,6 +69,7 @@ namespace slm {
 constexpr int LIN_RING = 3;   // weight / A register rings (chunks)
 
 struct LinearKParams {
+  static constexpr bool FP8 = false;
   const char* a;
   const char* w;
   const void* bias;  // [N] T or NULL
@@ -56,9 +84,30 @@ struct LinearKParams {
   int slice_chunk[LIN_MAX_SPLIT + 1];
 };
 
-template <typename T, int RT, int NW>
-__global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) {
+struct Fp8LinearKParams {
+  static constexpr bool FP8 = true;
+  const char* a;
+  const char* w;
+  const float* w_scale;  // [N] or NULL (1.0)
+  const void* bias;      // [N] T or NULL
+  void* c;
+  float* part;           // [split_k][M][N] or NULL (split_k == 1)
+  int64_t lda, ldw, ldc;  // elements (ldw: bytes)
+  int M, N;
+  int n_tiles;       // N / 32
+  int tail_units;    // (K % 128) / 32
+  int split_k;
+  int silu;
+  int slice_chunk[LIN_MAX_SPLIT + 1];
+};
+
+template <typename T, int RT, int NW, typename KP>
+__global__ void __launch_bounds__(NW * 64) linear_kernel(const KP p) {
   typedef typename Mfma<T>::frag frag_t;
+  constexpr bool FP8 = KP::FP8;
+  constexpr int WB = FP8 ? 1 : 2;  // bytes per weight
+  constexpr int WL = 4 * WB;       // 16-B weight loads per lane and chunk
+  constexpr int SPL = 2 / WB;      // MFMA steps (8 k) a 16-B weight load holds
   constexpr int NT = NW * 64;
   constexpr int ROWS = RT * 32;
   constexpr int STAGE = ROWS * 256;  // one chunk of A: ROWS x 128 k
@@ -92,7 +141,8 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
   const int c0 = p.slice_chunk[ks];
   const int nC = p.slice_chunk[ks + 1] - c0;
   const int tail_units = ks == p.split_k - 1 ? p.tail_units : 0;
-  const uint32_t kbase = (uint32_t)c0 * 256u;  // bytes into a row
+  const uint32_t a_kbase = (uint32_t)c0 * 256u;         // bytes into a row of A
+  const uint32_t w_kbase = (uint32_t)c0 * (128u * WB);  // bytes into a row of W
 
   // ---- A: this thread's P (row, 16-B slot) sources of a chunk; rows beyond M are clamped, never stored ----
   const char* a_src[P];
@@ -104,10 +154,10 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
     const int row = idx >> 4, slot = idx & 15;
     int gr = row0 + row;
     gr = gr < p.M ? gr : p.M - 1;
-    a_src[i] = p.a + 2 * ((int64_t)gr * p.lda + slot * 8) + kbase;
+    a_src[i] = p.a + 2 * ((int64_t)gr * p.lda + slot * 8) + a_kbase;
     a_dst[i] = stage_swz(row, slot);
   }
-  const char* wlane = p.w + 2 * (((int64_t)nt * 32 + mrow) * p.ldw) + kbase;
+  const char* wlane = p.w + WB * (((int64_t)nt * 32 + mrow) * p.ldw) + w_kbase;
   const int a_row = mrow * 256;
   const int a_swz = mrow & 15;
 
@@ -121,7 +171,7 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
     const int last = nC - 1;
     auto clampc = [&](int c) { return c < last ? c : last; };
     u32x4 areg[LIN_RING][P];
-    u32x4 wreg[LIN_RING][8];
+    u32x4 wreg[LIN_RING][WL];
     auto a_load = [&](int c, u32x4 (&dst)[P]) {
       const uint32_t off = (uint32_t)clampc(c) * 256u;
 #pragma unroll
@@ -131,12 +181,12 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
 #pragma unroll
       for (int i = 0; i < P; ++i) *reinterpret_cast<u32x4*>(smem + stage * STAGE + a_dst[i]) = src[i];
     };
-    // lane half kh: the 128 contiguous bytes [kh * 128, kh * 128 + 128) of the chunk's 256 B of row n
-    const char* wl = wlane + kh * 128;
-    auto w_load = [&](int c, u32x4 (&w)[8]) {
-      const uint32_t off = (uint32_t)clampc(c) * 256u;
+    // lane half kh: the 64 WB contiguous bytes [kh * 64 WB, kh * 64 WB + 64 WB) of the chunk's 128 WB bytes of row n
+    const char* wl = wlane + kh * (64 * WB);
+    auto w_load = [&](int c, u32x4 (&w)[WL]) {
+      const uint32_t off = (uint32_t)clampc(c) * (128u * WB);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) w[q] = *reinterpret_cast<const u32x4*>(wl + off + q * 16);
+      for (int j = 0; j < WL; ++j) w[j] = *reinterpret_cast<const u32x4*>(wl + off + j * 16);
     };
 
     // prologue in the order the steady-state iterations issue (A, then the weights of the same chunk)
@@ -159,19 +209,23 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
 #pragma unroll
       for (int u = 0; u < LIN_RING; ++u) {
         const int i = base + u;  // chunk; ring slot u
-        // A for chunk i + 3 into the registers chunk i left (stored one iteration ago)
+        // A for chunk i + LIN_RING into the registers chunk i left (stored one iteration ago)
         a_load(i + LIN_RING, areg[u]);
         __builtin_amdgcn_sched_barrier(0);
         if (i < nC) {
           const char* sbase = smem + stage * STAGE + a_row;
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const frag_t wf = __builtin_bit_cast(frag_t, wreg[u][q]);
+          for (int j = 0; j < WL; ++j) {
 #pragma unroll
-            for (int t = 0; t < RT; ++t) {
-              const frag_t af = __builtin_bit_cast(
-                  frag_t, *reinterpret_cast<const u32x4*>(sbase + t * (32 * 256) + (((kh * 8 + q) ^ a_swz) << 4)));
-              acc[t] = Mfma<T>::run(wf, af, acc[t]);
+            for (int h = 0; h < SPL; ++h) {
+              const int q = j * SPL + h;  // MFMA step q: k = 64 kh + 8 q .. + 8 of the chunk
+              const frag_t wf = step_frag<T, FP8>(wreg[u][j], h);
+#pragma unroll
+              for (int t = 0; t < RT; ++t) {
+                const frag_t af = __builtin_bit_cast(
+                    frag_t, *reinterpret_cast<const u32x4*>(sbase + t * (32 * 256) + (((kh * 8 + q) ^ a_swz) << 4)));
+                acc[t] = Mfma<T>::run(wf, af, acc[t]);
+              }
             }
           }
         }
@@ -179,7 +233,7 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
         __builtin_amdgcn_sched_barrier(0);
         w_load(i + LIN_RING, wreg[u]);
         __builtin_amdgcn_sched_barrier(0);
-        // chunk i + 1 (loaded two iterations ago) -> the buffer everybody finished reading one barrier ago
+        // chunk i + 1 (loaded LIN_RING - 1 iterations ago) -> the buffer everybody finished reading one barrier ago
         a_store(stage ^ 1, areg[(u + 1) % LIN_RING]);
         __syncthreads();
         stage ^= 1;
@@ -189,27 +243,33 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
 
   // ---- K % 128 (last slice): up to three 32-deep units in natural k order, one at a time ----
   if (tail_units > 0) {
-    const uint32_t koff = (uint32_t)nC * 256u;  // bytes behind the slice's chunks
-    __syncthreads();                            // nobody reads the stages any more
+    const uint32_t a_koff = (uint32_t)nC * 256u;  // bytes of a row of A behind the slice's chunks
+    __syncthreads();                              // nobody reads the stages any more
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       if (a_slot < tail_units * 4)
-        *reinterpret_cast<u32x4*>(smem + a_dst[i]) = *reinterpret_cast<const u32x4*>(a_src[i] + koff);
+        *reinterpret_cast<u32x4*>(smem + a_dst[i]) = *reinterpret_cast<const u32x4*>(a_src[i] + a_koff);
     }
     __syncthreads();
     const char* sbase = smem + a_row;
-    const char* wt = wlane + koff + kh * 32;
+    // lane half kh: k = 16 kh .. + 16 of a unit, WB 16-B loads
+    const char* wt = wlane + (uint32_t)nC * (128u * WB) + kh * (16 * WB);
 #pragma unroll
     for (int t3 = 0; t3 < 3; ++t3) {
       if (t3 < tail_units) {
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const frag_t wf = __builtin_bit_cast(frag_t, *reinterpret_cast<const u32x4*>(wt + t3 * 64 + s * 16));
+        for (int j = 0; j < WB; ++j) {
+          const u32x4 wv = *reinterpret_cast<const u32x4*>(wt + t3 * (32 * WB) + j * 16);
 #pragma unroll
-          for (int t = 0; t < RT; ++t) {
-            const frag_t af = __builtin_bit_cast(
-                frag_t, *reinterpret_cast<const u32x4*>(sbase + t * (32 * 256) + (((t3 * 4 + kh * 2 + s) ^ a_swz) << 4)));
-            acc[t] = Mfma<T>::run(wf, af, acc[t]);
+          for (int h = 0; h < SPL; ++h) {
+            const int s = j * SPL + h;  // step s of the unit: k = 16 kh + 8 s .. + 8
+            const frag_t wf = step_frag<T, FP8>(wv, h);
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+              const frag_t af = __builtin_bit_cast(
+                  frag_t, *reinterpret_cast<const u32x4*>(sbase + t * (32 * 256) + (((t3 * 4 + kh * 2 + s) ^ a_swz) << 4)));
+              acc[t] = Mfma<T>::run(wf, af, acc[t]);
+            }
           }
         }
       }
@@ -219,6 +279,20 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
 
   // ---- epilogue.  C^T layout: lane (m = lane & 31, kh), registers 4 j .. 4 j + 3 = columns 8 j + 4 kh + {0..3}
   const int ncol0 = nt * 32 + 4 * kh;  // + 8 j
+  if constexpr (FP8) {  // y = acc * w_scale[n], in place
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x4 s = {1.f, 1.f, 1.f, 1.f};
+      if (p.w_scale) s = *reinterpret_cast<const f32x4*>(p.w_scale + ncol0 + 8 * j);
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        acc[t][4 * j] = scaled(acc[t][4 * j], s.x);
+        acc[t][4 * j + 1] = scaled(acc[t][4 * j + 1], s.y);
+        acc[t][4 * j + 2] = scaled(acc[t][4 * j + 2], s.z);
+        acc[t][4 * j + 3] = scaled(acc[t][4 * j + 3], s.w);
+      }
+    }
+  }
   if (p.part) {  // a K slice: the fp32 slab, no bias, no rounding
     if (!nvalid) return;
     float* slab = p.part + (int64_t)ks * p.M * p.N;
@@ -292,13 +366,14 @@ __global__ void __launch_bounds__(NW * 64) linear_kernel(const LinearKParams p) 
   }
 }
 
-template <typename T, int RT, int NW>
-static void launch_linear(const LinearKParams& kp, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL((linear_kernel<T, RT, NW>), grid, dim3(NW * 64), 0, st, kp);
+// ---- host: one path for slm_linear_args and slm_fp8_linear_args ----
+template <typename T, int RT, int NW, typename KP>
+static void launch_linear(const KP& kp, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((linear_kernel<T, RT, NW, KP>), grid, dim3(NW * 64), 0, st, kp);
 }
 
-template <typename T>
-static void launch_linear_form(const LinearKParams& kp, int rt, int nw, dim3 grid, hipStream_t st) {
+template <typename T, typename KP>
+static void launch_linear_form(const KP& kp, int rt, int nw, dim3 grid, hipStream_t st) {
   if (rt == 4) launch_linear<T, 4, 4>(kp, grid, st);
   else if (rt == 2 && nw == 4) launch_linear<T, 2, 4>(kp, grid, st);
   else if (rt == 2) launch_linear<T, 2, 2>(kp, grid, st);
@@ -307,12 +382,8 @@ static void launch_linear_form(const LinearKParams& kp, int rt, int nw, dim3 gri
   else launch_linear<T, 1, 1>(kp, grid, st);
 }
 
-}  // namespace slm
-
-extern "C" {
-
-SLM_API int slm_linear_plan(const slm_linear_args* a, slm_linear_plan_info* out) {
-  using namespace slm;
+template <typename Args>
+static int linear_plan_info(const Args* a, slm_linear_plan_info* out) {
   LinearPlan pl;
   if (!out) return SLM_ERR_INVALID_ARG;
   const int rc = plan_linear(a, &pl);
@@ -326,19 +397,22 @@ SLM_API int slm_linear_plan(const slm_linear_args* a, slm_linear_plan_info* out)
   return SLM_OK;
 }
 
-SLM_API size_t slm_linear_workspace_bytes(const slm_linear_args* a) {
-  slm::LinearPlan pl;
-  return slm::plan_linear(a, &pl) == SLM_OK ? (size_t)pl.ws_bytes : 0;
+template <typename Args>
+static size_t linear_workspace_bytes(const Args* a) {
+  LinearPlan pl;
+  return plan_linear(a, &pl) == SLM_OK ? (size_t)pl.ws_bytes : 0;
 }
 
-SLM_API int32_t slm_linear_deferred_splits(const slm_linear_args* a) {
-  slm::LinearPlan pl;
-  return slm::plan_linear(a, &pl) == SLM_OK && (a->flags & SLM_LINEAR_DEFER_REDUCE) && !a->bias && pl.split_k > 1
+template <typename Args>
+static int32_t linear_deferred_splits(const Args* a) {
+  LinearPlan pl;
+  return plan_linear(a, &pl) == SLM_OK && (a->flags & SLM_LINEAR_DEFER_REDUCE) && !a->bias && pl.split_k > 1
              ? pl.split_k : 0;
 }
 
-SLM_API int slm_linear(const slm_linear_args* a, void* stream) {
-  using namespace slm;
+template <typename Args>
+static int run_linear(const Args* a, void* stream) {
+  constexpr bool FP8 = std::is_same<Args, slm_fp8_linear_args>::value;
   LinearPlan pl;
   const int rc = plan_linear(a, &pl);
   if (rc != SLM_OK) return rc;
@@ -347,14 +421,19 @@ SLM_API int slm_linear(const slm_linear_args* a, void* stream) {
   const bool defer = (a->flags & SLM_LINEAR_DEFER_REDUCE) && !a->bias && pl.split_k > 1;
   if (!a->a || !a->w || !a->c) return SLM_ERR_INVALID_ARG;
   if (a->lda < a->K || a->ldw < a->K || a->ldc < (silu ? a->N / 2 : a->N)) return SLM_ERR_INVALID_ARG;
-  if (!aligned16(a->a) || a->lda % 8 || !aligned16(a->w) || a->ldw % 8 || !aligned16(a->c) || a->ldc % 8 ||
+  // a weight row starts on a 16-B boundary: 8 T or 16 e4m3 weights
+  if (!aligned16(a->a) || a->lda % 8 || !aligned16(a->w) || a->ldw % (FP8 ? 16 : 8) || !aligned16(a->c) || a->ldc % 8 ||
       (reinterpret_cast<uintptr_t>(a->bias) & 7u) || !aligned16(a->workspace))
     return SLM_ERR_ALIGNMENT;
+  if constexpr (FP8) {
+    if (!aligned16(a->w_scale)) return SLM_ERR_ALIGNMENT;
+  }
   if (pl.ws_bytes > 0 && (!a->workspace || a->workspace_bytes < pl.ws_bytes)) return SLM_ERR_WORKSPACE;
 
-  LinearKParams kp;
+  typename std::conditional<FP8, Fp8LinearKParams, LinearKParams>::type kp;
   kp.a = reinterpret_cast<const char*>(a->a);
   kp.w = reinterpret_cast<const char*>(a->w);
+  if constexpr (FP8) kp.w_scale = a->w_scale;
   kp.bias = pl.split_k > 1 ? nullptr : a->bias;  // a split call adds it in the reduce
   kp.c = a->c;
   kp.part = pl.split_k > 1 ? reinterpret_cast<float*>(a->workspace) : nullptr;
@@ -376,5 +455,23 @@ SLM_API int slm_linear(const slm_linear_args* a, void* stream) {
   });
   return hip_check_launch();
 }
+
+}  // namespace slm
+
+extern "C" {
+
+SLM_API int slm_linear_plan(const slm_linear_args* a, slm_linear_plan_info* out) {
+  return slm::linear_plan_info(a, out);
+}
+SLM_API size_t slm_linear_workspace_bytes(const slm_linear_args* a) { return slm::linear_workspace_bytes(a); }
+SLM_API int32_t slm_linear_deferred_splits(const slm_linear_args* a) { return slm::linear_deferred_splits(a); }
+SLM_API int slm_linear(const slm_linear_args* a, void* stream) { return slm::run_linear(a, stream); }
+
+SLM_API int slm_fp8_linear_plan(const slm_fp8_linear_args* a, slm_linear_plan_info* out) {
+  return slm::linear_plan_info(a, out);
+}
+SLM_API size_t slm_fp8_linear_workspace_bytes(const slm_fp8_linear_args* a) { return slm::linear_workspace_bytes(a); }
+SLM_API int32_t slm_fp8_linear_deferred_splits(const slm_fp8_linear_args* a) { return slm::linear_deferred_splits(a); }
+SLM_API int slm_fp8_linear(const slm_fp8_linear_args* a, void* stream) { return slm::run_linear(a, stream); }
 
 }  // extern "C"

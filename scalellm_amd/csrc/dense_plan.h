@@ -1,5 +1,6 @@
-// dense_plan.h -- the launch plan the weight-stream linears share (dense.hip: slm_linear, dense_fp8.hip:
-// slm_fp8_linear; include/slm_hip.h sections 13 and 15).  Host only.
+// dense_plan.h -- the launch plan of dense.hip's two entries (slm_linear, slm_fp8_linear; include/slm_hip.h sections
+// 13 and 15), over either argument struct: slm_fp8_linear_args is slm_linear_args, field for field, plus w_scale.
+// Host only.
 #pragma once
 #include "common.h"
 #include "tuning.h"
@@ -18,7 +19,8 @@ struct LinearPlan {
   uint64_t lds_bytes, ws_bytes;
 };
 
-inline int plan_linear(const slm_linear_args* a, LinearPlan* pl) {
+template <typename Args>
+inline int plan_linear(const Args* a, LinearPlan* pl) {
   if (!a) return SLM_ERR_INVALID_ARG;
   if (a->M < 0 || a->K <= 0 || a->N <= 0) return SLM_ERR_INVALID_ARG;
   if (a->dtype != SLM_F16 && a->dtype != SLM_BF16) return SLM_ERR_UNSUPPORTED;

@@ -1,5 +1,6 @@
-// fp8_cvt.h -- what the fp8 (e4m3fn) weight-only kernels share (dense_fp8.hip, moe_gemm_fp8.hip): the exact
-// e4m3 -> T conversion into MFMA weight fragments, and the fp32 channel-scale multiply.
+// fp8_cvt.h -- the fp8 (e4m3fn) weight side of the weight-stream kernels (dense.hip, moe_gemm.hip): the exact
+// e4m3 -> T conversion into MFMA weight fragments, the MFMA step's weight fragment of either weight side, and the fp32
+// channel-scale multiply.
 #pragma once
 #include "common.h"
 
@@ -31,6 +32,14 @@ __device__ __forceinline__ typename Mfma<T>::frag fp8x8_frag(uint32_t d0, uint32
   const u32x4 f = {fp8x2_to_t<T, false>(d0), fp8x2_to_t<T, true>(d0), fp8x2_to_t<T, false>(d1),
                    fp8x2_to_t<T, true>(d1)};
   return __builtin_bit_cast(typename Mfma<T>::frag, f);
+}
+
+// The weight fragment of one MFMA step out of a 16-B weight load.  T weights: the load is the fragment (8 k).  e4m3
+// weights: the load holds 16 k, the fragments of two steps; step h = 0 / 1 of the load takes dwords 0, 1 / 2, 3.
+template <typename T, bool FP8>
+__device__ __forceinline__ typename Mfma<T>::frag step_frag(const u32x4& w, int h) {
+  if constexpr (FP8) return h ? fp8x8_frag<T>(w.z, w.w) : fp8x8_frag<T>(w.x, w.y);
+  else return __builtin_bit_cast(typename Mfma<T>::frag, w);
 }
 
 // y = acc * s as an fp32 value in a register: the compiler may not contract it into the bias add that follows

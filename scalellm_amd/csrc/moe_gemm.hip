@@ -1,17 +1,21 @@
-// moe_gemm.hip -- grouped dense fp16 / bf16 GEMM over the experts of a mixture-of-experts layer
-// (include/slm_hip.h section 10, slm_moe_gemm; the reference's Sm80KernelGroupedGemm, src/kernels/gemm/,
-// in its own form: A[m, k], W[e, n, k], rows gathered through sorted_token_idxes / expert_ids).
+// moe_gemm.hip -- grouped GEMM over the experts of a mixture-of-experts layer, checkpoint-layout weights, one kernel
+// for both weight sides:
+//  * slm_moe_gemm (include/slm_hip.h section 10): dense fp16 / bf16 experts; the reference's
+//    Sm80KernelGroupedGemm, src/kernels/gemm/, in its own form: A[m, k], W[e, n, k], rows gathered through
+//    sorted_token_idxes / expert_ids
+//  * slm_moe_fp8_gemm (section 16): fp8 (e4m3fn) weight-only experts with fp32 channel scales.
 //
 // For every 32-row block b of the aligned token list (slm_moe_align_block with block_size 32):
 //     C[idx, :] = epilogue( A[idx / a_div, :] . W_e^T ),  e = expert_ids[b], idx = sorted[b * 32 + r]
+// (e4m3: epilogue( (A . e4m3(W_e)^T) * w_scale[e, :] )).
 // The aligned-list contract is w4_moe.hip's; what differs is the weight operand.  W_e is the checkpoint
 // tensor [N, K], k-contiguous, and that IS the B operand of the 32x32x16 MFMA: lane (n = lane & 31,
 // h = lane >> 5) holds 8 consecutive k of column n.  So the weights go from global memory to the MFMA
 // in 16-B loads: no LDS stage, no transpose, no prepack.
 //
 // k order.  An MFMA sums 16 products; which 16 k they are is free as long as both operands agree.  K is
-// streamed in 128-deep chunks and lane half h takes the k range [64 h, 64 h + 64) of the chunk: its eight
-// 16-B loads are 128 contiguous bytes of row n (a cache line when ldw allows it), and MFMA step q = 0..7
+// streamed in 128-deep chunks and lane half h takes the k range [64 h, 64 h + 64) of the chunk: its
+// 16-B loads are contiguous bytes of row n (a cache line when ldw allows it), and MFMA step q = 0..7
 // sums k = 64 h + 8 q + j over (h, j).  A's fragments come from a [32 rows][128 k] LDS image of the chunk
 // in natural k order: lane (r, h) reads slot 8 h + q of row r (w4_stream32.h's XOR swizzle: conflict-free
 // ds_read_b128).  A K that is no multiple of 128 ends in up to three 32-deep units in natural order
@@ -32,12 +36,30 @@
 // SLM_MOE_SILU_MUL: rows [0, N/2) of W_e are the gate, [N/2, N) the up projection; waves (0, 1) and
 // (2, 3) hold the (gate, up) tiles of one output tile, the up wave hands its T-rounded tile over through
 // LDS: the bits of the plain GEMM followed by slm_silu_mul.
+//
+// The weight side is the kernel parameter struct's compile-time choice (KP::FP8), as in dense.hip:
+//  * T weights: a lane's 64 k of a chunk are 128 bytes of row n, eight 16-B loads; load q IS the weight fragment
+//    of MFMA step q.  A tail unit is two loads per lane half.
+//  * e4m3 weights: the 64 k are 64 BYTES, four 16-B loads; load j holds the fragments of the two steps 2 j (dwords
+//    0, 1) and 2 j + 1 (dwords 2, 3).  e4m3 -> T is exact (fp8_cvt.h): step q sees exactly the k -- and the T
+//    values -- it sees on T(W), so the accumulators are the T side's bit for bit.  A tail unit is one load per lane
+//    half.
+//  * e4m3 only, the scale.  In the C layout of the 32x32 MFMA a lane holds ONE column (col = lane & 31): one scale
+//    load per lane, w_scale[e * scale_stride + n].  It multiplies the fp32 accumulator (never the converter's scale
+//    operand), then row_scale[idx] multiplies that product, then one rounding.  Under SiLU * mul the gate and the
+//    up wave each scale their tile by their own channels before the T rounding and the LDS hand-over.
+// Ring depth: MG_RING = 3 chunks for both weight sides, as dense.hip found (its header: a six-chunk ring measured
+// slower on e4m3).  No result bit depends on it.
+#include <type_traits>
+
 #include "common.h"
+#include "fp8_cvt.h"
 #include "moe_gemm_plan.h"
 
 namespace slm {
 
 struct MoeDenseKParams {
+  static constexpr bool FP8 = false;
   const void* a;
   const char* w;            // expert 0
   void* c;
@@ -57,9 +79,36 @@ struct MoeDenseKParams {
   int silu;
 };
 
-template <typename T, int NW>
-__global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseKParams p) {
+struct MoeFp8KParams {
+  static constexpr bool FP8 = true;
+  const void* a;
+  const char* w;            // expert 0
+  const float* w_scale;     // expert 0's [N], or NULL (1.0)
+  void* c;
+  const float* row_scale;   // [n_flat] or NULL
+  const int32_t* sorted;    // [>= n_padded]
+  const int32_t* expert_ids;
+  const int32_t* n_padded;  // [1]
+  int64_t w_stride;         // bytes per expert
+  int64_t scale_stride;     // floats per expert
+  int64_t lda, ldw, ldc;    // elements (ldw: bytes)
+  int n_flat;               // rows of c; indices >= n_flat are padding
+  int a_div;
+  int n_experts;
+  int n_tiles;              // N / 32
+  int n_chunks;             // K / 128
+  int tail_units;           // (K % 128) / 32
+  int n_nblocks;            // workgroups per row block
+  int silu;
+};
+
+template <typename T, int NW, typename KP>
+__global__ void __launch_bounds__(NW * 64) moe_gemm_kernel(const KP p) {
   typedef typename Mfma<T>::frag frag_t;
+  constexpr bool FP8 = KP::FP8;
+  constexpr int WB = FP8 ? 1 : 2;  // bytes per weight
+  constexpr int WL = 4 * WB;       // 16-B weight loads per lane and chunk
+  constexpr int SPL = 2 / WB;      // MFMA steps (8 k) a 16-B weight load holds
   constexpr int NT = NW * 64;
   constexpr int P = 512 / NT;  // 16-B pieces of a chunk of A per thread
   __shared__ __attribute__((aligned(16))) char smem[MG_LDS_BYTES];
@@ -107,7 +156,10 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
     a_dst[i] = stage_swz(row, slot);
   }
   // the expert base is a 64-bit pointer, offsets inside an expert 32-bit
-  const char* wlane = p.w + (int64_t)e * p.w_stride + 2 * (((int64_t)nt * 32 + mrow) * p.ldw);
+  const char* wexp = p.w + (int64_t)e * p.w_stride;
+  // the lane's row of W_e = its column of C (clamped tiles: a valid duplicate)
+  const int64_t ncol = (int64_t)nt * 32 + mrow;
+  const char* wlane = wexp + WB * (ncol * p.ldw);
   const int a_row = mrow * 256;
   const int a_swz = mrow & 15;
 
@@ -120,7 +172,7 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
     const int last = nC - 1;
     auto clampc = [&](int c) { return c < last ? c : last; };
     u32x4 areg[MG_RING][P];
-    u32x4 wreg[MG_RING][8];
+    u32x4 wreg[MG_RING][WL];
     auto a_load = [&](int c, u32x4 (&dst)[P]) {
       const uint32_t off = (uint32_t)clampc(c) * 256u;
 #pragma unroll
@@ -130,12 +182,12 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
 #pragma unroll
       for (int i = 0; i < P; ++i) *reinterpret_cast<u32x4*>(smem + stage * MG_STAGE_BYTES + a_dst[i]) = src[i];
     };
-    // lane half kh: the 128 contiguous bytes [kh * 128, kh * 128 + 128) of the chunk's 256 B of row n
-    const char* wl = wlane + kh * 128;
-    auto w_load = [&](int c, u32x4 (&w)[8]) {
-      const uint32_t off = (uint32_t)clampc(c) * 256u;
+    // lane half kh: the 64 WB contiguous bytes [kh * 64 WB, kh * 64 WB + 64 WB) of the chunk's 128 WB bytes of row n
+    const char* wl = wlane + kh * (64 * WB);
+    auto w_load = [&](int c, u32x4 (&w)[WL]) {
+      const uint32_t off = (uint32_t)clampc(c) * (128u * WB);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) w[q] = *reinterpret_cast<const u32x4*>(wl + off + q * 16);
+      for (int j = 0; j < WL; ++j) w[j] = *reinterpret_cast<const u32x4*>(wl + off + j * 16);
     };
 
     // prologue in the order the steady-state iterations issue (A, then the weights of the same chunk)
@@ -164,10 +216,15 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
         if (i < nC) {
           const char* sbase = smem + stage * MG_STAGE_BYTES + a_row;
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const frag_t af = __builtin_bit_cast(
-                frag_t, *reinterpret_cast<const u32x4*>(sbase + (((kh * 8 + q) ^ a_swz) << 4)));
-            acc = Mfma<T>::run(af, __builtin_bit_cast(frag_t, wreg[u][q]), acc);
+          for (int j = 0; j < WL; ++j) {
+#pragma unroll
+            for (int h = 0; h < SPL; ++h) {
+              const int q = j * SPL + h;  // MFMA step q: k = 64 kh + 8 q .. + 8 of the chunk
+              const frag_t wf = step_frag<T, FP8>(wreg[u][j], h);
+              const frag_t af = __builtin_bit_cast(
+                  frag_t, *reinterpret_cast<const u32x4*>(sbase + (((kh * 8 + q) ^ a_swz) << 4)));
+              acc = Mfma<T>::run(af, wf, acc);
+            }
           }
         }
         // the refill AFTER the old values are consumed (pinned): each ring slot keeps its registers
@@ -184,29 +241,43 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
 
   // ---- K % 128: up to three 32-deep units in natural k order, one at a time ----
   if (p.tail_units > 0) {
-    const uint32_t koff = (uint32_t)nC * 256u;  // bytes into a row
-    __syncthreads();                            // nC == 0: s_idx; otherwise nobody reads the stages any more
+    const uint32_t a_koff = (uint32_t)nC * 256u;  // bytes of a row of A behind the chunks
+    __syncthreads();                              // nC == 0: s_idx; otherwise nobody reads the stages any more
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       if (a_slot < p.tail_units * 4)
-        *reinterpret_cast<u32x4*>(smem + a_dst[i]) = *reinterpret_cast<const u32x4*>(a_src[i] + koff);
+        *reinterpret_cast<u32x4*>(smem + a_dst[i]) = *reinterpret_cast<const u32x4*>(a_src[i] + a_koff);
     }
     __syncthreads();
     const char* sbase = smem + a_row;
-    const char* wt = wlane + koff + kh * 32;
+    // lane half kh: k = 16 kh .. + 16 of a unit, WB 16-B loads
+    const char* wt = wlane + (uint32_t)nC * (128u * WB) + kh * (16 * WB);
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       if (t < p.tail_units) {
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const u32x4 wv = *reinterpret_cast<const u32x4*>(wt + t * 64 + s * 16);
-          const frag_t af = __builtin_bit_cast(
-              frag_t, *reinterpret_cast<const u32x4*>(sbase + (((t * 4 + kh * 2 + s) ^ a_swz) << 4)));
-          acc = Mfma<T>::run(af, __builtin_bit_cast(frag_t, wv), acc);
+        for (int j = 0; j < WB; ++j) {
+          const u32x4 wv = *reinterpret_cast<const u32x4*>(wt + t * (32 * WB) + j * 16);
+#pragma unroll
+          for (int h = 0; h < SPL; ++h) {
+            const int s = j * SPL + h;  // step s of the unit: k = 16 kh + 8 s .. + 8
+            const frag_t wf = step_frag<T, FP8>(wv, h);
+            const frag_t af = __builtin_bit_cast(
+                frag_t, *reinterpret_cast<const u32x4*>(sbase + (((t * 4 + kh * 2 + s) ^ a_swz) << 4)));
+            acc = Mfma<T>::run(af, wf, acc);
+          }
         }
       }
     }
     __syncthreads();  // the SiLU exchange below reuses the stage
+  }
+
+  if constexpr (FP8) {  // y = acc * w_scale[e, n]: the lane's one column, one fp32 multiply per element, in place
+    if (p.w_scale) {
+      const float s = p.w_scale[(int64_t)e * p.scale_stride + ncol];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = scaled(acc[r], s);
+    }
   }
 
   // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5); the row goes to C[idx];
@@ -224,19 +295,17 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
       }
       __syncthreads();
       if ((wave & 1) || !nvalid) return;
-      const int64_t ocol = (int64_t)nt * 32 + mrow;  // the gate wave: nt = the output tile
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
+      for (int r = 0; r < 16; ++r) {  // the gate wave: nt = the output tile, ncol the output column
         const int fi = s_idx[(r & 3) + 8 * (r >> 2) + 4 * kh];
         const float g = lo_f32<T>((uint32_t)pack1<T>(acc[r]));
         const float u = lo_f32<T>((uint32_t)ex[r * 64 + lane]);
-        if ((unsigned)fi < (unsigned)p.n_flat) cbase[(int64_t)fi * p.ldc + ocol] = pack1<T>(silu_mul1(g, u));
+        if ((unsigned)fi < (unsigned)p.n_flat) cbase[(int64_t)fi * p.ldc + ncol] = pack1<T>(silu_mul1(g, u));
       }
       return;
     }
   }
   if (!nvalid) return;
-  const int64_t ncol = (int64_t)nt * 32 + mrow;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int fi = s_idx[(r & 3) + 8 * (r >> 2) + 4 * kh];
@@ -248,25 +317,25 @@ __global__ void __launch_bounds__(NW * 64) moe_dense_gemm_kernel(const MoeDenseK
   }
 }
 
+// ---- host: one path for slm_moe_gemm_dense_args and slm_moe_fp8_gemm_args ----
 // (the launch shape, moe_gemm_waves, is moe_gemm_plan.h's)
-template <typename T, int NW>
-static void launch_moe_dense(const MoeDenseKParams& kp, unsigned grid, hipStream_t st) {
-  hipLaunchKernelGGL((moe_dense_gemm_kernel<T, NW>), dim3(grid), dim3(NW * 64), 0, st, kp);
+template <typename T, int NW, typename KP>
+static void launch_moe_gemm(const KP& kp, unsigned grid, hipStream_t st) {
+  hipLaunchKernelGGL((moe_gemm_kernel<T, NW, KP>), dim3(grid), dim3(NW * 64), 0, st, kp);
 }
 
-template <typename T>
-static void launch_moe_dense_nw(const MoeDenseKParams& kp, int nw, unsigned grid, hipStream_t st) {
-  if (nw == 4) launch_moe_dense<T, 4>(kp, grid, st);
-  else if (nw == 2) launch_moe_dense<T, 2>(kp, grid, st);
-  else launch_moe_dense<T, 1>(kp, grid, st);
+template <typename T, typename KP>
+static void launch_moe_gemm_nw(const KP& kp, int nw, unsigned grid, hipStream_t st) {
+  if (nw == 4) launch_moe_gemm<T, 4>(kp, grid, st);
+  else if (nw == 2) launch_moe_gemm<T, 2>(kp, grid, st);
+  else launch_moe_gemm<T, 1>(kp, grid, st);
 }
 
-}  // namespace slm
-
-extern "C" {
-
-SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) {
-  using namespace slm;
+template <typename Args>
+static int run_moe_gemm(const Args* a, void* stream) {
+  constexpr bool FP8 = std::is_same<Args, slm_moe_fp8_gemm_args>::value;
+  constexpr int WB = FP8 ? 1 : 2;   // bytes per weight; ldw and w_expert_stride count weights
+  constexpr int WA = 16 / WB;       // weights per 16-B load
   if (!a) return SLM_ERR_INVALID_ARG;
   if (a->n_flat < 0 || a->K <= 0 || a->N <= 0 || a->a_div < 1 || a->n_experts < 1 || a->max_blocks < 0)
     return SLM_ERR_INVALID_ARG;
@@ -275,25 +344,31 @@ SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) {
   const bool silu = (a->flags & SLM_MOE_SILU_MUL) != 0;
   if (silu && a->row_scale) return SLM_ERR_INVALID_ARG;
   if (a->K % 32 || a->N % 32 || (silu && (a->N / 2) % 32)) return SLM_ERR_UNSUPPORTED;
-  // 32-bit offsets inside one expert; flat indices are int32
-  if (a->K * a->N * 2 >= ((int64_t)1 << 32) || a->n_flat >= ((int64_t)1 << 31) - 256) return SLM_ERR_UNSUPPORTED;
+  // 32-bit byte offsets inside one expert; flat indices are int32
+  if (a->K * a->N * WB >= ((int64_t)1 << 32) || a->n_flat >= ((int64_t)1 << 31) - 256) return SLM_ERR_UNSUPPORTED;
   if (a->n_flat == 0 || a->max_blocks == 0) return SLM_OK;
   if (!a->a || !a->w || !a->c || !a->sorted_token_idxes || !a->expert_ids || !a->n_padded_tokens)
     return SLM_ERR_INVALID_ARG;
   const int64_t n_out = silu ? a->N / 2 : a->N;
   if (a->lda < a->K || a->ldw < a->K || a->ldc < n_out || a->w_expert_stride < (a->N - 1) * a->ldw + a->K)
     return SLM_ERR_INVALID_ARG;
-  if (!aligned16(a->a) || a->lda % 8 || !aligned16(a->w) || a->ldw % 8 || a->w_expert_stride % 8 ||
+  if constexpr (FP8) {
+    if (a->w_scale && a->w_scale_expert_stride < a->N) return SLM_ERR_INVALID_ARG;
+  }
+  if (!aligned16(a->a) || a->lda % 8 || !aligned16(a->w) || a->ldw % WA || a->w_expert_stride % WA ||
       (reinterpret_cast<uintptr_t>(a->c) & 1u) || (reinterpret_cast<uintptr_t>(a->row_scale) & 3u))
     return SLM_ERR_ALIGNMENT;
-  if (a->N * a->ldw * 2 >= ((int64_t)1 << 32)) return SLM_ERR_UNSUPPORTED;  // a strided expert: still < 4 GiB
+  if constexpr (FP8) {
+    if (reinterpret_cast<uintptr_t>(a->w_scale) & 3u) return SLM_ERR_ALIGNMENT;
+  }
+  if (a->N * a->ldw * WB >= ((int64_t)1 << 32)) return SLM_ERR_UNSUPPORTED;  // a strided expert: still < 4 GiB
   const int64_t n_tiles = a->N / 32;
   const int nw = moe_gemm_waves(a->max_blocks, n_tiles, silu);
   const int64_t n_nblocks = gemm_col_groups(n_tiles, nw, silu);
   const int64_t grid = (int64_t)a->max_blocks * n_nblocks;
   if (grid >= ((int64_t)1 << 31)) return SLM_ERR_UNSUPPORTED;
 
-  MoeDenseKParams kp;
+  typename std::conditional<FP8, MoeFp8KParams, MoeDenseKParams>::type kp;
   kp.a = a->a;
   kp.w = reinterpret_cast<const char*>(a->w);
   kp.c = a->c;
@@ -301,7 +376,11 @@ SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) {
   kp.sorted = a->sorted_token_idxes;
   kp.expert_ids = a->expert_ids;
   kp.n_padded = a->n_padded_tokens;
-  kp.w_stride = a->w_expert_stride * 2;
+  kp.w_stride = a->w_expert_stride * WB;
+  if constexpr (FP8) {
+    kp.w_scale = a->w_scale;
+    kp.scale_stride = a->w_scale ? a->w_scale_expert_stride : 0;
+  }
   kp.lda = a->lda; kp.ldw = a->ldw; kp.ldc = a->ldc;
   kp.n_flat = (int)a->n_flat;
   kp.a_div = a->a_div;
@@ -313,8 +392,15 @@ SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) {
   kp.silu = silu ? 1 : 0;
   hip_clear_error();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  dispatch_dtype(a->dtype, [&](auto t) { launch_moe_dense_nw<decltype(t)>(kp, nw, (unsigned)grid, st); });
+  dispatch_dtype(a->dtype, [&](auto t) { launch_moe_gemm_nw<decltype(t)>(kp, nw, (unsigned)grid, st); });
   return hip_check_launch();
 }
+
+}  // namespace slm
+
+extern "C" {
+
+SLM_API int slm_moe_gemm(const slm_moe_gemm_dense_args* a, void* stream) { return slm::run_moe_gemm(a, stream); }
+SLM_API int slm_moe_fp8_gemm(const slm_moe_fp8_gemm_args* a, void* stream) { return slm::run_moe_gemm(a, stream); }
 
 }  // extern "C"

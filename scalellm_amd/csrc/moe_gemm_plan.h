@@ -1,5 +1,5 @@
-// moe_gemm_plan.h -- what the grouped GEMMs over checkpoint-layout experts share (moe_gemm.hip, moe_gemm_fp8.hip):
-// the chunk / ring constants and the launch shape.
+// moe_gemm_plan.h -- the chunk / ring constants and the launch shape of moe_gemm.hip's grouped GEMMs over
+// checkpoint-layout experts.
 #pragma once
 #include "common.h"
 

@@ -8,7 +8,7 @@
 //   slm::moe_w4_grouped_gemm   the grouped int4 GEMM over stacked packed experts (the reference's grouped GEMM,
 //                              src/kernels/gemm/, is a dense fp16 / bf16 kernel; int4 experts have no counterpart).
 //   slm::moe_grouped_gemm      that dense fp16 / bf16 grouped GEMM over W[e, n, k].
-//   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm_fp8.hip).
+//   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm.hip).
 //   slm::moe_router            the fused router: gate GEMM + routing in one launch (section 17, csrc/moe_router.hip).
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).

@@ -778,23 +778,34 @@ def w4_dequant(packed: PackedW4) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------
 # dense (unquantised) linear: slm_hip.h section 13
 # ---------------------------------------------------------------------------------------
-def _linear_args(a, weight, c, bias, defer_reduce: bool, silu_mul: bool) -> "_lib.LinearArgs":
-    _require_gpu(a, weight, c, bias)
+def _linear_args(a, weight, w_scale, c, bias, defer_reduce: bool, silu_mul: bool, fp8: bool = False):
+    """Checks and argument block of linear() and its plan query, or with fp8 of fp8_linear(): the same block plus
+    w_scale, over e4m3 bytes (`weight`) that do not share the activations' dtype"""
+    name = "fp8_linear" if fp8 else "linear"
+    _require_gpu(a, weight, w_scale, c, bias)
     if silu_mul and defer_reduce:
         raise SlmError("silu_mul and defer_reduce cannot be combined")
+    if fp8 and weight.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise SlmError(f"fp8_linear takes float8_e4m3fn weights (or their bytes), not {weight.dtype}")
     if a.dim() != 2 or c.dim() != 2 or weight.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1 or \
             weight.stride(1) != 1:
         raise SlmError("A [M, K], W [N, K] and C [M, N] must be 2-D with contiguous rows")
     N, K = weight.shape
     if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a.size(0) != c.size(0):
-        raise SlmError("linear shape mismatch")
-    if a.dtype != weight.dtype or c.dtype != weight.dtype or (bias is not None and bias.dtype != weight.dtype):
-        raise SlmError("activation / weight / bias / output dtypes must match")
+        raise SlmError(f"{name} shape mismatch")
+    if (not fp8 and a.dtype != weight.dtype) or c.dtype != a.dtype or (bias is not None and bias.dtype != a.dtype):
+        raise SlmError("activation / bias / output dtypes must match" if fp8 else
+                       "activation / weight / bias / output dtypes must match")
     if bias is not None and (bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous()):
         raise SlmError("bias must be a contiguous [N] tensor")
-    g = _lib.LinearArgs()
+    if w_scale is not None and (w_scale.dtype != torch.float32 or w_scale.dim() != 1 or w_scale.numel() != N or
+                                not w_scale.is_contiguous()):
+        raise SlmError("w_scale must be a contiguous fp32 [N] tensor (expand a per-tensor scale on the host)")
+    g = _lib.Fp8LinearArgs() if fp8 else _lib.LinearArgs()
     g.a, g.w, g.c = a.data_ptr(), weight.data_ptr(), c.data_ptr()
     g.bias = bias.data_ptr() if bias is not None else None
+    if fp8:
+        g.w_scale = w_scale.data_ptr() if w_scale is not None else None
     g.M, g.K, g.N = a.size(0), K, N
     g.lda, g.ldw, g.ldc = a.stride(0), weight.stride(0), c.stride(0)
     g.dtype = _dtype_code(a)
@@ -807,14 +818,17 @@ def _linear_args(a, weight, c, bias, defer_reduce: bool, silu_mul: bool) -> "_li
     return g
 
 
+def _linear_plan(entry: str, g) -> "_lib.LinearPlanInfo":
+    info = _lib.LinearPlanInfo()
+    check(getattr(_lib.lib(), entry + "_plan")(C.byref(g), C.byref(info)), entry + "_plan")
+    return info
+
+
 def linear_plan(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Optional[torch.Tensor] = None,
                 defer_reduce: bool = False, silu_mul: bool = False) -> "_lib.LinearPlanInfo":
     """The launch linear() would give these very arguments now, under the tuning knobs in force
     (slm_linear_plan): row tiles, waves, grid, K slices.  A host-side query: nothing runs on the GPU."""
-    g = _linear_args(a, weight, c, bias, defer_reduce, silu_mul)
-    info = _lib.LinearPlanInfo()
-    check(_lib.lib().slm_linear_plan(C.byref(g), C.byref(info)), "slm_linear_plan")
-    return info
+    return _linear_plan("slm_linear", _linear_args(a, weight, None, c, bias, defer_reduce, silu_mul))
 
 
 def _run_linear(entry: str, g, dev: torch.device, defer_reduce: bool) -> DeferredPartials:
@@ -851,7 +865,8 @@ def linear(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Optiona
 
     silu_mul: rows [0, N/2) of `weight` are the gate, [N/2, N) the up projection and `c` is [M, N/2] =
     silu(gate) * up -- the bits of linear() followed by silu_and_mul()."""
-    return _run_linear("slm_linear", _linear_args(a, weight, c, bias, defer_reduce, silu_mul), a.device, defer_reduce)
+    return _run_linear("slm_linear", _linear_args(a, weight, None, c, bias, defer_reduce, silu_mul), a.device,
+                       defer_reduce)
 
 
 # ---------------------------------------------------------------------------------------
@@ -875,48 +890,11 @@ def quantize_fp8_weight(w: torch.Tensor, per: str = "channel"):
     return w8, scale
 
 
-def _fp8_linear_args(a, w8, w_scale, c, bias, defer_reduce: bool, silu_mul: bool) -> "_lib.Fp8LinearArgs":
-    _require_gpu(a, w8, w_scale, c, bias)
-    if silu_mul and defer_reduce:
-        raise SlmError("silu_mul and defer_reduce cannot be combined")
-    if w8.dtype not in (torch.float8_e4m3fn, torch.uint8):
-        raise SlmError(f"fp8_linear takes float8_e4m3fn weights (or their bytes), not {w8.dtype}")
-    if a.dim() != 2 or c.dim() != 2 or w8.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1 or w8.stride(1) != 1:
-        raise SlmError("A [M, K], W [N, K] and C [M, N] must be 2-D with contiguous rows")
-    N, K = w8.shape
-    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a.size(0) != c.size(0):
-        raise SlmError("fp8_linear shape mismatch")
-    if c.dtype != a.dtype or (bias is not None and bias.dtype != a.dtype):
-        raise SlmError("activation / bias / output dtypes must match")
-    if bias is not None and (bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous()):
-        raise SlmError("bias must be a contiguous [N] tensor")
-    if w_scale is not None and (w_scale.dtype != torch.float32 or w_scale.dim() != 1 or w_scale.numel() != N or
-                                not w_scale.is_contiguous()):
-        raise SlmError("w_scale must be a contiguous fp32 [N] tensor (expand a per-tensor scale on the host)")
-    g = _lib.Fp8LinearArgs()
-    g.a, g.w, g.c = a.data_ptr(), w8.data_ptr(), c.data_ptr()
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.w_scale = w_scale.data_ptr() if w_scale is not None else None
-    g.M, g.K, g.N = a.size(0), K, N
-    g.lda, g.ldw, g.ldc = a.stride(0), w8.stride(0), c.stride(0)
-    g.dtype = _dtype_code(a)
-    g.flags = _lib.SLM_LINEAR_SHARES_CHIP if _chip_flag() else 0
-    if silu_mul:
-        g.flags |= _lib.SLM_LINEAR_SILU_MUL
-    if defer_reduce:
-        g.flags |= _lib.SLM_LINEAR_DEFER_REDUCE
-    g.workspace, g.workspace_bytes = None, 0
-    return g
-
-
 def fp8_linear_plan(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
                     bias: Optional[torch.Tensor] = None, defer_reduce: bool = False,
                     silu_mul: bool = False) -> "_lib.LinearPlanInfo":
     """The launch fp8_linear() would give these very arguments now (slm_fp8_linear_plan); a host-side query."""
-    g = _fp8_linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul)
-    info = _lib.LinearPlanInfo()
-    check(_lib.lib().slm_fp8_linear_plan(C.byref(g), C.byref(info)), "slm_fp8_linear_plan")
-    return info
+    return _linear_plan("slm_fp8_linear", _linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul, fp8=True))
 
 
 def fp8_linear(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
@@ -926,8 +904,8 @@ def fp8_linear(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor
     w_scale[N] + bias), fp32 accumulate, the scale applied to the fp32 sum, one rounding.  `w8` is the checkpoint's
     float8_e4m3fn weight [N, K] (rows contiguous, row stride a multiple of 16), streamed as bytes and converted in
     registers; `w_scale` fp32 [N] or None (1.0).  defer_reduce, silu_mul and the returned handle: as linear()."""
-    return _run_linear("slm_fp8_linear", _fp8_linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul), a.device,
-                       defer_reduce)
+    return _run_linear("slm_fp8_linear", _linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul, fp8=True),
+                       a.device, defer_reduce)
 
 
 # ---------------------------------------------------------------------------------------
@@ -1663,15 +1641,13 @@ def moe_w4_grouped_gemm(a: torch.Tensor, experts: PackedMoeW4, c: torch.Tensor, 
     check(_lib.lib().slm_moe_w4a16_gemm(C.byref(g), _stream()), "slm_moe_w4a16_gemm")
 
 
-def moe_grouped_gemm(a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, sorted_token_idxes: torch.Tensor,
-                     expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor, a_div: int,
-                     row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
-    """C[idx] = epilogue(A[idx // a_div] . W[e]^T) over unquantised experts w [E, N, K] (the checkpoint layout,
-    k contiguous; expert and row strides may be larger than dense), for the 32-row blocks
-    moe_align_block(block_size = 32) produced.  silu_mul: rows [0, N/2) of an expert are the gate, [N/2, N) the up
-    projection, c is [n_flat, N / 2]; row_scale: fp32 [n_flat] routing weights applied to the fp32 accumulator.
-    The grid covers expert_ids.numel() blocks; the count in use is read on the device."""
-    _require_gpu(a, w, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+def _moe_grouped_gemm(a, w, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, a_div, row_scale, silu_mul,
+                      fp8: bool) -> None:
+    """Checks, argument block and launch of moe_grouped_gemm(), or with fp8 of moe_fp8_grouped_gemm(): the same
+    block plus w_scale, over e4m3 bytes (`w`) that do not share the activations' dtype"""
+    _require_gpu(a, w, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    if fp8 and w.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise SlmError(f"moe_fp8_grouped_gemm takes float8_e4m3fn weights (or their bytes), not {w.dtype}")
     if a.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1:
         raise SlmError("A and C must be 2-D with contiguous rows")
     if w.dim() != 3 or w.stride(2) != 1:
@@ -1680,51 +1656,11 @@ def moe_grouped_gemm(a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, sorted_t
     n_flat = c.size(0)
     if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a_div < 1 or a.size(0) * a_div < n_flat:
         raise SlmError("grouped GEMM shape mismatch")
-    if a.dtype != w.dtype or c.dtype != w.dtype:
+    if fp8:
+        if a.dtype not in (torch.float16, torch.bfloat16) or c.dtype != a.dtype:
+            raise SlmError("activation and output must share one dtype, fp16 or bf16")
+    elif a.dtype != w.dtype or c.dtype != w.dtype:
         raise SlmError("activation / output dtype must match the experts' dtype")
-    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
-    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
-        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
-    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
-                                  row_scale.numel() != n_flat):
-        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
-    g = _lib.MoeDenseGemmArgs()
-    g.a, g.w, g.c = a.data_ptr(), w.data_ptr(), c.data_ptr()
-    g.row_scale = row_scale.data_ptr() if row_scale is not None else None
-    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
-    g.n_padded_tokens = n_padded_tokens.data_ptr()
-    g.w_expert_stride = w.stride(0) if E > 1 else max(w.stride(0), (N - 1) * w.stride(1) + K)
-    g.n_flat, g.K, g.N = n_flat, K, N
-    g.lda, g.ldw, g.ldc = a.stride(0), w.stride(1), c.stride(0)
-    g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
-    g.dtype = _dtype_code(a)
-    g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
-    check(_lib.lib().slm_moe_gemm(C.byref(g), _stream()), "slm_moe_gemm")
-
-
-def moe_fp8_grouped_gemm(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
-                         sorted_token_idxes: torch.Tensor, expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor,
-                         a_div: int, row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
-    """moe_grouped_gemm over fp8 experts (slm_hip.h section 16): C[idx] = epilogue((A[idx // a_div] . e4m3(W8[e])^T)
-    * w_scale[e]).  `w8` is [E, N, K] float8_e4m3fn (or its bytes as uint8), the checkpoint layout, k contiguous,
-    expert and row strides may be padded (multiples of 16); `w_scale` fp32 [E, N] (rows contiguous, the expert
-    stride may be padded) or None (1.0), applied to the fp32 accumulator before row_scale and the one rounding.
-    silu_mul, row_scale, the aligned list and the grid: as moe_grouped_gemm."""
-    _require_gpu(a, w8, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
-    if w8.dtype not in (torch.float8_e4m3fn, torch.uint8):
-        raise SlmError(f"moe_fp8_grouped_gemm takes float8_e4m3fn weights (or their bytes), not {w8.dtype}")
-    if a.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1:
-        raise SlmError("A and C must be 2-D with contiguous rows")
-    if w8.dim() != 3 or w8.stride(2) != 1:
-        raise SlmError("expert weights must be [n_experts, N, K] with k contiguous")
-    E, N, K = w8.shape
-    n_flat = c.size(0)
-    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a_div < 1 or a.size(0) * a_div < n_flat:
-        raise SlmError("grouped GEMM shape mismatch")
-    if a.dtype not in (torch.float16, torch.bfloat16) or c.dtype != a.dtype:
-        raise SlmError("activation and output must share one dtype, fp16 or bf16")
     if w_scale is not None and (w_scale.dtype != torch.float32 or tuple(w_scale.shape) != (E, N) or
                                 w_scale.stride(1) != 1):
         raise SlmError("w_scale must be fp32 [n_experts, N] with contiguous rows (expand a per-tensor scale)")
@@ -1736,21 +1672,49 @@ def moe_fp8_grouped_gemm(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[to
     if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
                                   row_scale.numel() != n_flat):
         raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
-    g = _lib.MoeFp8GemmArgs()
-    g.a, g.w, g.c = a.data_ptr(), w8.data_ptr(), c.data_ptr()
-    g.w_scale = w_scale.data_ptr() if w_scale is not None else None
+    g = _lib.MoeFp8GemmArgs() if fp8 else _lib.MoeDenseGemmArgs()
+    g.a, g.w, g.c = a.data_ptr(), w.data_ptr(), c.data_ptr()
     g.row_scale = row_scale.data_ptr() if row_scale is not None else None
     g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
     g.n_padded_tokens = n_padded_tokens.data_ptr()
-    # a single expert's stride(0) is not meaningful: any multiple of 16 covering the expert will do
-    g.w_expert_stride = w8.stride(0) if E > 1 else max(w8.stride(0), N * w8.stride(1))
-    g.w_scale_expert_stride = 0 if w_scale is None else (w_scale.stride(0) if E > 1 else max(w_scale.stride(0), N))
+    # a single expert's stride(0) is not meaningful: what covers the expert will do (fp8: a multiple of 16)
+    g.w_expert_stride = w.stride(0) if E > 1 else \
+        max(w.stride(0), N * w.stride(1) if fp8 else (N - 1) * w.stride(1) + K)
+    if fp8:
+        g.w_scale = w_scale.data_ptr() if w_scale is not None else None
+        g.w_scale_expert_stride = 0 if w_scale is None else \
+            (w_scale.stride(0) if E > 1 else max(w_scale.stride(0), N))
     g.n_flat, g.K, g.N = n_flat, K, N
-    g.lda, g.ldw, g.ldc = a.stride(0), w8.stride(1), c.stride(0)
+    g.lda, g.ldw, g.ldc = a.stride(0), w.stride(1), c.stride(0)
     g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
     g.dtype = _dtype_code(a)
     g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
-    check(_lib.lib().slm_moe_fp8_gemm(C.byref(g), _stream()), "slm_moe_fp8_gemm")
+    entry = "slm_moe_fp8_gemm" if fp8 else "slm_moe_gemm"
+    check(getattr(_lib.lib(), entry)(C.byref(g), _stream()), entry)
+
+
+def moe_grouped_gemm(a: torch.Tensor, w: torch.Tensor, c: torch.Tensor, sorted_token_idxes: torch.Tensor,
+                     expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor, a_div: int,
+                     row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """C[idx] = epilogue(A[idx // a_div] . W[e]^T) over unquantised experts w [E, N, K] (the checkpoint layout,
+    k contiguous; expert and row strides may be larger than dense), for the 32-row blocks
+    moe_align_block(block_size = 32) produced.  silu_mul: rows [0, N/2) of an expert are the gate, [N/2, N) the up
+    projection, c is [n_flat, N / 2]; row_scale: fp32 [n_flat] routing weights applied to the fp32 accumulator.
+    The grid covers expert_ids.numel() blocks; the count in use is read on the device."""
+    _moe_grouped_gemm(a, w, None, c, sorted_token_idxes, expert_ids, n_padded_tokens, a_div, row_scale, silu_mul,
+                      fp8=False)
+
+
+def moe_fp8_grouped_gemm(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor], c: torch.Tensor,
+                         sorted_token_idxes: torch.Tensor, expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor,
+                         a_div: int, row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """moe_grouped_gemm over fp8 experts (slm_hip.h section 16): C[idx] = epilogue((A[idx // a_div] . e4m3(W8[e])^T)
+    * w_scale[e]).  `w8` is [E, N, K] float8_e4m3fn (or its bytes as uint8), the checkpoint layout, k contiguous,
+    expert and row strides may be padded (multiples of 16); `w_scale` fp32 [E, N] (rows contiguous, the expert
+    stride may be padded) or None (1.0), applied to the fp32 accumulator before row_scale and the one rounding.
+    silu_mul, row_scale, the aligned list and the grid: as moe_grouped_gemm."""
+    _moe_grouped_gemm(a, w8, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, a_div, row_scale, silu_mul,
+                      fp8=True)
 
 
 # ---------------------------------------------------------------------------------------
