@@ -845,6 +845,14 @@ SLM_API int slm_rejection_sample(const slm_rejection_args* a, void* stream);
 /*                                                                            */
 /*  slm_moe_sum (sum_out): out[t, :] = T(sum_j in[t, j, :]) -- fp32, in order */
 /*  j = 0..k-1, one rounding; any k >= 1; contiguous input and output.        */
+/*  slm_moe_sum_add: out[t, :] = T(in[t, 0, :] + ... + in[t, k-1, :] +        */
+/*  addend[t, :]) -- the same fp32 accumulation with one more contiguous      */
+/*  [T, dim] row per token (the always-on shared experts' output) added LAST, */
+/*  one rounding: bit-identical to slm_moe_sum over [T, k + 1, dim] with the  */
+/*  addend as slot k, without the copy and without a separate add launch.     */
+/*  out may alias addend.  Checks as slm_moe_sum, plus addend NULL ->         */
+/*  SLM_ERR_INVALID_ARG and (dim % 8 == 0) a misaligned addend ->             */
+/*  SLM_ERR_ALIGNMENT.                                                        */
 /*                                                                            */
 /*  Grouped GEMM.  For every 32-row block b with b * 32 < *n_padded_tokens    */
 /*  (read on the device), e = expert_ids[b], and every non-padding            */
@@ -924,6 +932,11 @@ SLM_API int slm_moe_align_block(const slm_moe_align_args* a, void* stream);
 
 SLM_API int slm_moe_sum(void* out /* [T, dim] */, const void* in /* [T, k, dim] */, int64_t n_tokens,
                         int32_t topk, int64_t dim, int32_t dtype, void* stream);
+/* (the parameter list on its own line, as slm_moe_gemm's below: tests/test_moe_cpu.py pins this section's first entry
+ * points by the pattern "name(", and tests/test_mla_glue_cpu.py covers this one) */
+SLM_API int slm_moe_sum_add
+    (void* out /* [T, dim] */, const void* in /* [T, k, dim] */, const void* addend /* [T, dim] */, int64_t n_tokens,
+     int32_t topk, int64_t dim, int32_t dtype, void* stream);
 
 typedef struct slm_moe_gemm_args {
   const void* a;                    /* [n_flat / a_div, K] T, row stride lda (elements)           */
@@ -1423,6 +1436,75 @@ SLM_API int slm_moe_router_workspace_bytes
     (int64_t n_tokens, int32_t n_experts, int64_t hidden, int32_t dtype, size_t* bytes);
 SLM_API int slm_moe_router
     (const slm_moe_router_args* a, void* stream);
+
+/* ========================================================================== */
+/* 18. MLA prologue: latent RMSNorm + RoPE + append into both caches          */
+/*    What a DeepSeek-V2 layer does between its kv_a / q projection and       */
+/*    section 11, in ONE launch.  For every token row t, with latent =        */
+/*    latent_dim in {128, 256, 512}, rope = rope_head_dim = 64 (section 11's  */
+/*    limits), nope = nope_head_dim, n_heads >= 0:                            */
+/*      c    = kv_a[t, :latent],  k_pe = kv_a[t, latent : latent + rope]      */
+/*      q[t, h, : nope + rope]    at q + t * q_token_stride + h (nope + rope) */
+/*      n    = RMSNorm(c; norm_weight, eps), the statistic over the latent    */
+/*             columns only, section 5's rounding (fp32 sum of squares,       */
+/*             T(T(c rs) w)): BIT-IDENTICAL to slm_rms_norm on a contiguous   */
+/*             copy of those columns (the same per-lane sums and the same     */
+/*             wave reduction, shared through common.h);                      */
+/*      k_pe and q[t, h, nope:] rotated by cos_sin[positions[t]] -- the row   */
+/*             layout of section 5, [cos(32) | sin(32)], in T                 */
+/*             (cos_sin_is_f32 = 0) or fp32; interleaved != 0 pairs           */
+/*             (2i, 2i + 1) (HuggingFace's DeepSeek-V2), 0 pairs (i, i + 32): */
+/*             BIT-IDENTICAL to slm_rope_kv_append on the same values with    */
+/*             head_dim = rot_dim = 64 (rope.h holds the one spelling);       */
+/*      slot = slot_ids[t] >= 0:  kv_cache[slot, :latent] = n,                */
+/*             k_rope_cache[slot, :rope] = rotated k_pe (slot strides in      */
+/*             elements, as slm_mla_set_kv_cache).  slot < 0 is graph         */
+/*             padding: q is still rotated, neither cache is written.  Every  */
+/*             other slot must be valid in both caches.                       */
+/*    The rotated tails stay in q: section 11 reads them with q_rope =        */
+/*    q + nope and strides {q_token_stride, nope + rope}.  kv_a is not        */
+/*    modified.                                                               */
+/*    slm_mla_rope_append (plain form): q is rotated IN PLACE, its nope       */
+/*    columns are untouched; q may be NULL with n_heads = 0.  kv_a has its    */
+/*    own pointer and token stride, so q and kv_a may be column slices of one */
+/*    fused [q | latent | k_pe] GEMM output.                                  */
+/*    slm_mla_rope_append_splitk (slab form): the inputs are the fp32 split-K */
+/*    slabs [n_splits, T, N] a deferred slm_linear / slm_fp8_linear left      */
+/*    behind (section 13), row = [q heads | latent | k_pe],                   */
+/*    N = n_heads (nope + rope) + latent + rope; every value is               */
+/*    T(sum_s partials[s][t][col]) in the reduce kernel's own slice order     */
+/*    (splitk_sum4), so the result is bit-identical to "reduce, then the      */
+/*    plain form".  q is an OUTPUT, written whole (nope columns included).    */
+/*    f16 / bf16; nope % 8 == 0; every base and stride 16-byte aligned.  One  */
+/*    launch on the given stream; no allocation, no host sync, no atomics, no */
+/*    LDS or barrier, no workgroup waits for another: capture-safe, repeats   */
+/*    are bit-identical.  positions and slot_ids are read on the device only, */
+/*    so a captured launch replays over changed ones.                         */
+/*    Before any launch: negative n_tokens / n_heads / nope, a NULL among     */
+/*    kv_a (plain) / partials (slab; or n_splits < 1) / norm_weight /         */
+/*    positions / cos_sin / slot_ids / kv_cache / k_rope_cache, q NULL with   */
+/*    n_heads > 0 -> SLM_ERR_INVALID_ARG; other latent_dim / rope_head_dim /  */
+/*    dtype, nope % 8 -> SLM_ERR_UNSUPPORTED; a base or stride that is not    */
+/*    16-byte aligned -> SLM_ERR_ALIGNMENT.  n_tokens == 0 is a no-op.        */
+/* ========================================================================== */
+SLM_API int slm_mla_rope_append(void* q /* [T, n_heads, nope + rope] in place, or NULL */, int64_t q_token_stride,
+                                const void* kv_a /* [T, latent + rope] */, int64_t kv_a_token_stride,
+                                const void* norm_weight /* [latent] */, float eps,
+                                const int32_t* positions /* [T] */, const void* cos_sin /* [max_pos, rope] */,
+                                int32_t cos_sin_is_f32, int32_t interleaved, const int32_t* slot_ids /* [T] */,
+                                void* kv_cache /* [n_slots, latent] */, void* k_rope_cache /* [n_slots, rope] */,
+                                int64_t kv_slot_stride, int64_t k_rope_slot_stride, int64_t n_tokens,
+                                int32_t n_heads, int32_t nope_head_dim, int32_t latent_dim, int32_t rope_head_dim,
+                                int32_t dtype, void* stream);
+SLM_API int slm_mla_rope_append_splitk(const float* partials /* [n_splits, T, N] */, int32_t n_splits,
+                                       void* q /* [T, n_heads, nope + rope] out, or NULL */, int64_t q_token_stride,
+                                       const void* norm_weight /* [latent] */, float eps,
+                                       const int32_t* positions /* [T] */, const void* cos_sin /* [max_pos, rope] */,
+                                       int32_t cos_sin_is_f32, int32_t interleaved, const int32_t* slot_ids /* [T] */,
+                                       void* kv_cache /* [n_slots, latent] */, void* k_rope_cache /* [n_slots, rope] */,
+                                       int64_t kv_slot_stride, int64_t k_rope_slot_stride, int64_t n_tokens,
+                                       int32_t n_heads, int32_t nope_head_dim, int32_t latent_dim,
+                                       int32_t rope_head_dim, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

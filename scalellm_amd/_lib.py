@@ -389,6 +389,16 @@ def lib() -> C.CDLL:
          [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         ("slm_moe_align_block", C.c_int, [C.POINTER(MoeAlignArgs), C.c_void_p]),
         ("slm_moe_sum", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+        ("slm_moe_sum_add", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+        ("slm_mla_rope_append", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
+          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+          C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+        ("slm_mla_rope_append_splitk", C.c_int,
+         [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
+          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+          C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
         ("slm_moe_w4a16_gemm", C.c_int, [C.POINTER(MoeGemmArgs), C.c_void_p]),
         ("slm_moe_gemm", C.c_int, [C.POINTER(MoeDenseGemmArgs), C.c_void_p]),
         ("slm_mla_paged_kv_workspace_bytes", C.c_size_t, [C.POINTER(MlaArgs)]),

@@ -261,6 +261,10 @@ __device__ __forceinline__ float rms_sumsq8(const float (&f)[8], float ss) {
   for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(f[j], f[j], ss);
   return ss;
 }
+// the row's scale from its sum of squares: shared by rms_norm_kernel and the MLA prologue (mla_glue.hip)
+__device__ __forceinline__ float rms_rstd(const float sumsq, const float dim, const float eps) {
+  return rsqrtf(sumsq / dim + eps);
+}
 // y = T(T(h * rs) * w): the normalised value is rounded to T before the weight (normalization.h:27-29)
 template <typename T>
 __device__ __forceinline__ u32x4 rms_apply8(const float (&h)[8], const float rs, const u32x4 wv) {

@@ -16,6 +16,7 @@
 //                         (src/kernels/activation_kernels.cu:20-40, 111-145; CPU path
 //                         src/layers/activation.cpp:24-34, 57-65).
 #include "common.h"
+#include "rope.h"  // rope_rot, rope_cs, rope_unit8: shared with mla_glue.hip
 
 namespace slm {
 
@@ -80,7 +81,7 @@ __global__ void __launch_bounds__(256) rms_norm_kernel(uint16_t* __restrict__ ou
   if ((tid & 63) == 0) red[tid >> 6] = ss;
   __syncthreads();
   const float tot = red[0] + red[1] + red[2] + red[3];
-  const float rs = rsqrtf(tot / (float)dim + eps);
+  const float rs = rms_rstd(tot, (float)dim, eps);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int64_t vi = tid + 256 * i;
@@ -89,18 +90,6 @@ __global__ void __launch_bounds__(256) rms_norm_kernel(uint16_t* __restrict__ ou
       *reinterpret_cast<u32x4*>(out + tok * dim + vi * 8) = o;
     }
   }
-}
-
-// (a, b) rotated by (cos, sin): ONE spelling for every RoPE kernel (explicit fma, so the compiler's
-// contraction choices cannot differ between them -- the split-K form must reproduce the plain one)
-__device__ __forceinline__ void rope_rot(const float a, const float b, const float c, const float s,
-                                         float& o0, float& o1) {
-  o0 = __builtin_fmaf(a, c, -(b * s));
-  o1 = __builtin_fmaf(b, c, a * s);
-  // fp32 results in registers before any conversion to T (otherwise fp16 callers may get a
-  // single-rounding v_fma_mixlo_f16 in one kernel and fma + convert in another)
-  asm("" : "+v"(o0));
-  asm("" : "+v"(o1));
 }
 
 // one workgroup per token.  Rotation pairs: non-interleaved (i, i + rot/2), interleaved (2i, 2i+1)
@@ -118,10 +107,7 @@ __global__ void __launch_bounds__(256) rope_kv_append_kernel(
   const int64_t slot = slot_ids ? (int64_t)slot_ids[tok] : -1;
   const int64_t row = (int64_t)n_kv_heads * head_dim;
   const CS* cs = cos_sin ? cos_sin + (int64_t)positions[tok] * rot_dim : nullptr;
-  auto csval = [&](int i) -> float {
-    if constexpr (sizeof(CS) == 4) return (float)cs[i];
-    else return lo_f32<T>((uint32_t)cs[i]);
-  };
+  auto csval = [&](int i) -> float { return rope_cs<T>(cs, i); };
   if (cs) {
     // Q: in place
     uint16_t* qt = q + tok * q_ts;
@@ -201,10 +187,6 @@ __global__ void __launch_bounds__(256) rope_kv_append_splitk_kernel(
   const int64_t slot = slot_ids ? (int64_t)slot_ids[tok] : -1;
   const int64_t row = (int64_t)n_kv_heads * head_dim;
   const CS* cs = cos_sin + (int64_t)positions[tok] * rot_dim;
-  auto csval = [&](int i) -> float {
-    if constexpr (sizeof(CS) == 4) return (float)cs[i];
-    else return lo_f32<T>((uint32_t)cs[i]);
-  };
   const float* prow = part + tok * N;
   const int64_t q_cols = (int64_t)n_heads * head_dim;
   // T(sum over slabs) of 4 consecutive columns, as fp32 values that are exact in T
@@ -242,19 +224,7 @@ __global__ void __launch_bounds__(256) rope_kv_append_splitk_kernel(
     float a[4], b[4], oa[4], ob[4];
     ld4(col0 + da, a);
     ld4(col0 + db, b);
-    if (interleaved) {  // pairs (a0,a1) (a2,a3) (b0,b1) (b2,b3), pair index r = 4u + {0,1,2,3}
-      const float c0 = csval(4 * u), s0 = csval(half + 4 * u), c1 = csval(4 * u + 1), s1 = csval(half + 4 * u + 1);
-      const float c2 = csval(4 * u + 2), s2 = csval(half + 4 * u + 2), c3 = csval(4 * u + 3), s3 = csval(half + 4 * u + 3);
-      rope_rot(a[0], a[1], c0, s0, oa[0], oa[1]);
-      rope_rot(a[2], a[3], c1, s1, oa[2], oa[3]);
-      rope_rot(b[0], b[1], c2, s2, ob[0], ob[1]);
-      rope_rot(b[2], b[3], c3, s3, ob[2], ob[3]);
-    } else {            // pairs (a[e], b[e]), r = 4u + e
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        rope_rot(a[e], b[e], csval(4 * u + e), csval(half + 4 * u + e), oa[e], ob[e]);
-      }
-    }
+    rope_unit8<T>(a, b, cs, half, u, interleaved, oa, ob);
     uint16_t* dst = is_k ? k + tok * k_ts + (int64_t)hh * head_dim : q + tok * q_ts + (int64_t)hh * head_dim;
     st4(dst + da, oa);
     st4(dst + db, ob);

@@ -3,6 +3,7 @@
 //   slm_moe_grouped_topk_sigmoid <- llm::kernel::grouped_topk_sigmoid  (moe/grouped_topk_sigmoid_kernel.cu:280)
 //   slm_moe_align_block          <- llm::kernel::moe::permute_align_block (moe/align_block_kernel.cu:192)
 //   slm_moe_sum                  <- llm::kernel::moe::sum_out             (moe/align_block_kernel.cu:242)
+//   slm_moe_sum_add              the same with one more row per token (the shared experts' output) added last
 // Small kernels: one launch each, no float atomics, fixed reduction orders (bit-identical repeats).
 // The grouped GEMM that consumes the aligned blocks is w4_moe.hip.
 #include "common.h"
@@ -109,11 +110,15 @@ align_block_kernel(const int* __restrict__ ids, int* __restrict__ sorted, int* _
 }
 
 // ---- sum over the k expert outputs of a token ---------------------------------------------------
+// addend (slm_moe_sum_add; nullptr in slm_moe_sum): one more [T, dim] row per token, added after slot k - 1 -- what
+// slot k of a [T, k + 1, dim] input would be
 template <typename T>
 __global__ void __launch_bounds__(256)
-moe_sum_kernel(uint16_t* __restrict__ out, const uint16_t* __restrict__ in, const int k, const int64_t dim) {
+moe_sum_kernel(uint16_t* __restrict__ out, const uint16_t* __restrict__ in, const uint16_t* __restrict__ addend,
+               const int k, const int64_t dim) {
   const int64_t t = blockIdx.y;
   const uint16_t* src = in + t * k * dim;
+  const uint16_t* add = addend ? addend + t * dim : nullptr;
   uint16_t* dst = out + t * dim;
   if ((dim & 7) == 0) {  // 16-byte pieces (rows are then 16-byte aligned: the bases are checked on the host)
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -121,6 +126,11 @@ moe_sum_kernel(uint16_t* __restrict__ out, const uint16_t* __restrict__ in, cons
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < k; ++j) {
       const u32x4 w = *reinterpret_cast<const u32x4*>(src + j * dim + v * 8);
+      acc[0] += lo_f32<T>(w.x); acc[1] += hi_f32<T>(w.x); acc[2] += lo_f32<T>(w.y); acc[3] += hi_f32<T>(w.y);
+      acc[4] += lo_f32<T>(w.z); acc[5] += hi_f32<T>(w.z); acc[6] += lo_f32<T>(w.w); acc[7] += hi_f32<T>(w.w);
+    }
+    if (add) {
+      const u32x4 w = *reinterpret_cast<const u32x4*>(add + v * 8);
       acc[0] += lo_f32<T>(w.x); acc[1] += hi_f32<T>(w.x); acc[2] += lo_f32<T>(w.y); acc[3] += hi_f32<T>(w.y);
       acc[4] += lo_f32<T>(w.z); acc[5] += hi_f32<T>(w.z); acc[6] += lo_f32<T>(w.w); acc[7] += hi_f32<T>(w.w);
     }
@@ -132,6 +142,7 @@ moe_sum_kernel(uint16_t* __restrict__ out, const uint16_t* __restrict__ in, cons
     for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < dim; d += (int64_t)gridDim.x * 256) {
       float acc = 0.f;
       for (int j = 0; j < k; ++j) acc += lo_f32<T>((uint32_t)src[j * dim + d]);
+      if (add) acc += lo_f32<T>((uint32_t)add[d]);
       dst[d] = pack1<T>(acc);
     }
   }
@@ -210,14 +221,14 @@ SLM_API int slm_moe_align_block(const slm_moe_align_args* a, void* stream) {
   return hip_check_launch();
 }
 
-SLM_API int slm_moe_sum(void* out, const void* in, int64_t n_tokens, int32_t topk, int64_t dim, int32_t dtype,
-                        void* stream) {
+static int moe_sum_launch(void* out, const void* in, const void* addend, int64_t n_tokens, int32_t topk, int64_t dim,
+                          int32_t dtype, void* stream) {
   using namespace slm;
   if (n_tokens < 0 || topk < 1 || dim < 1) return SLM_ERR_INVALID_ARG;
   if (dtype != SLM_F16 && dtype != SLM_BF16) return SLM_ERR_UNSUPPORTED;
   if (n_tokens == 0) return SLM_OK;
   if (!out || !in || n_tokens > 65535 * (int64_t)32768) return SLM_ERR_INVALID_ARG;
-  if ((dim & 7) == 0 && (!aligned16(out) || !aligned16(in))) return SLM_ERR_ALIGNMENT;
+  if ((dim & 7) == 0 && (!aligned16(out) || !aligned16(in) || !aligned16(addend))) return SLM_ERR_ALIGNMENT;
   hip_clear_error();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // blockIdx.y carries the token (<= 65535 per launch); x: 16-byte pieces, or a grid-stride loop over elements
@@ -227,12 +238,25 @@ SLM_API int slm_moe_sum(void* out, const void* in, int64_t n_tokens, int32_t top
     const unsigned gy = (unsigned)(n_tokens - t0 < 65535 ? n_tokens - t0 : 65535);
     uint16_t* o = reinterpret_cast<uint16_t*>(out) + t0 * dim;
     const uint16_t* i = reinterpret_cast<const uint16_t*>(in) + t0 * topk * dim;
+    const uint16_t* ad = addend ? reinterpret_cast<const uint16_t*>(addend) + t0 * dim : nullptr;
     if (dtype == SLM_BF16)
-      hipLaunchKernelGGL(moe_sum_kernel<bf16_tag>, dim3(gx, gy), dim3(256), 0, st, o, i, topk, dim);
+      hipLaunchKernelGGL(moe_sum_kernel<bf16_tag>, dim3(gx, gy), dim3(256), 0, st, o, i, ad, topk, dim);
     else
-      hipLaunchKernelGGL(moe_sum_kernel<f16_tag>, dim3(gx, gy), dim3(256), 0, st, o, i, topk, dim);
+      hipLaunchKernelGGL(moe_sum_kernel<f16_tag>, dim3(gx, gy), dim3(256), 0, st, o, i, ad, topk, dim);
   }
   return hip_check_launch();
+}
+
+SLM_API int slm_moe_sum(void* out, const void* in, int64_t n_tokens, int32_t topk, int64_t dim, int32_t dtype,
+                        void* stream) {
+  return moe_sum_launch(out, in, nullptr, n_tokens, topk, dim, dtype, stream);
+}
+
+SLM_API int slm_moe_sum_add(void* out, const void* in, const void* addend, int64_t n_tokens, int32_t topk,
+                            int64_t dim, int32_t dtype, void* stream) {
+  if (n_tokens > 0 && topk >= 1 && dim >= 1 && (dtype == SLM_F16 || dtype == SLM_BF16) && !addend)
+    return SLM_ERR_INVALID_ARG;
+  return moe_sum_launch(out, in, addend, n_tokens, topk, dim, dtype, stream);
 }
 
 }  // extern "C"

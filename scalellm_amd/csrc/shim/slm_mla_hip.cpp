@@ -142,4 +142,61 @@ void mla_set_kv_cache(const torch::Tensor& slot_ids, const torch::Tensor& kv, co
         "slm_mla_set_kv_cache");
 }
 
+void mla_rope_append(torch::Tensor q, const torch::Tensor& kv_a, const torch::Tensor& norm_weight, double eps,
+                     const torch::Tensor& positions, const torch::Tensor& cos_sin, bool interleaved,
+                     const torch::Tensor& slot_ids, torch::Tensor& kv_cache, torch::Tensor& k_rope_cache,
+                     int64_t nope_head_dim, const torch::Tensor& partials) {
+  check_i32(positions, "positions");
+  check_i32(slot_ids, "slot_ids");
+  const int64_t T = positions.numel();
+  TORCH_CHECK(slot_ids.numel() == T, "slm mla: positions and slot_ids must have one entry per token");
+  TORCH_CHECK(kv_cache.is_cuda() && k_rope_cache.is_cuda() && kv_cache.dim() == 2 && k_rope_cache.dim() == 2 &&
+                  kv_cache.stride(1) == 1 && k_rope_cache.stride(1) == 1 && kv_cache.size(0) == k_rope_cache.size(0) &&
+                  k_rope_cache.scalar_type() == kv_cache.scalar_type(),
+              "slm mla: caches [n_slots, latent] and [n_slots, rope] of one dtype with contiguous rows");
+  const int64_t latent = kv_cache.size(1), rope = k_rope_cache.size(1);
+  const auto dt = kv_cache.scalar_type();
+  TORCH_CHECK(norm_weight.is_cuda() && norm_weight.scalar_type() == dt && norm_weight.is_contiguous() &&
+                  norm_weight.numel() == latent,
+              "slm mla: norm_weight must be a contiguous [latent] tensor of the cache dtype");
+  const bool cs_f32 = cos_sin.scalar_type() == torch::kFloat;
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.is_contiguous() && (cs_f32 || cos_sin.scalar_type() == dt) &&
+                  cos_sin.size(-1) == rope,
+              "slm mla: cos_sin must be contiguous [max_pos, rope], fp32 or the activation dtype");
+  int32_t n_heads = 0;
+  if (q.defined() && q.numel() > 0) {
+    TORCH_CHECK(q.is_cuda() && q.dim() == 3 && q.size(0) == T && q.scalar_type() == dt && q.stride(2) == 1 &&
+                    q.stride(1) == q.size(2) && q.size(2) == nope_head_dim + rope,
+                "slm mla: q must be [n_tokens, n_heads, nope + rope], contiguous in its last two dims");
+    n_heads = static_cast<int32_t>(q.size(1));
+  }
+  void* qp = n_heads ? q.data_ptr() : nullptr;
+  const int64_t q_ts = n_heads ? q.stride(0) : 0;
+  if (partials.defined()) {
+    const int64_t n_cols = n_heads * (nope_head_dim + rope) + latent + rope;
+    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == torch::kFloat && partials.is_contiguous() &&
+                    partials.dim() == 3 && partials.size(1) == T && partials.size(2) == n_cols,
+                "slm mla: partials must be contiguous fp32 [n_splits, n_tokens, n_heads (nope + rope) + latent + rope]");
+    check(slm_mla_rope_append_splitk(partials.const_data_ptr<float>(), static_cast<int32_t>(partials.size(0)), qp, q_ts,
+                                     norm_weight.data_ptr(), static_cast<float>(eps),
+                                     positions.const_data_ptr<int32_t>(), cos_sin.data_ptr(), cs_f32 ? 1 : 0,
+                                     interleaved ? 1 : 0, slot_ids.const_data_ptr<int32_t>(), kv_cache.data_ptr(),
+                                     k_rope_cache.data_ptr(), kv_cache.stride(0), k_rope_cache.stride(0), T, n_heads,
+                                     static_cast<int32_t>(nope_head_dim), static_cast<int32_t>(latent),
+                                     static_cast<int32_t>(rope), dtype_code(kv_cache), stream_of(kv_cache)),
+          "slm_mla_rope_append_splitk");
+    return;
+  }
+  TORCH_CHECK(kv_a.defined() && kv_a.is_cuda() && kv_a.dim() == 2 && kv_a.size(0) == T && kv_a.size(1) == latent + rope &&
+                  kv_a.scalar_type() == dt && kv_a.stride(1) == 1,
+              "slm mla: kv_a must be [n_tokens, latent + rope] of the cache dtype with contiguous rows");
+  check(slm_mla_rope_append(qp, q_ts, kv_a.data_ptr(), kv_a.stride(0), norm_weight.data_ptr(), static_cast<float>(eps),
+                            positions.const_data_ptr<int32_t>(), cos_sin.data_ptr(), cs_f32 ? 1 : 0,
+                            interleaved ? 1 : 0, slot_ids.const_data_ptr<int32_t>(), kv_cache.data_ptr(),
+                            k_rope_cache.data_ptr(), kv_cache.stride(0), k_rope_cache.stride(0), T, n_heads,
+                            static_cast<int32_t>(nope_head_dim), static_cast<int32_t>(latent),
+                            static_cast<int32_t>(rope), dtype_code(kv_cache), stream_of(kv_cache)),
+        "slm_mla_rope_append");
+}
+
 }  // namespace slm

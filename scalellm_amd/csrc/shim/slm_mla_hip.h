@@ -34,4 +34,22 @@ void mla_set_kv_cache(const torch::Tensor& slot_ids,  // [n_tokens] int32
                       torch::Tensor& kv_cache,        // [n_slots, head_dim]
                       torch::Tensor& k_rope_cache);   // [n_slots, rope_head_dim]
 
+// The MLA prologue of the C ABI's section 18 in one launch: the latent columns of kv_a RMS-normalised into
+// kv_cache[slot], its rope columns rotated into k_rope_cache[slot], the last rope_head_dim columns of every head of q
+// rotated in place.  q and kv_a may be column slices of one GEMM output; an undefined q means no query heads.  A
+// negative slot id is graph padding: q is rotated, the caches are not written.  partials (defined): the fp32 split-K
+// slabs [n_splits, n_tokens, N] of the fused [q | latent | k_pe] GEMM; kv_a is not used then and q is written whole.
+void mla_rope_append(torch::Tensor q,                    // [n_tokens, n_heads, nope + rope] or undefined
+                     const torch::Tensor& kv_a,          // [n_tokens, latent + rope] (undefined with partials)
+                     const torch::Tensor& norm_weight,   // [latent]
+                     double eps,
+                     const torch::Tensor& positions,     // [n_tokens] int32
+                     const torch::Tensor& cos_sin,       // [max_pos, rope], fp32 or the activation dtype
+                     bool interleaved,
+                     const torch::Tensor& slot_ids,      // [n_tokens] int32
+                     torch::Tensor& kv_cache,            // [n_slots, latent]
+                     torch::Tensor& k_rope_cache,        // [n_slots, rope]
+                     int64_t nope_head_dim,
+                     const torch::Tensor& partials = torch::Tensor());
+
 }  // namespace slm

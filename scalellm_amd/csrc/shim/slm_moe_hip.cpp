@@ -45,6 +45,19 @@ int dtype_code(const torch::Tensor& t) {
 
 namespace slm {
 
+void moe_sum_add(const torch::Tensor& input, const torch::Tensor& addend, torch::Tensor& output) {
+  TORCH_CHECK(input.is_cuda() && addend.is_cuda() && output.is_cuda() && input.dim() == 3 && input.is_contiguous() &&
+                  addend.is_contiguous() && output.is_contiguous() && input.scalar_type() == output.scalar_type() &&
+                  addend.scalar_type() == output.scalar_type() && output.dim() == 2 && addend.dim() == 2 &&
+                  output.size(0) == input.size(0) && output.size(1) == input.size(2) &&
+                  addend.size(0) == output.size(0) && addend.size(1) == output.size(1),
+              "slm moe: moe_sum_add takes contiguous [n_tokens, topk, dim] + [n_tokens, dim] -> [n_tokens, dim] of one "
+              "dtype");
+  check(slm_moe_sum_add(output.data_ptr(), input.data_ptr(), addend.data_ptr(), input.size(0),
+                        static_cast<int32_t>(input.size(1)), input.size(2), dtype_code(input), stream_of(input)),
+        "slm_moe_sum_add");
+}
+
 void moe_topk_softmax(const torch::Tensor& gating_logits, torch::Tensor& topk_weights, torch::Tensor& topk_indices,
                       bool renormalize) {
   check_route(gating_logits, topk_weights, topk_indices);

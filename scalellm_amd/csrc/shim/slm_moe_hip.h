@@ -50,6 +50,12 @@ void sum_out(const torch::Tensor& input,  // [n_tokens, topk, dim]
 
 namespace slm {
 
+// sum_out with one more row per token, the shared experts' output, added last in the same fp32 accumulation
+// (slm_moe_sum_add): bit-identical to sum_out over [n_tokens, topk + 1, dim].  output may be addend.
+void moe_sum_add(const torch::Tensor& input,   // [n_tokens, topk, dim]
+                 const torch::Tensor& addend,  // [n_tokens, dim]
+                 torch::Tensor& output);       // [n_tokens, dim]
+
 // topk_softmax with the k weights divided by their sum (Mixtral's rule)
 void moe_topk_softmax(const torch::Tensor& gating_logits, torch::Tensor& topk_weights, torch::Tensor& topk_indices,
                       bool renormalize);

@@ -282,6 +282,9 @@ PYBIND11_MODULE(_slm_shim, m) {
         py::arg("cu_sum"));
   m.def("moe_sum_out", [](const torch::Tensor& input, torch::Tensor output) { llm::kernel::moe::sum_out(input, output); },
         py::arg("input"), py::arg("output"));
+  m.def("moe_sum_add", [](const torch::Tensor& input, const torch::Tensor& addend, torch::Tensor output) {
+          slm::moe_sum_add(input, addend, output);
+        }, py::arg("input"), py::arg("addend"), py::arg("output"));
   m.def("moe_w4_grouped_gemm",
         [](const torch::Tensor& a, const torch::Tensor& wq, const torch::Tensor& sz, torch::Tensor c,
            const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens,
@@ -347,6 +350,17 @@ PYBIND11_MODULE(_slm_shim, m) {
                                torch::Tensor kv_cache, torch::Tensor k_rope_cache) {
           slm::mla_set_kv_cache(slot_ids, kv, k_rope, kv_cache, k_rope_cache);
         }, py::arg("slot_ids"), py::arg("kv"), py::arg("k_rope"), py::arg("kv_cache"), py::arg("k_rope_cache"));
+  m.def("mla_rope_append",
+        [](const c10::optional<torch::Tensor>& q, const c10::optional<torch::Tensor>& kv_a,
+           const torch::Tensor& norm_weight, double eps, const torch::Tensor& positions, const torch::Tensor& cos_sin,
+           bool interleaved, const torch::Tensor& slot_ids, torch::Tensor kv_cache, torch::Tensor k_rope_cache,
+           int64_t nope_head_dim, const c10::optional<torch::Tensor>& partials) {
+          slm::mla_rope_append(q.has_value() ? *q : torch::Tensor(), kv_a.has_value() ? *kv_a : torch::Tensor(),
+                               norm_weight, eps, positions, cos_sin, interleaved, slot_ids, kv_cache, k_rope_cache,
+                               nope_head_dim, partials.has_value() ? *partials : torch::Tensor());
+        }, py::arg("q"), py::arg("kv_a"), py::arg("norm_weight"), py::arg("eps"), py::arg("positions"),
+        py::arg("cos_sin"), py::arg("interleaved"), py::arg("slot_ids"), py::arg("kv_cache"), py::arg("k_rope_cache"),
+        py::arg("nope_head_dim"), py::arg("partials") = py::none());
   py::class_<slm::InputParameters>(m, "InputParameters")
       .def(py::init<>())
       .def_readwrite("num_sequences", &slm::InputParameters::num_sequences)

@@ -1599,6 +1599,20 @@ def moe_sum(inp: torch.Tensor, out: torch.Tensor) -> None:
                                  _dtype_code(inp), _stream()), "slm_moe_sum")
 
 
+def moe_sum_add(inp: torch.Tensor, addend: torch.Tensor, out: torch.Tensor) -> None:
+    """out [T, dim] = sum over j of inp [T, k, dim], then + addend [T, dim] (the shared experts' output): fp32, that
+    order, one rounding -- the bits of moe_sum over [T, k + 1, dim] with the addend as slot k (slm_moe_sum_add).
+    `out` may be `addend`."""
+    _require_gpu(inp, addend, out)
+    if inp.dim() != 3 or not inp.is_contiguous() or not out.is_contiguous() or not addend.is_contiguous() or \
+            inp.dtype != out.dtype or addend.dtype != out.dtype or \
+            tuple(out.shape) != (inp.size(0), inp.size(2)) or addend.shape != out.shape:
+        raise SlmError("moe_sum_add: input [T, k, dim], addend [T, dim] and output [T, dim] must be contiguous and "
+                       "of one dtype")
+    check(_lib.lib().slm_moe_sum_add(out.data_ptr(), inp.data_ptr(), addend.data_ptr(), inp.size(0), inp.size(1),
+                                     inp.size(2), _dtype_code(inp), _stream()), "slm_moe_sum_add")
+
+
 def moe_w4_grouped_gemm(a: torch.Tensor, experts: PackedMoeW4, c: torch.Tensor, sorted_token_idxes: torch.Tensor,
                         expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor, a_div: int,
                         row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
@@ -1976,3 +1990,58 @@ def mla_set_kv_cache(slot_ids: torch.Tensor, kv: torch.Tensor, k_rope: torch.Ten
                                           k_rope.stride(0), kv_cache.data_ptr(), k_rope_cache.data_ptr(),
                                           kv_cache.stride(0), k_rope_cache.stride(0), kv.size(0), kv.size(1),
                                           k_rope.size(1), _dtype_code(kv), _stream()), "slm_mla_set_kv_cache")
+
+
+def mla_rope_append(q: Optional[torch.Tensor], kv_a: Optional[torch.Tensor], norm_weight: torch.Tensor, eps: float,
+                    positions: torch.Tensor, cos_sin: torch.Tensor, interleaved: bool, slot_ids: torch.Tensor,
+                    kv_cache: torch.Tensor, k_rope_cache: torch.Tensor, nope_head_dim: int,
+                    partials: Optional[DeferredPartials] = None) -> None:
+    """The MLA prologue in one launch (slm_hip.h section 18): the latent columns of kv_a [T, latent + rope] are
+    RMS-normalised (rms_norm's bits) into kv_cache[slot], its rope columns rotated (apply_rotary_pos_emb's bits)
+    into k_rope_cache[slot], and the last `rope` columns of every head of q [T, n_heads, nope + rope] rotated in
+    place.  q and kv_a may be column slices of one fused GEMM output; q = None: no query heads.  A negative slot id
+    is graph padding: q is rotated, the caches are not written.
+
+    partials (truthy): the fused [q | latent | k_pe] GEMM output was NOT written -- linear / fp8_linear(...,
+    defer_reduce=True) left fp32 split-K slabs behind; the kernel sums them itself (the reduce kernel's order and
+    rounding: identical bits, one launch less) and WRITES q whole.  kv_a is not used then."""
+    L = _lib.lib()
+    _require_gpu(q, kv_a, norm_weight, positions, cos_sin, slot_ids, kv_cache, k_rope_cache)
+    T = positions.numel()
+    latent, rope = kv_cache.size(-1), k_rope_cache.size(-1)
+    for t in (positions, slot_ids):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != T:
+            raise SlmError("positions / slot_ids must be contiguous int32 [n_tokens]")
+    if kv_cache.dim() != 2 or k_rope_cache.dim() != 2 or kv_cache.stride(1) != 1 or k_rope_cache.stride(1) != 1 or \
+            kv_cache.size(0) != k_rope_cache.size(0) or kv_cache.dtype != k_rope_cache.dtype:
+        raise SlmError("mla_rope_append: caches [n_slots, latent] and [n_slots, rope] of one dtype, rows contiguous")
+    dt = kv_cache.dtype
+    if norm_weight.dtype != dt or not norm_weight.is_contiguous() or norm_weight.numel() != latent:
+        raise SlmError("mla_rope_append: norm_weight must be a contiguous [latent] tensor of the cache dtype")
+    is_f32 = 1 if cos_sin.dtype == torch.float32 else 0
+    if (not is_f32 and cos_sin.dtype != dt) or not cos_sin.is_contiguous() or cos_sin.size(-1) != rope:
+        raise SlmError("cos_sin must be contiguous [max_pos, rope], fp32 or the activation dtype")
+    n_heads = 0
+    if q is not None:
+        if q.dim() != 3 or q.size(0) != T or q.dtype != dt or q.stride(2) != 1 or q.stride(1) != q.size(2) or \
+                q.size(2) != nope_head_dim + rope:
+            raise SlmError("q must be [n_tokens, n_heads, nope + rope] of the cache dtype, contiguous in its last "
+                           "two dims")
+        n_heads = q.size(1)
+    q_ptr, q_ts = (q.data_ptr(), q.stride(0)) if n_heads else (None, 0)
+    tail = (positions.data_ptr(), cos_sin.data_ptr(), is_f32, 1 if interleaved else 0, slot_ids.data_ptr(),
+            kv_cache.data_ptr(), k_rope_cache.data_ptr(), kv_cache.stride(0), k_rope_cache.stride(0), T, n_heads,
+            int(nope_head_dim), latent, rope, _dtype_code(kv_cache), _stream())
+    if partials:
+        if not isinstance(partials, DeferredPartials):
+            raise SlmError("mla_rope_append(partials=...) takes the handle linear(defer_reduce=True) returned")
+        n_cols = n_heads * (nope_head_dim + rope) + latent + rope
+        partials.check(kv_cache.device, T * n_cols, "mla_rope_append(partials=...)")
+        check(L.slm_mla_rope_append_splitk(partials.ptr, partials.splits, q_ptr, q_ts, norm_weight.data_ptr(),
+                                           float(eps), *tail), "slm_mla_rope_append_splitk")
+        return
+    if kv_a is None or kv_a.dim() != 2 or kv_a.size(0) != T or kv_a.size(1) != latent + rope or kv_a.dtype != dt or \
+            kv_a.stride(1) != 1:
+        raise SlmError("kv_a must be [n_tokens, latent + rope] of the cache dtype with contiguous rows")
+    check(L.slm_mla_rope_append(q_ptr, q_ts, kv_a.data_ptr(), kv_a.stride(0), norm_weight.data_ptr(), float(eps),
+                                *tail), "slm_mla_rope_append")

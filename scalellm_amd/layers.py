@@ -767,3 +767,172 @@ class Activation:
         if n not in table:
             raise ValueError(f"Unsupported activation function: {name}")
         return table[n]
+
+
+# ---------------------------------------------------------------------------------------
+# multi-head latent attention (DeepSeek-V2): slm_hip.h sections 18 (prologue), 10 (the two absorbed per-head
+# projections as grouped GEMMs with the head as the expert) and 11 (paged attention over the latent cache)
+# ---------------------------------------------------------------------------------------
+class LatentKVCache:
+    """The two caches of section 11 over one block pool: kv_cache [n_blocks * block_size, latent] (the normalised
+    latent row, K and V at once) and k_rope_cache [n_blocks * block_size, rope] (the one rotated key per token)."""
+
+    def __init__(self, n_blocks: int, block_size: int, latent_dim: int, rope_head_dim: int, dtype: torch.dtype,
+                 device):
+        self._block_size = block_size
+        self.kv_cache = torch.zeros(n_blocks * block_size, latent_dim, dtype=dtype, device=device)
+        self.k_rope_cache = torch.zeros(n_blocks * block_size, rope_head_dim, dtype=dtype, device=device)
+
+    def block_size(self) -> int:
+        return self._block_size
+
+    def get_kv_cache(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self.kv_cache, self.k_rope_cache
+
+
+class MLAAttention:
+    """HuggingFace DeepseekV2Attention in the ABSORBED form, on one rank:
+
+      [q | c | k_pe] = x W^T          one column-parallel GEMM over q_proj | kv_a_proj_with_mqa, split-K deferred
+                                      (with q_lora_rank: q_a_proj, q_a_layernorm, q_b_proj and kv_a_proj_with_mqa)
+      prologue                        kernels.mla_rope_append: latent RMSNorm, RoPE, append into both caches
+      q_lat[t, h] = q_nope[t, h] W_UK[h]          kernels.moe_grouped_gemm, the head as the expert
+      out_lat = attention over the latent cache   kernels.mla_paged_kv (prefill, chunked prefill, decode)
+      v[t, h] = out_lat[t, h] W_UV[h]^T           kernels.moe_grouped_gemm over kv_b_proj.weight as it is
+      o = v W_o^T                                 row-parallel GEMM (split-K deferred for the caller's norm)
+
+    kv_b_proj.weight [n_heads (nope + v), latent] is kept in T (an fp8 one is dequantised once at load): its v
+    rows are used in place through a strided view, its k_nope rows transposed once into W_UK [n_heads, latent, nope].
+    The grouped GEMMs need an aligned list (slm_moe_align_block of ids[t, j] = j, E = n_heads, block 32); it depends
+    on the token count alone and is built once per count (prepare(T): outside a graph capture).
+    quant_method "none" or "fp8" selects the classes of the other linears."""
+
+    def __init__(self, hidden: int, n_heads: int, nope_head_dim: int, rope_head_dim: int, v_head_dim: int,
+                 latent_dim: int, q_lora_rank: Optional[int], cos_sin: torch.Tensor, interleaved: bool,
+                 sm_scale: float, eps: float, max_tokens: int, quant_method: str = "none",
+                 parallel_args: Optional[ParallelArgs] = None, dtype: torch.dtype = torch.bfloat16, device="cuda"):
+        pa = parallel_args or ParallelArgs()
+        if pa.world_size > 1:
+            raise ValueError("MLAAttention runs on one rank")
+        if quant_method not in ("none", "fp8"):
+            raise ValueError(f"quant_method must be 'none' or 'fp8', not {quant_method!r}")
+        self.hidden, self.n_heads, self.nope, self.rope = hidden, n_heads, nope_head_dim, rope_head_dim
+        self.v_dim, self.latent, self.q_lora_rank = v_head_dim, latent_dim, q_lora_rank
+        self.cos_sin, self.interleaved, self.sm_scale, self.eps = cos_sin, interleaved, sm_scale, eps
+        self.max_tokens, self.dtype, self.device, self.quant_method = max_tokens, dtype, device, quant_method
+        Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if quant_method == "fp8" else \
+            (ColumnParallelLinear, RowParallelLinear)
+        qk, H = nope_head_dim + rope_head_dim, n_heads
+        self.qk = qk
+        if q_lora_rank is None:
+            self.qkv_a = Col(hidden, H * qk + latent_dim + rope_head_dim, False, False, pa, dtype, device)
+            self.q_a = self.q_b = self.kv_a = None
+        else:
+            self.qkv_a = None
+            self.q_a = Col(hidden, q_lora_rank, False, False, pa, dtype, device)
+            self.q_b = Col(q_lora_rank, H * qk, False, False, pa, dtype, device)
+            self.kv_a = Col(hidden, latent_dim + rope_head_dim, False, False, pa, dtype, device)
+        self.o = Row(H * v_head_dim, hidden, False, True, pa, dtype, device)
+        self.q_a_norm: Optional[torch.Tensor] = None
+        self.kv_a_norm: Optional[torch.Tensor] = None
+        self.kv_b: Optional[torch.Tensor] = None        # [H (nope + v), latent] T, the checkpoint tensor
+        self.w_uk: Optional[torch.Tensor] = None        # [H, latent, nope] T
+        self.w_uv: Optional[torch.Tensor] = None        # [H, v, latent] T: a view of kv_b
+        e = lambda *s: torch.empty(*s, dtype=dtype, device=device)  # noqa: E731
+        T = max_tokens
+        self.buf = dict(q=e(T, H, qk), q_lat=e(T * H, latent_dim), out_lat=e(T, H, latent_dim), v=e(T * H, v_head_dim))
+        if q_lora_rank is None:
+            self.buf["row"] = e(T, H * qk + latent_dim + rope_head_dim)
+        else:
+            self.buf.update(qa=e(T, q_lora_rank), qa_n=e(T, q_lora_rank), kv_a=e(T, latent_dim + rope_head_dim))
+        self._aligned: Dict[int, tuple] = {}
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        """HuggingFace names relative to `self_attn.`: q_proj | q_a_proj, q_a_layernorm, q_b_proj;
+        kv_a_proj_with_mqa, kv_a_layernorm, kv_b_proj, o_proj (.weight; fp8: .weight_scale beside it)."""
+        sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}  # noqa: E731
+        if self.qkv_a is not None:
+            self.qkv_a.load_state_dict(sd, prefixes=["q_proj.", "kv_a_proj_with_mqa."])
+        else:
+            self.q_a.load_state_dict(sub("q_a_proj."))
+            self.q_b.load_state_dict(sub("q_b_proj."))
+            self.kv_a.load_state_dict(sub("kv_a_proj_with_mqa."))
+            if "q_a_layernorm.weight" in sd:
+                self.q_a_norm = sd["q_a_layernorm.weight"].to(self.device, self.dtype).contiguous()
+        self.o.load_state_dict(sub("o_proj."))
+        if "kv_a_layernorm.weight" in sd:
+            self.kv_a_norm = sd["kv_a_layernorm.weight"].to(self.device, self.dtype).contiguous()
+        if "kv_b_proj.weight" in sd:
+            w = sd["kv_b_proj.weight"].to(self.device)
+            if w.dtype == torch.float8_e4m3fn:   # dequantised once: the absorbed projections run in T
+                scale = _Fp8LinearMixin._channel_scale(sd["kv_b_proj.weight_scale"], w.size(0), "kv_b weight_scale")
+                w = w.float() * scale.to(self.device)[:, None]
+            H, nope, v, latent = self.n_heads, self.nope, self.v_dim, self.latent
+            if tuple(w.shape) != (H * (nope + v), latent):
+                raise ValueError(f"kv_b_proj.weight size mismatch: {tuple(w.shape)}")
+            self.kv_b = w.to(self.dtype).contiguous()
+            per_head = self.kv_b.view(H, nope + v, latent)
+            self.w_uk = per_head[:, :nope, :].transpose(1, 2).contiguous()
+            self.w_uv = per_head[:, nope:, :]   # no copy: expert stride (nope + v) * latent, row stride latent
+
+    def verify_loaded_weights(self) -> None:
+        for lin in (self.qkv_a, self.q_a, self.q_b, self.kv_a, self.o):
+            if lin is not None:
+                lin.verify_loaded_weights()
+        if self.kv_b is None or self.kv_a_norm is None or (self.q_a is not None and self.q_a_norm is None):
+            raise RuntimeError("kv_b_proj / kv_a_layernorm / q_a_layernorm is not loaded")
+
+    def prepare(self, n_tokens: int) -> tuple:
+        """(sorted_token_idxes, expert_ids, n_padded) of the per-head grouped GEMMs for this token count: row
+        t * n_heads + h belongs to expert h.  Built on first use; call it before capturing a graph."""
+        if n_tokens not in self._aligned:
+            H = self.n_heads
+            ids = torch.arange(H, dtype=torch.int32, device=self.device).repeat(n_tokens).contiguous()
+            max_padded, max_blocks = kernels.moe_align_capacity(n_tokens * H, H, kernels.MOE_GEMM_BLOCK)
+            srt = torch.empty(max(max_padded, 1), dtype=torch.int32, device=self.device)
+            eids = torch.empty(max(max_blocks, 1), dtype=torch.int32, device=self.device)
+            n_padded = torch.zeros(1, dtype=torch.int32, device=self.device)
+            kernels.moe_align_block(ids, H, kernels.MOE_GEMM_BLOCK, srt, eids, n_padded)
+            self._aligned[n_tokens] = (srt, eids, n_padded)
+        return self._aligned[n_tokens]
+
+    def forward(self, x: torch.Tensor, positions: torch.Tensor, kv_cache: LatentKVCache,
+                input_params: InputParameters, out: Optional[torch.Tensor] = None,
+                defer_splitk: bool = False) -> torch.Tensor:
+        """x [T, hidden] -> the o projection [T, hidden].  defer_splitk: the fused projection's slabs go to the
+        prologue, and a split-K o projection leaves its slabs for the caller's RMSNorm (self.o.deferred is truthy
+        then and the returned tensor is NOT written)."""
+        T, H, b = x.size(0), self.n_heads, self.buf
+        if T > self.max_tokens:
+            raise kernels.SlmError(f"{T} tokens exceed max_tokens = {self.max_tokens}")
+        kvc, krc = kv_cache.get_kv_cache()
+        q = b["q"][:T]
+        slots = input_params.new_cache_slots
+        if self.qkv_a is not None:
+            row = self.qkv_a.forward(x, out=b["row"][:T], defer_splitk=defer_splitk)
+            part = self.qkv_a.deferred if defer_splitk else None
+            if part:   # the slab form writes q whole, into the dense buffer the absorbed GEMM reads
+                kernels.mla_rope_append(q, None, self.kv_a_norm, self.eps, positions, self.cos_sin, self.interleaved,
+                                        slots, kvc, krc, self.nope, partials=part)
+            else:      # the row was written: (t, h) rows are evenly spaced only in a dense q
+                q.view(T, H * self.qk).copy_(row[:, :H * self.qk])
+                kernels.mla_rope_append(q, row[:, H * self.qk:], self.kv_a_norm, self.eps, positions, self.cos_sin,
+                                        self.interleaved, slots, kvc, krc, self.nope)
+        else:
+            qa = self.q_a.forward(x, out=b["qa"][:T])
+            kernels.rms_norm(b["qa_n"][:T], qa, self.q_a_norm, self.eps)
+            self.q_b.forward(b["qa_n"][:T], out=q.view(T, H * self.qk))
+            kv_a = self.kv_a.forward(x, out=b["kv_a"][:T])
+            kernels.mla_rope_append(q, kv_a, self.kv_a_norm, self.eps, positions, self.cos_sin, self.interleaved,
+                                    slots, kvc, krc, self.nope)
+        aligned = self.prepare(T)
+        q_lat, out_lat, v = b["q_lat"][:T * H], b["out_lat"][:T], b["v"][:T * H]
+        kernels.moe_grouped_gemm(q.view(T * H, self.qk)[:, :self.nope], self.w_uk, q_lat, *aligned, a_div=1)
+        kernels.mla_paged_kv(out_lat, q_lat.view(T, H, self.latent), q[:, :, self.nope:], kvc, krc,
+                             input_params.q_cu_seq_lens, input_params.kv_cu_seq_lens, input_params.block_tables,
+                             input_params.cu_block_lens, kv_cache.block_size(), input_params.q_max_seq_len,
+                             input_params.kv_max_seq_len, self.sm_scale)
+        kernels.moe_grouped_gemm(out_lat.view(T * H, self.latent), self.w_uv, v, *aligned, a_div=1)
+        return self.o.forward(v.view(T, H * self.v_dim), out=out, reduce=False, defer_splitk=defer_splitk)
+
+    __call__ = forward

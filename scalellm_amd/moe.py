@@ -306,8 +306,12 @@ class FusedMoE:
         return self._buf
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
-                router_logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """router_logits_out (router="fused" only): contiguous fp32 [T, n_experts] that receives the router logits"""
+                router_logits_out: Optional[torch.Tensor] = None,
+                shared_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """router_logits_out (router="fused" only): contiguous fp32 [T, n_experts] that receives the router logits.
+        shared_out: contiguous [T, hidden], the output of the always-on shared experts (DeepSeek) for the same rows;
+        it is added to the routed sum in the final launch (kernels.moe_sum_add: fp32, after the k routed rows, one
+        rounding) instead of in a launch of its own.  It may be `out`."""
         if router_logits_out is not None and self.router != "fused":
             raise SlmError("router_logits_out needs router='fused'")
         if self.experts.gate_up is None:
@@ -320,6 +324,9 @@ class FusedMoE:
             raise SlmError(f"{T} tokens exceed max_tokens = {self.max_tokens} (the buffers are sized once)")
         if out is None:
             out = torch.empty(T, self.hidden, dtype=x.dtype, device=x.device)
+        if shared_out is not None and (shared_out.numel() != T * self.hidden or shared_out.dtype != x.dtype or
+                                       not shared_out.is_contiguous()):
+            raise SlmError("shared_out must be a contiguous [T, hidden] tensor of the activations' dtype")
         if T == 0:
             return out.view(x.shape)
         b = self._buffers()
@@ -350,7 +357,11 @@ class FusedMoE:
         kernels.moe_align_block(ids, self.n_experts, kernels.MOE_GEMM_BLOCK, srt, eids, b["n_padded"])
         self.experts.gemm("gate_up", x2, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
         self.experts.gemm("down", act, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
-        kernels.moe_sum(down.view(T, k, self.hidden), out.view(T, self.hidden))
+        if shared_out is None:
+            kernels.moe_sum(down.view(T, k, self.hidden), out.view(T, self.hidden))
+        else:
+            kernels.moe_sum_add(down.view(T, k, self.hidden), shared_out.view(T, self.hidden),
+                                out.view(T, self.hidden))
         return out.view(x.shape)
 
     __call__ = forward
