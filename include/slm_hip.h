@@ -1506,6 +1506,70 @@ SLM_API int slm_mla_rope_append_splitk(const float* partials /* [n_splits, T, N]
                                        int32_t n_heads, int32_t nope_head_dim, int32_t latent_dim,
                                        int32_t rope_head_dim, int32_t dtype, void* stream);
 
+/* ========================================================================== */
+/* 19. QK-norm prologue: per-head q / k RMSNorm + RoPE + KV append            */
+/*    What a Qwen3 / Qwen3-MoE layer does between its qkv projection and      */
+/*    section 2's attention, in ONE launch.  For every token row t, every q   */
+/*    head h < n_heads and every k head h < n_kv_heads, with D = head_dim in  */
+/*    {64, 128, 256} and rot_dim == D (the whole head rotates):               */
+/*      x    = q[t, h, :D] (at q + t * q_token_stride + h D) or k[t, h, :D]   */
+/*      n    = RMSNorm(x; w, eps) over the head's D values, w = q_norm_weight */
+/*             or k_norm_weight ([D], shared by all heads), section 5's       */
+/*             rounding (fp32 sum of squares, T(T(x rs) w));                  */
+/*      n rotated by cos_sin[positions[t]] -- section 5's row layout          */
+/*             [cos(D/2) | sin(D/2)], in T (cos_sin_is_f32 = 0) or fp32;      */
+/*             interleaved != 0 pairs (2i, 2i + 1), 0 pairs (i, i + D/2);     */
+/*      q and k are written IN PLACE; slot = slot_ids[t] >= 0: k and v also   */
+/*             go to key_cache / value_cache [n_slots, n_kv_heads, D]         */
+/*             (dense slot rows, as slm_rope_kv_append).  slot < 0 is graph   */
+/*             padding: q and k are still rotated in place, nothing is        */
+/*             appended.  slot_ids == NULL skips the append.  v is only       */
+/*             copied.                                                        */
+/*    BIT-IDENTICAL to slm_rms_norm over contiguous copies of q viewed as     */
+/*    [T * n_heads, D] rows and of k as [T * n_kv_heads, D] rows, followed by */
+/*    slm_rope_kv_append (the per-lane sums, the wave reduction, rope_unit8:  */
+/*    shared through common.h and rope.h).                                    */
+/*    slm_qk_norm_rope_kv_append_splitk (slab form): the inputs are the fp32  */
+/*    split-K slabs [n_splits, T, N] a deferred GEMM left behind (sections 3  */
+/*    and 13), row = [q | k | v], N = (n_heads + 2 n_kv_heads) D; every value */
+/*    is T(sum_s partials[s][t][col]) in the reduce kernel's slice order      */
+/*    (splitk_sum4), so the result is bit-identical to "reduce, then the      */
+/*    plain form".  q, k and v are OUTPUTS, as in                             */
+/*    slm_rope_kv_append_splitk.                                              */
+/*    f16 / bf16; token strides multiples of 8 elements, every base 16-byte   */
+/*    aligned.  One launch on the given stream; no allocation, no host sync,  */
+/*    no atomics, no LDS or barrier: capture-safe, repeats are bit-identical. */
+/*    positions and slot_ids are read on the device only, so a captured       */
+/*    launch replays over changed ones.                                       */
+/*    Before any launch: negative n_tokens / head_dim / rot_dim, n_heads or   */
+/*    n_kv_heads < 1, a NULL among q / k / v / q_norm_weight / k_norm_weight  */
+/*    / positions / cos_sin, caches NULL with slot_ids given, partials NULL   */
+/*    or n_splits < 1 (slab form) -> SLM_ERR_INVALID_ARG; other head_dim,     */
+/*    rot_dim != head_dim, other dtypes -> SLM_ERR_UNSUPPORTED; a base or     */
+/*    stride that is not 16-byte aligned -> SLM_ERR_ALIGNMENT.  n_tokens == 0 */
+/*    is a no-op.                                                             */
+/* ========================================================================== */
+SLM_API int slm_qk_norm_rope_kv_append(void* q /* [T, n_heads, D] in place */, int64_t q_token_stride,
+                                       void* k /* [T, n_kv_heads, D] in place */, int64_t k_token_stride,
+                                       const void* v /* [T, n_kv_heads, D] */, int64_t v_token_stride,
+                                       const void* q_norm_weight /* [D] */, const void* k_norm_weight /* [D] */,
+                                       float eps, const int32_t* positions /* [T] */,
+                                       const void* cos_sin /* [max_pos, rot_dim] */, int32_t cos_sin_is_f32,
+                                       int32_t rot_dim, int32_t interleaved, const int32_t* slot_ids /* [T] or NULL */,
+                                       void* key_cache, void* value_cache, int64_t n_tokens, int32_t n_heads,
+                                       int32_t n_kv_heads, int32_t head_dim, int32_t dtype, void* stream);
+SLM_API int slm_qk_norm_rope_kv_append_splitk(const float* partials /* [n_splits, T, N] */, int32_t n_splits,
+                                              void* q /* out */, int64_t q_token_stride, void* k /* out */,
+                                              int64_t k_token_stride, void* v /* out */, int64_t v_token_stride,
+                                              const void* q_norm_weight /* [D] */,
+                                              const void* k_norm_weight /* [D] */, float eps,
+                                              const int32_t* positions /* [T] */,
+                                              const void* cos_sin /* [max_pos, rot_dim] */, int32_t cos_sin_is_f32,
+                                              int32_t rot_dim, int32_t interleaved,
+                                              const int32_t* slot_ids /* [T] or NULL */, void* key_cache,
+                                              void* value_cache, int64_t n_tokens, int32_t n_heads,
+                                              int32_t n_kv_heads, int32_t head_dim, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

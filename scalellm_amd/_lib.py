@@ -399,6 +399,14 @@ def lib() -> C.CDLL:
          [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
           C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+        ("slm_qk_norm_rope_kv_append", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
+          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+        ("slm_qk_norm_rope_kv_append_splitk", C.c_int,
+         [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+          C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+          C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
         ("slm_moe_w4a16_gemm", C.c_int, [C.POINTER(MoeGemmArgs), C.c_void_p]),
         ("slm_moe_gemm", C.c_int, [C.POINTER(MoeDenseGemmArgs), C.c_void_p]),
         ("slm_mla_paged_kv_workspace_bytes", C.c_size_t, [C.POINTER(MlaArgs)]),

@@ -213,6 +213,25 @@ __device__ __forceinline__ f32x4 splitk_sum4(const float* __restrict__ src, cons
   return s;
 }
 
+// 8 packed values of T -> fp32
+template <typename T>
+__device__ __forceinline__ void unpack8(const u32x4 a, float (&f)[8]) {
+  f[0] = lo_f32<T>(a.x); f[1] = hi_f32<T>(a.x); f[2] = lo_f32<T>(a.y); f[3] = hi_f32<T>(a.y);
+  f[4] = lo_f32<T>(a.z); f[5] = hi_f32<T>(a.z); f[6] = lo_f32<T>(a.w); f[7] = hi_f32<T>(a.w);
+}
+
+// T(sum over slabs) of 8 consecutive columns: the bits the split-K reduce kernel would have stored (the deferred
+// consumers mla_glue.hip and qk_norm.hip)
+template <typename T>
+__device__ __forceinline__ u32x4 slab_sum8(const float* __restrict__ src, const int64_t slab, const int n_splits) {
+  const f32x4 s0 = splitk_sum4(src, slab, n_splits);
+  const f32x4 s1 = splitk_sum4(src + 4, slab, n_splits);
+  u32x4 a;
+  a.x = pack2<T>(s0.x, s0.y); a.y = pack2<T>(s0.z, s0.w);
+  a.z = pack2<T>(s1.x, s1.y); a.w = pack2<T>(s1.z, s1.w);
+  return a;
+}
+
 // C[m, n] = T( sum_s part[s][m][n] + bias[n] ): THE split-K reduce (w4.hip, dense.hip).  A deferred consumer
 // (splitk_sum4, the same order) and this launch give identical bits
 template <typename T>

@@ -24,12 +24,6 @@ __device__ __forceinline__ u32x4 gemma_apply8(const float (&h)[8], const float r
   return r;
 }
 
-template <typename T>
-__device__ __forceinline__ void unpack8(const u32x4 a, float (&f)[8]) {
-  f[0] = lo_f32<T>(a.x); f[1] = hi_f32<T>(a.x); f[2] = lo_f32<T>(a.y); f[3] = hi_f32<T>(a.y);
-  f[4] = lo_f32<T>(a.z); f[5] = hi_f32<T>(a.z); f[6] = lo_f32<T>(a.w); f[7] = hi_f32<T>(a.w);
-}
-
 // sum over the row of the four waves' partial sums; `red` is this reduction's own LDS slot
 __device__ __forceinline__ float row_sum256(float v, float* red, const int tid) {
   v = group_sum<64>(v);

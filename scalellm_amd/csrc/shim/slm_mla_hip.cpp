@@ -199,4 +199,59 @@ void mla_rope_append(torch::Tensor q, const torch::Tensor& kv_a, const torch::Te
         "slm_mla_rope_append");
 }
 
+void qk_norm_rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v, const torch::Tensor& q_norm_weight,
+                            const torch::Tensor& k_norm_weight, double eps, const torch::Tensor& positions,
+                            const torch::Tensor& cos_sin, bool interleaved, const torch::Tensor& slot_ids,
+                            const torch::Tensor& key_cache, const torch::Tensor& value_cache,
+                            const torch::Tensor& partials) {
+  check_i32(positions, "positions");
+  const int64_t T = positions.numel();
+  const auto dt = q.scalar_type();
+  for (const torch::Tensor* t : {&q, &k, &v})
+    TORCH_CHECK(t->is_cuda() && t->dim() == 3 && t->size(0) == T && t->scalar_type() == dt && t->stride(2) == 1 &&
+                    t->stride(1) == t->size(2),
+                "slm qk_norm: q / k / v must be [n_tokens, heads, head_dim] of one dtype, contiguous in their last "
+                "two dims");
+  const int64_t D = q.size(2);
+  TORCH_CHECK(k.size(2) == D && v.sizes() == k.sizes(), "slm qk_norm: head_dim of q / k / v must match; v like k");
+  for (const torch::Tensor* w : {&q_norm_weight, &k_norm_weight})
+    TORCH_CHECK(w->is_cuda() && w->scalar_type() == dt && w->is_contiguous() && w->numel() == D,
+                "slm qk_norm: the norm weights must be contiguous [head_dim] tensors of the activation dtype");
+  const bool cs_f32 = cos_sin.scalar_type() == torch::kFloat;
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.is_contiguous() && (cs_f32 || cos_sin.scalar_type() == dt),
+              "slm qk_norm: cos_sin must be contiguous, fp32 or the activation dtype");
+  const bool append = slot_ids.defined();
+  if (append) {
+    check_i32(slot_ids, "slot_ids");
+    TORCH_CHECK(slot_ids.numel() == T, "slm qk_norm: positions and slot_ids must have one entry per token");
+    for (const torch::Tensor* c : {&key_cache, &value_cache})
+      TORCH_CHECK(c->defined() && c->is_cuda() && c->is_contiguous() && c->scalar_type() == dt && c->dim() == 3 &&
+                      c->size(1) == k.size(1) && c->size(2) == D,
+                  "slm qk_norm: caches must be contiguous [n_slots, n_kv_heads, head_dim] of the activation dtype");
+  }
+  const int32_t* sp = append ? slot_ids.const_data_ptr<int32_t>() : nullptr;
+  void* kc = append ? key_cache.data_ptr() : nullptr;
+  void* vc = append ? value_cache.data_ptr() : nullptr;
+  const int32_t H = static_cast<int32_t>(q.size(1)), KV = static_cast<int32_t>(k.size(1));
+  if (partials.defined()) {
+    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == torch::kFloat && partials.is_contiguous() &&
+                    partials.dim() == 3 && partials.size(1) == T && partials.size(2) == (H + 2 * KV) * D,
+                "slm qk_norm: partials must be contiguous fp32 [n_splits, n_tokens, (n_heads + 2 n_kv_heads) head_dim]");
+    check(slm_qk_norm_rope_kv_append_splitk(
+              partials.const_data_ptr<float>(), static_cast<int32_t>(partials.size(0)), q.data_ptr(), q.stride(0),
+              k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), q_norm_weight.data_ptr(), k_norm_weight.data_ptr(),
+              static_cast<float>(eps), positions.const_data_ptr<int32_t>(), cos_sin.data_ptr(), cs_f32 ? 1 : 0,
+              static_cast<int32_t>(cos_sin.size(-1)), interleaved ? 1 : 0, sp, kc, vc, T, H, KV,
+              static_cast<int32_t>(D), dtype_code(q), stream_of(q)),
+          "slm_qk_norm_rope_kv_append_splitk");
+    return;
+  }
+  check(slm_qk_norm_rope_kv_append(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                   q_norm_weight.data_ptr(), k_norm_weight.data_ptr(), static_cast<float>(eps),
+                                   positions.const_data_ptr<int32_t>(), cos_sin.data_ptr(), cs_f32 ? 1 : 0,
+                                   static_cast<int32_t>(cos_sin.size(-1)), interleaved ? 1 : 0, sp, kc, vc, T, H, KV,
+                                   static_cast<int32_t>(D), dtype_code(q), stream_of(q)),
+        "slm_qk_norm_rope_kv_append");
+}
+
 }  // namespace slm

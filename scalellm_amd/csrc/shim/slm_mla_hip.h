@@ -52,4 +52,23 @@ void mla_rope_append(torch::Tensor q,                    // [n_tokens, n_heads, 
                      int64_t nope_head_dim,
                      const torch::Tensor& partials = torch::Tensor());
 
+// The QK-norm prologue of the C ABI's section 19 in one launch (Qwen3): every head of q and k RMS-normalised over its
+// head_dim values with q_norm_weight / k_norm_weight, rotated over the whole head by cos_sin[positions], in place;
+// with slot_ids defined, k and v also go to their cache slot (a negative id appends nothing).  q / k / v may be
+// column slices of one GEMM output.  partials (defined): the fp32 split-K slabs [n_splits, n_tokens, N] of the fused
+// [q | k | v] GEMM; q, k and v are then outputs.
+void qk_norm_rope_kv_append(torch::Tensor q,                    // [n_tokens, n_heads, head_dim]
+                            torch::Tensor k,                    // [n_tokens, n_kv_heads, head_dim]
+                            torch::Tensor v,                    // [n_tokens, n_kv_heads, head_dim]
+                            const torch::Tensor& q_norm_weight,  // [head_dim]
+                            const torch::Tensor& k_norm_weight,  // [head_dim]
+                            double eps,
+                            const torch::Tensor& positions,      // [n_tokens] int32
+                            const torch::Tensor& cos_sin,        // [max_pos, head_dim], fp32 or the activation dtype
+                            bool interleaved,
+                            const torch::Tensor& slot_ids = torch::Tensor(),     // [n_tokens] int32 or undefined
+                            const torch::Tensor& key_cache = torch::Tensor(),    // [n_slots, n_kv_heads, head_dim]
+                            const torch::Tensor& value_cache = torch::Tensor(),  // [n_slots, n_kv_heads, head_dim]
+                            const torch::Tensor& partials = torch::Tensor());
+
 }  // namespace slm

@@ -361,6 +361,19 @@ PYBIND11_MODULE(_slm_shim, m) {
         }, py::arg("q"), py::arg("kv_a"), py::arg("norm_weight"), py::arg("eps"), py::arg("positions"),
         py::arg("cos_sin"), py::arg("interleaved"), py::arg("slot_ids"), py::arg("kv_cache"), py::arg("k_rope_cache"),
         py::arg("nope_head_dim"), py::arg("partials") = py::none());
+  m.def("qk_norm_rope_kv_append",
+        [](torch::Tensor q, torch::Tensor k, torch::Tensor v, const torch::Tensor& q_norm_weight,
+           const torch::Tensor& k_norm_weight, double eps, const torch::Tensor& positions, const torch::Tensor& cos_sin,
+           bool interleaved, const c10::optional<torch::Tensor>& slot_ids,
+           const c10::optional<torch::Tensor>& key_cache, const c10::optional<torch::Tensor>& value_cache,
+           const c10::optional<torch::Tensor>& partials) {
+          auto opt = [](const c10::optional<torch::Tensor>& t) { return t.has_value() ? *t : torch::Tensor(); };
+          slm::qk_norm_rope_kv_append(q, k, v, q_norm_weight, k_norm_weight, eps, positions, cos_sin, interleaved,
+                                      opt(slot_ids), opt(key_cache), opt(value_cache), opt(partials));
+        }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("q_norm_weight"), py::arg("k_norm_weight"),
+        py::arg("eps"), py::arg("positions"), py::arg("cos_sin"), py::arg("interleaved"),
+        py::arg("slot_ids") = py::none(), py::arg("key_cache") = py::none(), py::arg("value_cache") = py::none(),
+        py::arg("partials") = py::none());
   py::class_<slm::InputParameters>(m, "InputParameters")
       .def(py::init<>())
       .def_readwrite("num_sequences", &slm::InputParameters::num_sequences)

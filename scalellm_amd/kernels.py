@@ -1175,6 +1175,64 @@ def apply_rotary_pos_emb(query: torch.Tensor, key: torch.Tensor, positions: torc
         "slm_rope_kv_append")
 
 
+def qk_norm_rope_kv_append(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, q_norm_weight: torch.Tensor,
+                           k_norm_weight: torch.Tensor, eps: float, positions: torch.Tensor, cos_sin: torch.Tensor,
+                           interleaved: bool, slot_ids: Optional[torch.Tensor] = None,
+                           key_cache: Optional[torch.Tensor] = None, value_cache: Optional[torch.Tensor] = None,
+                           partials: Optional[DeferredPartials] = None) -> None:
+    """The QK-norm prologue in one launch (slm_hip.h section 19): every head of query [T, H, D] and key [T, KV, D]
+    RMS-normalised over its D values with q_norm_weight / k_norm_weight [D] (rms_norm's bits), then rotated by
+    cos_sin[positions] over the whole head (apply_rotary_pos_emb's bits), in place; with slot_ids the rotated key
+    and value also go to their cache slot (a negative id appends nothing).  The tensors may be column slices of one
+    fused qkv GEMM output.
+
+    partials (truthy): the fused [q | k | v] GEMM output was NOT written -- linear / fp8_linear / gptq_gemm(...,
+    defer_reduce=True) left fp32 split-K slabs behind; the kernel sums them itself (the reduce kernel's order and
+    rounding: identical bits, one launch less) and WRITES query, key and value."""
+    L = _lib.lib()
+    _require_gpu(query, key, value, q_norm_weight, k_norm_weight, positions, cos_sin, slot_ids, key_cache, value_cache)
+    for t in (query, key, value):
+        if t.dim() != 3 or t.stride(2) != 1 or t.stride(1) != t.size(2) or t.dtype != query.dtype:
+            raise SlmError("query / key / value must be [n_tokens, heads, head_dim] of one dtype, contiguous in "
+                           "their last two dims")
+    T, D = query.size(0), query.size(2)
+    if key.size(0) != T or key.size(2) != D or value.shape != key.shape:
+        raise SlmError("query / key / value token counts and head_dim must match; value like key")
+    if positions.dtype != torch.int32 or not positions.is_contiguous() or positions.numel() != T:
+        raise SlmError("positions must be contiguous int32 [n_tokens]")
+    for w in (q_norm_weight, k_norm_weight):
+        if w.dtype != query.dtype or not w.is_contiguous() or w.numel() != D:
+            raise SlmError("q_norm_weight / k_norm_weight must be contiguous [head_dim] of the activation dtype")
+    is_f32 = 1 if cos_sin.dtype == torch.float32 else 0
+    if (not is_f32 and cos_sin.dtype != query.dtype) or not cos_sin.is_contiguous():
+        raise SlmError("cos_sin must be contiguous, fp32 or the activation dtype")
+    append = slot_ids is not None
+    if append:
+        if key_cache is None or value_cache is None:
+            raise SlmError("append needs key_cache and value_cache")
+        if slot_ids.dtype != torch.int32 or not slot_ids.is_contiguous() or slot_ids.numel() != T:
+            raise SlmError("slot_ids must be contiguous int32 [n_tokens]")
+        for t in (key_cache, value_cache):
+            if not t.is_contiguous() or t.dtype != key.dtype or t.dim() != 3 or \
+                    tuple(t.shape[1:]) != tuple(key.shape[1:]):
+                raise SlmError("caches must be contiguous [n_slots, n_kv_heads, head_dim] of the activation dtype")
+    tail = (q_norm_weight.data_ptr(), k_norm_weight.data_ptr(), float(eps), positions.data_ptr(),
+            cos_sin.data_ptr(), is_f32, cos_sin.size(-1), 1 if interleaved else 0,
+            slot_ids.data_ptr() if append else None, key_cache.data_ptr() if append else None,
+            value_cache.data_ptr() if append else None, T, query.size(1), key.size(1), D, _dtype_code(query),
+            _stream())
+    if partials:
+        if not isinstance(partials, DeferredPartials):
+            raise SlmError("qk_norm_rope_kv_append(partials=...) takes the handle a deferred GEMM returned")
+        partials.check(query.device, T * (query.size(1) + 2 * key.size(1)) * D, "qk_norm_rope_kv_append(partials=...)")
+        check(L.slm_qk_norm_rope_kv_append_splitk(partials.ptr, partials.splits, query.data_ptr(), query.stride(0),
+                                                  key.data_ptr(), key.stride(0), value.data_ptr(), value.stride(0),
+                                                  *tail), "slm_qk_norm_rope_kv_append_splitk")
+        return
+    check(L.slm_qk_norm_rope_kv_append(query.data_ptr(), query.stride(0), key.data_ptr(), key.stride(0),
+                                       value.data_ptr(), value.stride(0), *tail), "slm_qk_norm_rope_kv_append")
+
+
 def silu_and_mul(out: torch.Tensor, x: torch.Tensor) -> None:
     """kernel::act_and_mul with SiLU (activation_kernels.cu:84): out = silu(x[:, :d]) * x[:, d:]."""
     L = _lib.lib()

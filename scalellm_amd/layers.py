@@ -97,7 +97,9 @@ class HipAttnHandler:
 
     def __init__(self, sm_scale: float, logits_soft_cap: float = 0.0,
                  alibi_slopes: Optional[torch.Tensor] = None, rotary_dim: int = 0,
-                 cos_sin: Optional[torch.Tensor] = None, interleaved: bool = False):
+                 cos_sin: Optional[torch.Tensor] = None, interleaved: bool = False,
+                 q_norm: Optional[torch.Tensor] = None, k_norm: Optional[torch.Tensor] = None,
+                 qk_norm_eps: Optional[float] = None):
         self.sm_scale = sm_scale
         self.logits_soft_cap = logits_soft_cap
         self.alibi_slopes = alibi_slopes
@@ -106,6 +108,15 @@ class HipAttnHandler:
         # fp32 split-K slabs of the fused qkv GEMM (kernels.DeferredPartials), consumed by the next
         # append_kv_cache(): the RoPE + append kernel then also does the split-K reduction
         self.qkv_partials = None
+        # Qwen3's per-head RMSNorm of q and k ([head_dim] weights) before RoPE: append_kv_cache() then issues
+        # kernels.qk_norm_rope_kv_append.  qk_norm_fused = False runs the composition of the older entry points
+        # instead (copies, two rms_norm, apply_rotary_pos_emb), which takes no deferred slabs
+        if (q_norm is None) != (k_norm is None) or (q_norm is not None and qk_norm_eps is None):
+            raise kernels.SlmError("q_norm and k_norm come together, with qk_norm_eps")
+        if q_norm is not None and cos_sin is None:
+            raise kernels.SlmError("the QK-norm prologue needs RoPE (cos_sin)")
+        self.q_norm, self.k_norm, self.qk_norm_eps = q_norm, k_norm, qk_norm_eps
+        self.qk_norm_fused = True
 
     @staticmethod
     def build_cos_sin(rotary_dim: int, max_position: int, inv_freq: torch.Tensor) -> torch.Tensor:
@@ -123,6 +134,26 @@ class HipAttnHandler:
     def append_kv_cache(self, kv_cache: KVCache, query, key, value, input_params: InputParameters):
         kc, vc = kv_cache.get_kv_cache()
         partials, self.qkv_partials = self.qkv_partials, None
+        if self.q_norm is not None:
+            if self._pending is None:
+                raise kernels.SlmError("the QK-norm prologue needs positions")
+            positions, self._pending = self._pending, None
+            if self.qk_norm_fused:
+                kernels.qk_norm_rope_kv_append(query, key, value, self.q_norm, self.k_norm, self.qk_norm_eps,
+                                               positions, self.cos_sin, self.interleaved,
+                                               slot_ids=input_params.new_cache_slots, key_cache=kc, value_cache=vc,
+                                               partials=partials)
+                return
+            if partials:
+                raise kernels.SlmError("the unfused QK-norm composition takes no deferred qkv partials")
+            for x, w in ((query, self.q_norm), (key, self.k_norm)):
+                rows = x.reshape(-1, x.size(-1)).contiguous()  # a copy: x is a column slice of the qkv row
+                kernels.rms_norm(rows, rows, w, self.qk_norm_eps)
+                x.copy_(rows.view_as(x))
+            kernels.apply_rotary_pos_emb(query, key, positions, self.cos_sin, self.rotary_dim, self.interleaved,
+                                         value=value, slot_ids=input_params.new_cache_slots, key_cache=kc,
+                                         value_cache=vc)
+            return
         if self._pending is not None:
             kernels.apply_rotary_pos_emb(query, key, self._pending, self.cos_sin, self.rotary_dim,
                                          self.interleaved, value=value,
