@@ -1,5 +1,6 @@
 """A Gemma-2-shaped decode step on the fused path, beside decode.LlamaDecodeStep and on its contract: seeded synthetic
-int4 checkpoint (keep_checkpoint), static buffers, forward(tokens, positions, params, return_logits, sampling),
+checkpoint (keep_checkpoint; int4 with quant_method "awq" / "gptq", f16 / bf16 with "none", which load_state_dict
+replaces by a HuggingFace one), static buffers, forward(tokens, positions, params, return_logits, sampling),
 capturable with torch.cuda.graph on one stream and one lane.  It drives the hot path the way the reference's
 Gemma2ModelImpl::forward does (src/models/google/gemma2.h:186-204, 221-276, 298-343):
 
@@ -26,8 +27,8 @@ import torch
 
 from . import kernels
 from .decode import _rand_int4_linear
-from .layers import (Attention, ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache, QuantArgs,
-                     RowParallelQLinear)
+from .layers import (Attention, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache,
+                     QuantArgs, RowParallelLinear, RowParallelQLinear)
 from .model_parallel import ParallelArgs
 
 
@@ -47,6 +48,23 @@ class Gemma2Shape:
     sliding_window: int = 4096              # even layers; odd layers attend globally (gemma2.h:249-251)
     attn_logit_soft_cap: float = 50.0
     final_logit_soft_cap: float = 30.0
+
+    @staticmethod
+    def from_hf_config(cfg) -> "Gemma2Shape":
+        """The shape of a HuggingFace Gemma2Config (the object, or the dict of its config.json).  HuggingFace's
+        sliding_window counts the keys a query sees, itself included; the field here is the attention kernel's
+        and counts the keys BEHIND the query (layers.Attention), so it is one less."""
+        get = cfg.get if isinstance(cfg, dict) else lambda k, d=None: getattr(cfg, k, d)  # noqa: E731
+        window = get("sliding_window")
+        return Gemma2Shape(
+            hidden=get("hidden_size"), n_heads=get("num_attention_heads"), n_kv_heads=get("num_key_value_heads"),
+            head_dim=get("head_dim"), intermediate=get("intermediate_size"), n_layers=get("num_hidden_layers"),
+            vocab=get("vocab_size"), rope_theta=float(get("rope_theta", 10000.0)),
+            rms_eps=float(get("rms_norm_eps", 1e-6)), max_position=get("max_position_embeddings", 8192),
+            attn_scalar=float(get("query_pre_attn_scalar")),
+            sliding_window=int(window) - 1 if window and window > 0 else -1,
+            attn_logit_soft_cap=float(get("attn_logit_softcapping") or 0.0),
+            final_logit_soft_cap=float(get("final_logit_softcapping") or 0.0))
 
     # the public HuggingFace configs (google/gemma-2-{2b,9b,27b}/config.json)
     @staticmethod
@@ -83,7 +101,11 @@ class Gemma2DecodeStep:
         self._sample_bufs = None
         D, H, inter = shape.head_dim, shape.hidden, shape.intermediate
         gen = torch.Generator(device=self.device).manual_seed(seed * 1000 + 29)
-        qa = QuantArgs(quant_method=quant_method, bits=4, group_size=group_size, zero_point=(quant_method == "awq"))
+        # quant_method "none": an f16 / bf16 checkpoint ([out, in] weights, streamed as they are by the dense GEMM)
+        self.quant_method = quant_method
+        dense = quant_method == "none"
+        qa = None if dense else \
+            QuantArgs(quant_method=quant_method, bits=4, group_size=group_size, zero_point=(quant_method == "awq"))
         inv_freq = 1.0 / (shape.rope_theta ** (torch.arange(0, D, 2, dtype=torch.float32, device=self.device) / D))
         cos_sin = HipAttnHandler.build_cos_sin(D, shape.max_position, inv_freq)
         # ONE handler (scale, cap, rotary table) shared by every layer; the window is the layer's
@@ -95,13 +117,20 @@ class Gemma2DecodeStep:
         for li in range(shape.n_layers):
             L = {"attn": Attention(shape.n_heads, shape.n_kv_heads, D, handler,
                                    sliding_window=shape.sliding_window if li % 2 == 0 else -1)}
-            L["qkv"] = ColumnParallelQLinear(H, nq + 2 * nkv, False, qa, False, pa, dtype, self.device)
-            L["o"] = RowParallelQLinear(nq, H, False, qa, True, pa, dtype, self.device)
-            L["gate_up"] = ColumnParallelQLinear(H, 2 * inter, False, qa, False, pa, dtype, self.device, act_mul=None)
-            L["down"] = RowParallelQLinear(inter, H, False, qa, True, pa, dtype, self.device)
             ck = {}
             for name, (K, N) in (("qkv", (H, nq + 2 * nkv)), ("o", (nq, H)), ("gate_up", (H, 2 * inter)),
                                  ("down", (inter, H))):
+                col = name in ("qkv", "gate_up")
+                if dense:
+                    L[name] = ColumnParallelLinear(K, N, False, False, pa, dtype, self.device) if col else \
+                        RowParallelLinear(K, N, False, True, pa, dtype, self.device)
+                    # unit-variance outputs for unit-variance inputs: the scores reach the soft cap's curved part
+                    ck[name] = {"weight": (torch.randn(N, K, device=self.device, generator=gen) * K ** -0.5).to(dtype)}
+                    L[name].load_shard(ck[name]["weight"])
+                    L[name].verify_loaded_weights()
+                    continue
+                L[name] = ColumnParallelQLinear(K, N, False, qa, False, pa, dtype, self.device) if col else \
+                    RowParallelQLinear(K, N, False, qa, True, pa, dtype, self.device)
                 ck[name] = _rand_int4_linear(gen, K, N, group_size, quant_method, dtype, self.device)
                 L[name].load_state_dict(ck[name])
                 L[name].verify_loaded_weights()
@@ -120,6 +149,26 @@ class Gemma2DecodeStep:
         e = lambda *s: torch.empty(*s, dtype=dtype, device=self.device)  # noqa: E731
         self.buf = dict(resid=e(T, H), normed=e(T, H), qkv=e(T, nq + 2 * nkv), attn=e(T, shape.n_heads, D),
                         o=e(T, H), gate_up=e(T, 2 * inter), act=e(T, inter), down=e(T, H))
+
+    def load_state_dict(self, sd) -> None:
+        """Replace the synthetic checkpoint by the tensors of a HuggingFace Gemma2ForCausalLM state dict
+        (quant_method "none"): q | k | v and gate | up are merged row-wise, as the fused GEMMs read them; the norm
+        weights stay the checkpoint's w of (1 + w); the lm_head is the embedding."""
+        if self.quant_method != "none":
+            raise ValueError("load_state_dict takes an unquantised checkpoint: build the step with quant_method='none'")
+        t = lambda name: sd[name].to(device=self.device, dtype=self.dtype)  # noqa: E731
+        for li, L in enumerate(self.layers):
+            p = f"model.layers.{li}."
+            merged = {"qkv": ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "o": ("self_attn.o_proj",),
+                      "gate_up": ("mlp.gate_proj", "mlp.up_proj"), "down": ("mlp.down_proj",)}
+            for name, parts in merged.items():
+                L[name].weight.copy_(torch.cat([t(p + part + ".weight") for part in parts], dim=0))
+            for name, hf in (("in_norm", "input_layernorm"), ("post_attn_norm", "post_attention_layernorm"),
+                             ("pre_ffn_norm", "pre_feedforward_layernorm"),
+                             ("post_ffn_norm", "post_feedforward_layernorm")):
+                L[name].copy_(t(p + hf + ".weight"))
+        self.final_norm.copy_(t("model.norm.weight"))
+        self.embed.copy_(t("model.embed_tokens.weight"))
 
     def reserve_workspaces(self, n_tokens: int, max_kv_len: int) -> None:
         """Grow the kernel workspaces once, before graph capture."""

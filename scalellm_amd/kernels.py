@@ -297,6 +297,60 @@ def paged_kv_varlen_mha(
     check(L.slm_paged_kv_varlen_mha(C.byref(a), _stream()), "slm_paged_kv_varlen_mha")
 
 
+def visible_kv_hint(max_kv_len: int, max_q_len: int, sliding_window: int) -> int:
+    """The max_kv_len HINT of a call whose rows all look through a sliding window (paged_kv_varlen_mha's count: the
+    keys behind the query; < 0 = none): a pure-decode row streams at most sliding_window + 1 keys however long its
+    sequence is, and the plan sizes the KV splits (>= 64 rows a share) from the hint -- given the context length
+    instead, a 32 k context cuts a 4 k window into 128 shares where 32 fill the chip (26 vs 19 us at batch 1).
+    Like every value of the hint it only shapes the launch."""
+    if sliding_window < 0 or max_q_len > 1:
+        return int(max_kv_len)
+    return min(int(max_kv_len), int(sliding_window) + 1)
+
+
+_decode_q_cu = {}  # (device key, batch) -> arange(batch + 1) int32: the q_cu_lens of a pure-decode call
+
+
+def paged_decode_attention(
+    out: torch.Tensor,            # [batch, n_heads, head_dim]
+    query: torch.Tensor,          # [batch, n_heads, head_dim]: ONE query token per sequence, its last
+    key_cache: torch.Tensor,      # [n_slots, n_kv_heads, head_dim]
+    value_cache: torch.Tensor,    # [n_slots, n_kv_heads, head_dim]
+    kv_cu_lens: torch.Tensor,     # [batch + 1] int32, the query token's own key included
+    block_table: torch.Tensor,    # flattened first-slot ids, int32
+    block_cu_lens: torch.Tensor,  # [batch + 1] int32
+    block_size: int,
+    max_kv_len: int,
+    sm_scale: Optional[float] = None,   # None: head_dim ** -0.5 (Gemma-2: query_pre_attn_scalar ** -0.5)
+    logit_softcap: float = 0.0,         # 0 = off; s = cap * tanh(s / cap) on every scaled score, before the mask
+    sliding_window: int = 0,            # <= 0 = off; the token at position L - 1 sees the keys p > L - 1 - window
+    num_splits: int = 0,
+) -> None:
+    """Decode attention in the vocabulary of the model configurations (HuggingFace attn_logit_softcapping,
+    sliding_window, query_pre_attn_scalar) over paged_kv_varlen_mha's kernels: the soft cap is the kernel's
+    compiled-in score transform, the window narrows every workgroup's KV range on the device (pages in front of
+    it are never read), and a KV split that falls outside it leaves an l = 0 partial the combine pass ignores.
+
+    `sliding_window` counts the keys a query sees, ITSELF INCLUDED, as the HuggingFace configurations do;
+    paged_kv_varlen_mha's counts the keys behind it, as the reference's handler does: window W here is W - 1
+    there.  With both options off this IS paged_kv_varlen_mha(..., max_q_len=1, sm_scale): the same launch."""
+    if query.dim() != 3 or kv_cu_lens.numel() != query.size(0) + 1:
+        raise SlmError("paged_decode_attention takes one query token per sequence: query [batch, n_heads, "
+                       "head_dim], kv_cu_lens [batch + 1]")
+    if logit_softcap < 0:
+        raise SlmError("logit_softcap must be >= 0 (0 = off)")
+    n = query.size(0)
+    key = (_dev_key(query.device), n)
+    q_cu = _decode_q_cu.get(key)
+    if q_cu is None:
+        q_cu = _decode_q_cu[key] = torch.arange(n + 1, dtype=torch.int32, device=query.device)
+    behind = int(sliding_window) - 1 if sliding_window > 0 else -1
+    paged_kv_varlen_mha(out, query, key_cache, value_cache, q_cu, kv_cu_lens, block_table, block_cu_lens, None,
+                        block_size, 1, visible_kv_hint(max_kv_len, 1, behind),
+                        query.size(2) ** -0.5 if sm_scale is None else sm_scale,
+                        logits_soft_cap=float(logit_softcap), sliding_window=behind, num_splits=num_splits)
+
+
 def paged_kv_varlen_mha_auto_splits(query, key_cache, q_cu_lens, block_size, max_q_len,
                                     max_kv_len) -> int:
     """Split-KV count the library's heuristic picks for these sizes (host-side only)."""

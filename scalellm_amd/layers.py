@@ -179,7 +179,8 @@ class HipAttnHandler:
                                     input_params.kv_cu_seq_lens, input_params.block_tables,
                                     input_params.cu_block_lens, self.alibi_slopes,
                                     kv_cache.block_size(), input_params.q_max_seq_len,
-                                    input_params.kv_max_seq_len, self.sm_scale,
+                                    kernels.visible_kv_hint(input_params.kv_max_seq_len, input_params.q_max_seq_len,
+                                                            sliding_window), self.sm_scale,
                                     self.logits_soft_cap, sliding_window,
                                     total_kv_len=total, phase=phase)
 

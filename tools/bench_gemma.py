@@ -1,6 +1,7 @@
 """The Gemma kernels (csrc/gemma.hip) and the Gemma-2 step against their own compositions.
 
-    python tools/bench_gemma.py [--out profiles/r13_gemma2.jsonl] [--iters 200] [--rows sandwich,soft_cap,step]
+    python tools/bench_gemma.py [--out profiles/r13_gemma2.jsonl] [--iters 200]
+                                [--rows sandwich,soft_cap,step,attn_window]
 
 Every time is a replay period, not a kernel time: the work captured in a hipGraph and replayed `iters` times between
 device events, after a warm-up of the same replays; the MEDIAN of `windows` such windows is reported, with the
@@ -20,6 +21,10 @@ smallest and largest beside it (spread).  One JSON line per row:
              greedy argmax included.  The same step with half the layers gives ms_per_layer (the difference over
              the layers dropped), embed_head_argmax_ms (what is left) and ms_42_layers_extrapolated -- an
              extrapolation, not a measurement.
+  attn_window  kernels.paged_decode_attention of Gemma-2-9B's attention (16 query heads on 8 KV heads x 256, soft cap
+             50, bf16, block 16) with sliding_window 4096 at context 4096 and at context 32768, batch 1 / 8 / 32:
+             the pages in front of the window are not read, so the two should take about the same time
+             (ratio_32k_over_4k); full_32k_us is the same call without the window, which reads all of them.
 """
 import argparse
 import json
@@ -152,6 +157,32 @@ def bench_step(args, dev):
                    ms_42_layers_extrapolated=round((full[0] + (42 - args.layers) * per_layer) / 1e3, 3)), args.out)
 
 
+def bench_attn_window(args, dev):
+    from scalellm_amd.decode import make_decode_inputs
+    H, HKV, D, block, window, cap = 16, 8, 256, 16, 4096, 50.0
+    for bs in (1, 8, 32):
+        us = {}
+        for ctx, win in ((4096, window), (32768, window), (32768, 0)):
+            _, _, p, n_blocks = make_decode_inputs(bs, ctx, block, dev, seed=2)
+            q = torch.randn(bs, H, D, device=dev).to(torch.bfloat16)
+            kc = torch.randn(n_blocks * block, HKV, D, device=dev).to(torch.bfloat16)
+            vc = torch.randn(n_blocks * block, HKV, D, device=dev).to(torch.bfloat16)
+            out = torch.empty_like(q)
+            us[(ctx, win)] = _graph_us(lambda: kernels.paged_decode_attention(
+                out, q, kc, vc, p.kv_cu_seq_lens, p.block_tables, p.cu_block_lens, block, ctx, logit_softcap=cap,
+                sliding_window=win), args.iters, args.windows)
+            del kc, vc
+            torch.cuda.empty_cache()
+        w4k, w32k, full = us[(4096, window)], us[(32768, window)], us[(32768, 0)]
+        nbytes = 2 * bs * window * HKV * D * 2
+        _emit(dict(row="attn_window", heads=[H, HKV, D], bs=bs, window=window, cap=cap, block=block, iters=args.iters,
+                   windows=args.windows, ctx_4k_us=round(w4k[0], 2),
+                   ctx_4k_us_min_max=[round(w4k[1], 2), round(w4k[2], 2)],
+                   ctx_32k_us=round(w32k[0], 2), ctx_32k_us_min_max=[round(w32k[1], 2), round(w32k[2], 2)],
+                   ratio_32k_over_4k=round(w32k[0] / w4k[0], 3), full_32k_us=round(full[0], 2),
+                   window_bytes=nbytes, ctx_32k_tbs=round(nbytes / w32k[0] * 1e-6, 3)), args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
@@ -173,6 +204,8 @@ def main():
         bench_soft_cap(args, dev)
     if "step" in rows:
         bench_step(args, dev)
+    if "attn_window" in rows:
+        bench_attn_window(args, dev)
 
 
 if __name__ == "__main__":
