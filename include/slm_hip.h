@@ -1570,6 +1570,78 @@ SLM_API int slm_qk_norm_rope_kv_append_splitk(const float* partials /* [n_splits
                                               void* value_cache, int64_t n_tokens, int32_t n_heads,
                                               int32_t n_kv_heads, int32_t head_dim, int32_t dtype, void* stream);
 
+/* ========================================================================== */
+/* 20. MXFP4 weight-only linear: W4A16 over OCP MX checkpoints                */
+/*    Section 13's linear over weights in OCP Microscaling FP4: e2m1 elements */
+/*    (1 sign, 2 exponent, 1 mantissa bit: 0, .5, 1, 1.5, 2, 3, 4, 6 and      */
+/*    their negatives; no infinity, no NaN) with ONE e8m0 scale byte e per 32 */
+/*    consecutive k, value 2^(e - 127).  The checkpoint tensors are read as   */
+/*    they are (Quark `weight` / `weight_scale`, gpt-oss `*_blocks` /         */
+/*    `*_scales`): no prepack, no group-size variants, no act-order.          */
+/*      w[n, k]   = T( e2m1(W[n, k]) * 2^(e[n, k / 32] - 127) )               */
+/*      C[m, n]   = T( sum_k A[m, k] * w[n, k] + bias[n] )    ONE rounding    */
+/*    The block scale is applied by the hardware converter                    */
+/*    (v_cvt_scalef32_pk_{bf16,f16}_fp4), never to the accumulator: it varies */
+/*    along K.  e2m1 has one mantissa bit, so w[n, k] is EXACT wherever it is */
+/*    zero or a normal number of T: bf16 for e in [2, 252], f16 for e in      */
+/*    [114, 140] (0.5 * 2^-13 is f16's smallest normal, 6 * 2^13 is finite).  */
+/*    There the MFMA sees exactly T(dequantised W) and, under the same plan,  */
+/*    the call is slm_linear on that tensor bit for bit: fp32 accumulation in */
+/*    section 13's order, the same slabs, the same epilogue.                  */
+/*    Outside that range, as observed on an MI355X through this entry (one    */
+/*    code per row, one-hot A) and pinned by tests/test_mxfp4_exact_gpu.py:   */
+/*      * below it the converter rounds the exact product to nearest even     */
+/*        into T's subnormals and keeps them (no flush): bf16 at e = 0 / 1    */
+/*        still gives every product exactly (0.5 * 2^-127 = 2^-128 is a bf16  */
+/*        subnormal); f16 at e = 100 gives 2^-24 for code 6.0 and 0 for the   */
+/*        rest (round to nearest even of 6 * 2^-27), 0 for everything at      */
+/*        e <= 2, exact subnormals at e = 112 / 113.  e = 0 is 2^-127: the    */
+/*        converter reads the scale's exponent field, not the value +0.0.     */
+/*      * above it a product beyond T's largest finite number is +-inf (bf16: */
+/*        4 and 6 at e = 253, 2 .. 6 at e = 254; f16: 4 and 6 at e = 141,     */
+/*        every non-zero code from e = 144 up), the other codes of the block  */
+/*        stay exact and the zero codes stay 0.  An inf weight poisons its    */
+/*        output column (inf * 0 = NaN in the MFMA).                          */
+/*      * e = 255, the MX NaN, gives NaN for EVERY code, zero included, in    */
+/*        both dtypes, and poisons the column like a NaN weight of section    */
+/*        13.  Checkpoints hold none of these; padding may (and is not read). */
+/*    W is [N, K/2] BYTES, a byte's LOW nibble is the lower k; row stride ldw */
+/*    in bytes, ldw >= K/2, ldw % 16 == 0, base 16-byte aligned.  w_scale is  */
+/*    [N, K/32] e8m0 bytes, REQUIRED (NULL is SLM_ERR_INVALID_ARG), row       */
+/*    stride lds in bytes, lds >= K/32, no alignment of base or stride        */
+/*    (K/32 is 21 at K = 672).  A, bias, C are T (f16 / bf16), lda / ldc as   */
+/*    in section 13.  Shapes (K % 32 == 0, N % 32 == 0), error codes, "all    */
+/*    validation before any launch", M == 0 (SLM_OK without a launch), the    */
+/*    launch shape, the K slices, the workspace ([split_k][M][N] fp32 slabs,  */
+/*    so the reduce launch and every deferred consumer of section 13 work     */
+/*    unchanged) and the flags (SLM_LINEAR_*, the same bits) are section      */
+/*    13's.  The plan is the dense plan of (M, N, K, dtype, flags, bias).     */
+/*    There is no _workspace_bytes query: the size is                         */
+/*    slm_linear_plan_info.workspace_bytes of slm_mxfp4_linear_plan.          */
+/*    Knobs: SLM_LINEAR_SPLITK / _RT / _NW force the form of this entry too   */
+/*    (csrc/dense.hip, csrc/mxfp4_cvt.h).                                     */
+/* ========================================================================== */
+typedef struct slm_mxfp4_linear_args {
+  const void* a;        /* [M, K] T, row stride lda                           */
+  const void* w;        /* [N, K/2] bytes of two e2m1 codes, row stride ldw (bytes) */
+  const void* bias;     /* [N] T or NULL                                      */
+  void* c;              /* [M, N] T ([M, N/2] with SLM_LINEAR_SILU_MUL), row stride ldc */
+  int64_t M, K, N;
+  int64_t lda, ldw, ldc;
+  int32_t dtype;        /* of a, bias and c                                   */
+  int32_t flags;        /* SLM_LINEAR_* bits, 0 = none                        */
+  void* workspace;      /* split-K slabs                                      */
+  size_t workspace_bytes;
+  const uint8_t* w_scale; /* [N, K/32] e8m0 bytes, required; everything above is slm_linear_args, field for field */
+  int64_t lds;          /* row stride of w_scale in bytes, >= K/32            */
+} slm_mxfp4_linear_args;
+
+/* As slm_linear_plan / _deferred_splits / slm_linear (section 13) for the MXFP4 entry; the plan is a pure host
+ * function and works without a GPU. */
+SLM_API int slm_mxfp4_linear_plan(const slm_mxfp4_linear_args* a, slm_linear_plan_info* out);
+SLM_API int32_t slm_mxfp4_linear_deferred_splits(const slm_mxfp4_linear_args* a);
+SLM_API int slm_mxfp4_linear(const slm_mxfp4_linear_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

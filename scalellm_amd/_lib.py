@@ -247,6 +247,12 @@ class Fp8LinearArgs(C.Structure):
     _fields_ = LinearArgs._fields_ + [("w_scale", C.c_void_p)]
 
 
+class Mxfp4LinearArgs(C.Structure):
+    """struct slm_mxfp4_linear_args (include/slm_hip.h section 20): slm_linear_args, field for field, plus the e8m0
+    block scales and their row stride."""
+    _fields_ = LinearArgs._fields_ + [("w_scale", C.c_void_p), ("lds", C.c_int64)]
+
+
 class LinearPlanInfo(C.Structure):
     """struct slm_linear_plan_info (include/slm_hip.h section 13)."""
     _fields_ = [
@@ -425,6 +431,9 @@ def lib() -> C.CDLL:
         ("slm_fp8_linear_deferred_splits", C.c_int32, [C.POINTER(Fp8LinearArgs)]),
         ("slm_fp8_linear_plan", C.c_int, [C.POINTER(Fp8LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_fp8_gemm", C.c_int, [C.POINTER(MoeFp8GemmArgs), C.c_void_p]),
+        ("slm_mxfp4_linear", C.c_int, [C.POINTER(Mxfp4LinearArgs), C.c_void_p]),
+        ("slm_mxfp4_linear_deferred_splits", C.c_int32, [C.POINTER(Mxfp4LinearArgs)]),
+        ("slm_mxfp4_linear_plan", C.c_int, [C.POINTER(Mxfp4LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

@@ -1,6 +1,6 @@
-// dense_plan.h -- the launch plan of dense.hip's two entries (slm_linear, slm_fp8_linear; include/slm_hip.h sections
-// 13 and 15), over either argument struct: slm_fp8_linear_args is slm_linear_args, field for field, plus w_scale.
-// Host only.
+// dense_plan.h -- the launch plan of dense.hip's three entries (slm_linear, slm_fp8_linear, slm_mxfp4_linear;
+// include/slm_hip.h sections 13, 15 and 20), over any of the argument structs: slm_fp8_linear_args and
+// slm_mxfp4_linear_args are slm_linear_args, field for field, plus their scales.  Host only.
 #pragma once
 #include "common.h"
 #include "tuning.h"

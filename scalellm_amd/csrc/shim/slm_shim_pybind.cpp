@@ -13,6 +13,7 @@
 #include "slm_moe_hip.h"
 #include "slm_permute_hip.h"
 #include "slm_fp8_linear_hip.h"
+#include "slm_mxfp4_linear_hip.h"
 #include "slm_linear_hip.h"
 #include "slm_qlinear_hip.h"
 #include "slm_rejection_sampler_hip.h"
@@ -193,6 +194,32 @@ PYBIND11_MODULE(_slm_shim, m) {
         [](const torch::Tensor& input, const torch::Tensor& weight, const std::optional<torch::Tensor>& w_scale,
            const std::optional<torch::Tensor>& bias, bool silu_mul) {
           return slm::fp8_linear(input, weight, w_scale.value_or(torch::Tensor()), bias, silu_mul);
+        },
+        py::arg("input"), py::arg("weight"), py::arg("w_scale"), py::arg("bias") = py::none(),
+        py::arg("silu_mul") = false);
+  // the MXFP4 weight-only layers: `weight` uint8 [N, K/2] + `weight_scale` uint8 [N, K/32]
+  m.def("create_column_parallel_mxfp4_linear",
+        [](int64_t in_features, int64_t out_features, bool bias, bool gather_output, int rank, int world_size,
+           torch::ScalarType dtype, int device_index, bool act_mul_silu) {
+          auto l = slm::create_column_parallel_mxfp4_linear(
+              in_features, out_features, bias, gather_output, slm::ParallelArgs(rank, world_size, nullptr),
+              torch::dtype(dtype).device(torch::Device(torch::kCUDA, device_index)));
+          if (act_mul_silu) l->set_act_mul_silu();
+          return std::static_pointer_cast<slm::ParallelLinearImpl>(l);
+        },
+        py::arg("in_features"), py::arg("out_features"), py::arg("bias"), py::arg("gather_output"), py::arg("rank"),
+        py::arg("world_size"), py::arg("dtype"), py::arg("device_index"), py::arg("act_mul_silu") = false);
+  m.def("create_row_parallel_mxfp4_linear",
+        [](int64_t in_features, int64_t out_features, bool bias, bool input_is_parallelized, int rank, int world_size,
+           torch::ScalarType dtype, int device_index) {
+          return std::static_pointer_cast<slm::ParallelLinearImpl>(slm::create_row_parallel_mxfp4_linear(
+              in_features, out_features, bias, input_is_parallelized, slm::ParallelArgs(rank, world_size, nullptr),
+              torch::dtype(dtype).device(torch::Device(torch::kCUDA, device_index))));
+        });
+  m.def("mxfp4_linear",
+        [](const torch::Tensor& input, const torch::Tensor& weight, const torch::Tensor& w_scale,
+           const std::optional<torch::Tensor>& bias, bool silu_mul) {
+          return slm::mxfp4_linear(input, weight, w_scale, bias, silu_mul);
         },
         py::arg("input"), py::arg("weight"), py::arg("w_scale"), py::arg("bias") = py::none(),
         py::arg("silu_mul") = false);

@@ -780,6 +780,45 @@ torch::Tensor fp8_linear(const torch::Tensor& input, const torch::Tensor& weight
   return c;
 }
 
+torch::Tensor mxfp4_linear(const torch::Tensor& input, const torch::Tensor& weight, const torch::Tensor& w_scale,
+                           const std::optional<torch::Tensor>& bias, bool silu_mul) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  const auto a = input.reshape({-1, input.size(-1)});
+  TORCH_CHECK(weight.dim() == 2 && weight.stride(1) == 1 && a.size(1) == 2 * weight.size(1) && a.stride(1) == 1 &&
+              weight.scalar_type() == torch::kUInt8,
+              "slm::mxfp4_linear: input [.., K] and a uint8 weight [N, K/2] of two e2m1 codes per byte");
+  const int64_t N = weight.size(0), K = a.size(1);
+  TORCH_CHECK(w_scale.defined() && w_scale.dim() == 2 && w_scale.stride(1) == 1 && w_scale.size(0) == N &&
+              K % 32 == 0 && w_scale.size(1) == K / 32 && w_scale.scalar_type() == torch::kUInt8,
+              "slm::mxfp4_linear: w_scale must be the uint8 e8m0 bytes [N, K/32]");
+  torch::Tensor c = torch::empty({a.size(0), silu_mul ? N / 2 : N}, a.options());
+  slm_mxfp4_linear_args g{};
+  g.a = a.const_data_ptr();
+  g.w = weight.const_data_ptr();
+  g.w_scale = w_scale.const_data_ptr<uint8_t>();
+  g.lds = w_scale.stride(0);
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->numel() == N && bias->is_contiguous() && bias->scalar_type() == a.scalar_type());
+    g.bias = bias->const_data_ptr();
+  }
+  g.c = c.mutable_data_ptr();
+  g.M = a.size(0); g.K = K; g.N = N;
+  g.lda = a.stride(0); g.ldw = weight.stride(0); g.ldc = c.stride(0);
+  g.dtype = dtype_code(a);
+  g.flags = silu_mul ? SLM_LINEAR_SILU_MUL : 0;
+  if (g.M == 0) return c;
+  slm_linear_plan_info info{};  // section 20 has no _workspace_bytes query: the plan carries the size
+  check(slm_mxfp4_linear_plan(&g, &info), "slm_mxfp4_linear_plan");
+  torch::Tensor ws;
+  if (info.workspace_bytes > 0) {
+    ws = workspace_for(a, info.workspace_bytes);
+    g.workspace = ws.mutable_data_ptr();
+    g.workspace_bytes = ws.nbytes();
+  }
+  check(slm_mxfp4_linear(&g, current_stream(a)), "slm_mxfp4_linear");
+  return c;
+}
+
 torch::Tensor W4Linear::forward(const torch::Tensor& input, const std::optional<torch::Tensor>& bias,
                                 std::optional<torch::Tensor> out) const {
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());

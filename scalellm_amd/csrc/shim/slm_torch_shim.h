@@ -221,6 +221,12 @@ torch::Tensor linear(const torch::Tensor& input, const torch::Tensor& weight, co
 torch::Tensor fp8_linear(const torch::Tensor& input, const torch::Tensor& weight, const torch::Tensor& w_scale,
                          const std::optional<torch::Tensor>& bias, bool silu_mul = false);
 
+// W4A16 on OCP MXFP4 weights (include/slm_hip.h section 20, slm_mxfp4_linear): weight uint8 [N, K/2] (two e2m1 codes
+// per byte, the low nibble the lower k) and w_scale uint8 [N, K/32] (e8m0), both streamed as they are; the rest as
+// linear().
+torch::Tensor mxfp4_linear(const torch::Tensor& input, const torch::Tensor& weight, const torch::Tensor& w_scale,
+                           const std::optional<torch::Tensor>& bias, bool silu_mul = false);
+
 // The reference's abstract process group, same five virtuals with the same meaning
 // (src/model_parallel/process_group.h:10-60): whatever drives llm::ProcessGroup* -- the parallel
 // layers, Worker::process_group_test -- drives this.

@@ -8,7 +8,8 @@ lm_head (column-parallel, gathered) and greedy argmax.  All four linears are int
 layer is int4 -- or, with quant_method="none", all four are unquantised f16 / bf16 weights in
 checkpoint layout (layers.ColumnParallelLinear / RowParallelLinear over slm_linear), or, with
 quant_method="fp8", those weights quantised per output channel to e4m3 (layers.ColumnParallelFp8Linear /
-RowParallelFp8Linear over slm_fp8_linear: W8A16).  Weights are
+RowParallelFp8Linear over slm_fp8_linear: W8A16), or, with quant_method="mxfp4", quantised to OCP MXFP4
+(layers.ColumnParallelMxfp4Linear / RowParallelMxfp4Linear over slm_mxfp4_linear: W4A16).  Weights are
 synthetic (seeded); there is no checkpoint IO on this path.
 
 One process per GPU; TP shards heads (attention needs no collective) and the GEMMs' N / K.
@@ -26,8 +27,9 @@ from typing import List, Optional
 import torch
 
 from . import kernels
-from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler,
-                     InputParameters, KVCache, uniform_kv_hint, QuantArgs, RowParallelFp8Linear, RowParallelLinear,
+from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelMxfp4Linear,
+                     ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache, uniform_kv_hint, QuantArgs,
+                     RowParallelFp8Linear, RowParallelLinear, RowParallelMxfp4Linear,
                      RowParallelQLinear)
 from .model_parallel import ParallelArgs
 
@@ -118,9 +120,9 @@ def _shard_rows(ck, fmt, k0, k1, group_size, bits=4):
 
 def lane_query(shape: "LlamaShape", n_heads: int, n_kv_heads: int, world_size: int, lanes_min: int,
                n_tokens: int, n_seqs: int, q_max_seq_len: int, kv_max_seq_len: int, tp_lanes_ok: bool = False,
-               weight_bits: int = 4):
+               weight_bits: float = 4):
     """slm_lane_query for a step of this shape (n_heads / n_kv_heads: per rank; weight_bits: 4 for the int4
-    linears, 16 for a dense step)."""
+    linears, 16 for a dense step, 8 for fp8, 4.25 for MXFP4: a nibble plus 1/32 of a scale byte)."""
     from ._lib import LaneQuery
     q = LaneQuery()
     q.n_tokens, q.n_seqs, q.q_max_seq_len, q.kv_max_seq_len = int(n_tokens), int(n_seqs), int(q_max_seq_len), \
@@ -128,9 +130,9 @@ def lane_query(shape: "LlamaShape", n_heads: int, n_kv_heads: int, world_size: i
     q.world_size, q.tp_lanes_ok, q.lanes_min = int(world_size), int(bool(tp_lanes_ok)), int(lanes_min)
     q.n_heads, q.n_kv_heads, q.head_dim = int(n_heads), int(n_kv_heads), int(shape.head_dim)
     # weight bytes of one decoder layer on this rank (packed int4, or 2 bytes per dense weight): qkv + o + gate_up + down
-    q.layer_weight_bytes = (shape.hidden * (n_heads + 2 * n_kv_heads) * shape.head_dim +
-                            n_heads * shape.head_dim * shape.hidden +
-                            3 * shape.hidden * shape.intermediate // world_size) * weight_bits // 8
+    q.layer_weight_bytes = int((shape.hidden * (n_heads + 2 * n_kv_heads) * shape.head_dim +
+                                n_heads * shape.head_dim * shape.hidden +
+                                3 * shape.hidden * shape.intermediate // world_size) * weight_bits) // 8
     q.kv_elem_bytes = 2
     return q
 
@@ -179,9 +181,11 @@ class LlamaDecodeStep:
         # linears are layers.{Column,Row}ParallelLinear over slm_linear; everything else of the step is shared
         # quant_method "fp8": that same checkpoint quantised per output channel to e4m3 (kernels.quantize_fp8_weight),
         # the four linears are layers.{Column,Row}ParallelFp8Linear over slm_fp8_linear; the rest is the dense path
-        self.fp8 = quant_method == "fp8"
-        dense = quant_method in ("none", "fp8")
-        self.dense, self.weight_bits = dense, 8 if self.fp8 else 16 if dense else 4
+        # quant_method "mxfp4": that same checkpoint quantised to OCP MXFP4 (kernels.quantize_mxfp4_weight: e2m1 nibbles,
+        # one e8m0 scale byte per 32 k), the four linears are layers.{Column,Row}ParallelMxfp4Linear over slm_mxfp4_linear
+        self.fp8, self.mxfp4 = quant_method == "fp8", quant_method == "mxfp4"
+        dense = quant_method in ("none", "fp8", "mxfp4")
+        self.dense, self.weight_bits = dense, 8 if self.fp8 else 4.25 if self.mxfp4 else 16 if dense else 4
         # fuse_silu: the merged gate_up weight is packed paired and SiLU*mul runs in the GEMM
         # epilogue (identical bits; False keeps the separate kernels.silu_and_mul launch)
         fuse_silu = fuse_silu and (shape.intermediate // pa.world_size) % 32 == 0
@@ -316,6 +320,7 @@ class LlamaDecodeStep:
         def rows(w, ranges):
             return torch.cat([w[a:b] for a, b in ranges], dim=0).contiguous()
         Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if self.fp8 else \
+            (ColumnParallelMxfp4Linear, RowParallelMxfp4Linear) if self.mxfp4 else \
             (ColumnParallelLinear, RowParallelLinear)
         L["qkv"] = Col(H, qkv_n * tp, False, False, pa, dtype, dev)
         L["o"] = Row(q_full, H, False, True, pa, dtype, dev)
@@ -341,6 +346,26 @@ class LlamaDecodeStep:
             if keep_checkpoint:
                 self.ckpt.append({n: {"weight": w.clone(), "weight_scale": c.clone()} for n, (w, c) in q8.items()})
             for name, (w, c) in q8.items():
+                L[name].load_shard(w, c)
+                L[name].verify_loaded_weights()
+            return
+        if self.mxfp4:
+            # the FULL weights are quantised block by block and cut afterwards: rows with their scale rows, columns
+            # (whole MX blocks: the K shard is a multiple of 32) with their scale columns
+            def q4(n, k):
+                return kernels.quantize_mxfp4_weight(draw(n, k))
+
+            def cols(ws, sl):
+                return ws[0][:, sl.start // 2:sl.stop // 2].contiguous(), ws[1][:, sl.start // 32:sl.stop // 32].contiguous()
+            w4, sc = q4(q_full + 2 * kv_full, H)
+            m4 = {"qkv": (rows(w4, qkv_rows), rows(sc, qkv_rows))}
+            m4["o"] = cols(q4(H, q_full), o_cols)
+            w4, sc = q4(2 * inter, H)
+            m4["gate_up"] = (rows(w4, gu_rows), rows(sc, gu_rows))
+            m4["down"] = cols(q4(H, inter), down_cols)
+            if keep_checkpoint:
+                self.ckpt.append({n: {"weight": w.clone(), "weight_scale": c.clone()} for n, (w, c) in m4.items()})
+            for name, (w, c) in m4.items():
                 L[name].load_shard(w, c)
                 L[name].verify_loaded_weights()
             return

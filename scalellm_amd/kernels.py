@@ -886,12 +886,15 @@ def linear_plan(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Op
 
 
 def _run_linear(entry: str, g, dev: torch.device, defer_reduce: bool) -> DeferredPartials:
-    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear (`entry`) over the argument block g"""
+    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear / slm_mxfp4_linear (`entry`) over the
+    argument block g"""
     L = _lib.lib()
     if g.M == 0:
         return DeferredPartials()
     deferred = getattr(L, entry + "_deferred_splits")(C.byref(g)) if defer_reduce else 0
-    need = getattr(L, entry + "_workspace_bytes")(C.byref(g))
+    # (section 20 declares no _workspace_bytes query: the plan carries the size)
+    need = _linear_plan(entry, g).workspace_bytes if entry == "slm_mxfp4_linear" else \
+        getattr(L, entry + "_workspace_bytes")(C.byref(g))
     ws = None
     if need:
         # deferred slabs live in their own buffer (gptq_gemm: nothing else's scratch may overwrite them)
@@ -960,6 +963,126 @@ def fp8_linear(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor
     registers; `w_scale` fp32 [N] or None (1.0).  defer_reduce, silu_mul and the returned handle: as linear()."""
     return _run_linear("slm_fp8_linear", _linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul, fp8=True),
                        a.device, defer_reduce)
+
+
+# ---------------------------------------------------------------------------------------
+# MXFP4 (e2m1 + e8m0 block scale) weight-only linear: slm_hip.h section 20
+# ---------------------------------------------------------------------------------------
+MXFP4_BLOCK = 32
+# e2m1: 1 sign, 2 exponent (bias 1), 1 mantissa bit; codes 0..7, bit 3 is the sign
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mxfp4_bytes(t: torch.Tensor, what: str = "weight") -> torch.Tensor:
+    """The uint8 view of an MXFP4 checkpoint tensor: uint8 as it is, a weight also as torch.float4_e2m1fn_x2 or in the
+    [N, K/32, 16] form of gpt-oss `*_blocks` (flattened to [N, K/2]), a scale (`what` ends in "scale") also as
+    torch.float8_e8m0fnu.  Anything else -- the other tensor's typed dtype included: swapped keys -- is a TypeError."""
+    typed = "float8_e8m0fnu" if what.endswith("scale") else "float4_e2m1fn_x2"
+    if t.dtype != torch.uint8 and t.dtype != getattr(torch, typed, None):
+        raise TypeError(f"mxfp4 linear: {what} must be uint8 bytes (or {typed}), not "
+                        f"{t.dtype} (quantize_mxfp4_weight makes them; nothing is quantised on load)")
+    if t.dtype != torch.uint8:
+        t = t.view(torch.uint8)
+    if t.dim() == 3:
+        if t.size(2) != MXFP4_BLOCK // 2:
+            raise ValueError(f"{what}: the blocked form is [N, K/32, 16], not {tuple(t.shape)}")
+        t = t.reshape(t.size(0), -1)
+    return t
+
+
+def quantize_mxfp4_weight(w: torch.Tensor):
+    """Load-time quantisation of a weight [N, K] (K % 32 == 0) to OCP MXFP4 (torch ops; nothing on the hot path):
+    (packed uint8 [N, K/2], scale uint8 [N, K/32]).  Per block of 32 consecutive k the shared exponent is
+    floor(log2(amax)) - 2 (2 = e2m1's largest exponent), stored as the e8m0 byte e = exponent + 127 clamped to
+    [1, 254]; an all-zero block gets e = 127.  Elements are w / 2^(e - 127) rounded to nearest even onto the e2m1 grid
+    {0, .5, 1, 1.5, 2, 3, 4, 6} and saturated at 6.  A byte's low nibble is the lower k.
+    w ~ dequantize_mxfp4_weight(packed, scale, dtype)."""
+    if w.dim() != 2 or w.size(1) % MXFP4_BLOCK:
+        raise ValueError("quantize_mxfp4_weight takes a 2-D weight [N, K] with K % 32 == 0")
+    N, K = w.shape
+    blocks = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blocks.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                                # amax = m 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    e = torch.where(amax > 0, (ex - 1 - 2 + 127).clamp(1, 254), torch.full_like(ex, 127)).to(torch.int32)
+    x = torch.ldexp(blocks, (127 - e)[:, :, None]).abs()     # exact: a power of two
+    # round to nearest even per region of the grid: steps 0.5 below 2, 1 below 4, 2 above; saturate at 6
+    q = torch.where(x < 2, torch.round(x * 2) / 2, torch.where(x < 4, torch.round(x), torch.round(x / 2) * 2)).clamp(max=6)
+    idx = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4)).to(torch.int32)
+    codes = (idx | (((blocks < 0) & (q > 0)).to(torch.int32) << 3)).reshape(N, K)
+    packed = (codes[:, 0::2] | (codes[:, 1::2] << 4)).to(torch.uint8).contiguous()
+    return packed, e.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4_weight(packed: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.float32):
+    """[N, K] of `dtype` = e2m1(code) * 2^(e - 127), the low nibble of a byte first; exact wherever the product is a
+    normal number of `dtype` (bf16: e in [2, 252]; f16: e in [114, 140]).  e = 255 (the MX NaN) gives NaN."""
+    packed, scale = mxfp4_bytes(packed), mxfp4_bytes(scale, "weight_scale")
+    N, K = packed.size(0), 2 * packed.size(1)
+    if scale.dim() != 2 or tuple(scale.shape) != (N, K // MXFP4_BLOCK) or K % MXFP4_BLOCK:
+        raise ValueError(f"weight_scale must be [N, K/32] = {(N, K // MXFP4_BLOCK)}, not {tuple(scale.shape)}")
+    codes = torch.stack((packed & 0xF, packed >> 4), dim=2).reshape(N, K).long()
+    table = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float64, device=packed.device)
+    e = scale.to(torch.int32).repeat_interleave(MXFP4_BLOCK, dim=1)
+    val = torch.ldexp(table[codes], e - 127)
+    return torch.where(e == 255, torch.full_like(val, float("nan")), val).to(dtype)
+
+
+def _mxfp4_args(a, w, w_scale, c, bias, defer_reduce: bool, silu_mul: bool):
+    """Checks and argument block of mxfp4_linear() and its plan query: slm_linear_args over nibble bytes, plus the
+    block scales and their row stride"""
+    _require_gpu(a, w, w_scale, c, bias)
+    if silu_mul and defer_reduce:
+        raise SlmError("silu_mul and defer_reduce cannot be combined")
+    if w_scale is None:
+        raise SlmError("mxfp4_linear needs the e8m0 block scales [N, K/32]")
+    try:
+        w, w_scale = mxfp4_bytes(w), mxfp4_bytes(w_scale, "w_scale")
+    except (TypeError, ValueError) as e:
+        raise SlmError(str(e)) from None
+    if a.dim() != 2 or c.dim() != 2 or w.dim() != 2 or w_scale.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1 or \
+            w.stride(1) != 1 or w_scale.stride(1) != 1:
+        raise SlmError("A [M, K], W [N, K/2], w_scale [N, K/32] and C [M, N] must be 2-D with contiguous rows")
+    N, K = w.size(0), 2 * w.size(1)
+    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a.size(0) != c.size(0) or K % MXFP4_BLOCK or \
+            tuple(w_scale.shape) != (N, K // MXFP4_BLOCK):
+        raise SlmError("mxfp4_linear shape mismatch")
+    if c.dtype != a.dtype or (bias is not None and bias.dtype != a.dtype):
+        raise SlmError("activation / bias / output dtypes must match")
+    if bias is not None and (bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous()):
+        raise SlmError("bias must be a contiguous [N] tensor")
+    g = _lib.Mxfp4LinearArgs()
+    g.a, g.w, g.c = a.data_ptr(), w.data_ptr(), c.data_ptr()
+    g.bias = bias.data_ptr() if bias is not None else None
+    g.w_scale, g.lds = w_scale.data_ptr(), w_scale.stride(0)
+    g.M, g.K, g.N = a.size(0), K, N
+    g.lda, g.ldw, g.ldc = a.stride(0), w.stride(0), c.stride(0)
+    g.dtype = _dtype_code(a)
+    g.flags = _lib.SLM_LINEAR_SHARES_CHIP if _chip_flag() else 0
+    if silu_mul:
+        g.flags |= _lib.SLM_LINEAR_SILU_MUL
+    if defer_reduce:
+        g.flags |= _lib.SLM_LINEAR_DEFER_REDUCE
+    g.workspace, g.workspace_bytes = None, 0
+    return g
+
+
+def mxfp4_linear_plan(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
+                      bias: Optional[torch.Tensor] = None, defer_reduce: bool = False,
+                      silu_mul: bool = False) -> "_lib.LinearPlanInfo":
+    """The launch mxfp4_linear() would give these very arguments now (slm_mxfp4_linear_plan); a host-side query."""
+    return _linear_plan("slm_mxfp4_linear", _mxfp4_args(a, w, w_scale, c, bias, defer_reduce, silu_mul))
+
+
+def mxfp4_linear(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
+                 bias: Optional[torch.Tensor] = None, silu_mul: bool = False,
+                 defer_reduce: bool = False) -> DeferredPartials:
+    """W4A16 linear over an OCP MXFP4 checkpoint: C[M, N] = T(A[M, K] . T(e2m1(W[N, K]) * 2^(e[N, K/32] - 127))^T +
+    bias), fp32 accumulate, one rounding.  `w` is the checkpoint's packed weight, uint8 [N, K/2] (low nibble = lower
+    k; rows contiguous, row stride a multiple of 16), `w_scale` its e8m0 bytes uint8 [N, K/32] (any row stride); both
+    are streamed as they are and converted in registers.  defer_reduce, silu_mul and the returned handle: as
+    linear()."""
+    return _run_linear("slm_mxfp4_linear", _mxfp4_args(a, w, w_scale, c, bias, defer_reduce, silu_mul), a.device,
+                       defer_reduce)
 
 
 # ---------------------------------------------------------------------------------------

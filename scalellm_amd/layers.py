@@ -232,8 +232,10 @@ class Attention:
 class QuantArgs:
     """layers/quantization/quant_args.h:10-33.  quant_method "fp8" with bits = 8 selects e4m3 weight-only (W8A16)
     weights where a layer offers them (moe.FusedMoE / ExpertParallelMoE; LlamaDecodeStep takes quant_method="fp8"
-    directly); group_size, desc_act and zero_point mean nothing there and are ignored."""
-    quant_method: str = "awq"   # "awq" | "gptq" | "fp8"
+    directly); group_size, desc_act and zero_point mean nothing there and are ignored.  quant_method "mxfp4" is OCP
+    MXFP4 weight-only (W4A16: e2m1 nibbles, one e8m0 scale byte per 32 k, bits = 4 and group_size = 32 by the format):
+    LlamaDecodeStep takes quant_method="mxfp4" directly (layers.{Column,Row}ParallelMxfp4Linear)."""
+    quant_method: str = "awq"   # "awq" | "gptq" | "fp8" | "mxfp4"
     bits: int = 4
     group_size: int = 128
     desc_act: bool = False
@@ -690,6 +692,132 @@ class RowParallelFp8Linear(_Fp8LinearMixin, RowParallelLinear):
             raise ValueError("row-parallel linears are never fused (parallel_linear.h:28-33)")
         self._load_one(sd, "weight", 1)
         self._load_scale(sd, self.out_features, -1)
+        if self.has_bias:
+            self._load_one(sd, "bias", -1)
+
+
+# ---------------------------------------------------------------------------------------
+# MXFP4 (e2m1 + e8m0 block scale) weight-only linear layers: W4A16 over slm_mxfp4_linear
+# ---------------------------------------------------------------------------------------
+class _Mxfp4LinearMixin:
+    """What the two MXFP4 classes add to _LinearBase: `weight` is the checkpoint's packed tensor, uint8
+    [N, K/2] (a byte's low nibble is the lower k) -- or the same bytes as [N, K/32, 16] (gpt-oss `*_blocks`) or
+    torch.float4_e2m1fn_x2 -- and `weight_scale` its e8m0 bytes, uint8 or torch.float8_e8m0fnu [N, K/32]; both are
+    kept as bytes and streamed as they are (kernels.mxfp4_linear).  A weight of any other dtype is an error --
+    quantising is the checkpoint's job (kernels.quantize_mxfp4_weight), not a side effect of loading."""
+
+    weight_scale: Optional[torch.Tensor] = None
+
+    def _set(self, name: str, t: torch.Tensor) -> None:
+        if name == "weight":
+            t = kernels.mxfp4_bytes(t, "weight")
+            if tuple(t.shape) != (self.local_out, self.local_in // 2):
+                raise ValueError(f"weight size mismatch: {tuple(t.shape)} vs {(self.local_out, self.local_in // 2)}")
+            self.weight = t.to(self.device).contiguous()
+        elif name == "weight_scale":
+            t = kernels.mxfp4_bytes(t, "weight_scale")
+            if tuple(t.shape) != (self.local_out, self.local_in // 32):
+                raise ValueError(f"weight_scale size mismatch: {tuple(t.shape)} vs "
+                                 f"{(self.local_out, self.local_in // 32)}")
+            self.weight_scale = t.to(self.device).contiguous()
+        else:
+            super()._set(name, t)
+
+    def _bytes_of(self, sd: Dict[str, torch.Tensor], key: str, cols: int) -> torch.Tensor:
+        """a checkpoint tensor as 2-D bytes, `cols` = its full row length"""
+        t = kernels.mxfp4_bytes(sd[key], key)
+        if t.dim() != 2 or t.size(1) != cols:
+            raise ValueError(f"{key} size mismatch: {tuple(sd[key].shape)} for in_features {self.in_features}")
+        return t
+
+    def load_shard(self, weight: torch.Tensor, weight_scale: torch.Tensor,  # noqa: D401
+                   bias: Optional[torch.Tensor] = None) -> None:
+        """THIS rank's shard, already cut: packed weight [local_out, local_in / 2] and scales [local_out,
+        local_in / 32]."""
+        if self.weight_scale is not None:
+            raise RuntimeError("weight_scale is loaded twice")
+        kernels.mxfp4_bytes(weight_scale, "weight_scale")
+        super().load_shard(weight, bias)
+        self._set("weight_scale", weight_scale)
+
+    def verify_loaded_weights(self, prefix: str = "") -> None:
+        super().verify_loaded_weights(prefix)
+        if self.weight_scale is None:
+            raise RuntimeError(f"weight_scale is not loaded for {prefix}weight_scale")
+
+    def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor],
+                defer_splitk: bool = False) -> torch.Tensor:
+        self.verify_loaded_weights()
+        x2 = x.reshape(-1, x.size(-1))
+        n_out = self.local_out // 2 if self.paired else self.local_out
+        if out is None:
+            out = torch.empty(x2.size(0), n_out, dtype=x.dtype, device=x.device)
+        self.deferred = kernels.mxfp4_linear(x2, self.weight, self.weight_scale, out, bias,
+                                             defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
+        self.deferred_splits = int(self.deferred)
+        return out
+
+
+class ColumnParallelMxfp4Linear(_Mxfp4LinearMixin, ColumnParallelLinear):
+    """ColumnParallelLinear over an MXFP4 checkpoint: weight AND weight_scale are sharded on dim 0.  A fused load
+    (prefixes=[...]) concatenates both tensors of the shards on dim 0 (q | k | v, gate | up)."""
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        K = self.in_features
+        if not prefixes:
+            for name, cols in (("weight", K // 2), ("weight_scale", K // 32)):
+                if name in sd:
+                    if getattr(self, name) is not None:
+                        raise RuntimeError(f"{name} is loaded twice")
+                    self._set(name, self._shard(self._bytes_of(sd, name, cols), 0, name))
+            if self.has_bias:
+                self._load_one(sd, "bias", 0)
+            return
+        # per prefix: (weight shard, scale shard); both tensors of a prefix come together
+        parts = self._parts.setdefault("weight", [None] * len(prefixes))
+        for i, p in enumerate(prefixes):
+            if p + "weight" not in sd:
+                if p + "weight_scale" in sd:
+                    raise RuntimeError(f"{p}weight_scale arrives without {p}weight")
+                continue
+            if parts[i] is not None or self.weight is not None:
+                raise RuntimeError(f"{p}weight is loaded twice")
+            w = self._bytes_of(sd, p + "weight", K // 2)
+            if p + "weight_scale" not in sd:
+                raise RuntimeError(f"{p}weight arrives without {p}weight_scale")
+            s = self._bytes_of(sd, p + "weight_scale", K // 32)
+            if s.size(0) != w.size(0):
+                raise ValueError(f"{p}weight_scale has {s.size(0)} rows for {w.size(0)} weight rows")
+            parts[i] = (self._shard(w, 0, p + "weight").to(self.device),
+                        self._shard(s, 0, p + "weight_scale").to(self.device))
+        if "weight" in self._parts and all(t is not None for t in parts):
+            self._set("weight", torch.cat([w for w, _ in parts], dim=0))
+            self._set("weight_scale", torch.cat([s for _, s in parts], dim=0))
+            del self._parts["weight"]
+        if self.has_bias:
+            self._load_fused(sd, prefixes, "bias")
+
+
+class RowParallelMxfp4Linear(_Mxfp4LinearMixin, RowParallelLinear):
+    """RowParallelLinear over an MXFP4 checkpoint: weight and weight_scale are both sharded on dim 1 (a scale byte
+    belongs to 32 k of its row), so the K shard must be a multiple of 32.  With world_size > 1: GEMM, all-reduce,
+    then the bias."""
+
+    def __init__(self, in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device):
+        super().__init__(in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device)
+        if self.local_in % 32:
+            raise ValueError(f"mxfp4 row-parallel linear: the K shard {self.local_in} (in_features {in_features} / "
+                             f"world_size {parallel_args.world_size}) must be a multiple of the MX block, 32")
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        if prefixes:
+            raise ValueError("row-parallel linears are never fused (parallel_linear.h:28-33)")
+        K = self.in_features
+        for name, cols in (("weight", K // 2), ("weight_scale", K // 32)):
+            if name in sd:
+                if getattr(self, name) is not None:
+                    raise RuntimeError(f"{name} is loaded twice")
+                self._set(name, self._shard(self._bytes_of(sd, name, cols), 1, name))
         if self.has_bias:
             self._load_one(sd, "bias", -1)
 
