@@ -1642,6 +1642,74 @@ SLM_API int slm_mxfp4_linear_plan(const slm_mxfp4_linear_args* a, slm_linear_pla
 SLM_API int32_t slm_mxfp4_linear_deferred_splits(const slm_mxfp4_linear_args* a);
 SLM_API int slm_mxfp4_linear(const slm_mxfp4_linear_args* a, void* stream);
 
+/* ========================================================================== */
+/* 21. MXFP4 mixture-of-experts: grouped W4A16 GEMM over OCP MX experts       */
+/*    slm_moe_gemm (section 10) with section 20's weight side.  For every     */
+/*    32-row block b of the aligned token list (slm_moe_align_block with      */
+/*    block_size 32), e = expert_ids[b], idx = sorted[b * 32 + r]:            */
+/*      w_e[n, k]   = T( e2m1(W_e[n, k]) * 2^(s_e[n, k / 32] - 127) )         */
+/*      acc[idx, n] = sum over k of A[idx / a_div, k] * w_e[n, k]             */
+/*      C[idx, n]   = T( acc * row_scale[idx] )          ONE rounding to T    */
+/*    The block scale is applied by the hardware converter, never to the      */
+/*    accumulator.  Where e2m1 * 2^(s - 127) is zero or a normal number of T  */
+/*    (bf16: s in [2, 252]; f16: s in [114, 140]) w_e is exact and the call   */
+/*    is slm_moe_gemm on the dequantised [E, N, K] tensor bit for bit (fp32   */
+/*    MFMA accumulation in slm_moe_gemm's k order, the same launch shapes):   */
+/*    the plain output, the row_scale form and the SLM_MOE_SILU_MUL form      */
+/*    alike.  Scale bytes outside that range behave as section 20 says        */
+/*    (subnormals kept, inf beyond T's range, s = 255 is NaN for every code). */
+/*    W_e = w + e * w_expert_stride BYTES, [N, K/2] bytes of two e2m1 codes,  */
+/*    a byte's LOW nibble the lower k, row stride ldw in bytes: the           */
+/*    checkpoint tensor (Quark `weight`, gpt-oss `*_blocks`), never           */
+/*    prepacked.  s_e = w_scale + e * w_scale_expert_stride BYTES, [N, K/32]  */
+/*    e8m0 bytes, row stride lds in bytes; REQUIRED.                          */
+/*    With SLM_MOE_SILU_MUL: rows [0, N/2) of W_e are the gate, [N/2, N) the  */
+/*    up projection, c[idx, i] = T(silu(T(gate)) * T(up)): the bits of the    */
+/*    plain call followed by slm_silu_mul.  Not with row_scale.               */
+/*    The aligned-list contract, dead blocks (beyond n_padded, expert ids     */
+/*    outside [0, E)), padding rows, the launch shape (128 / 64 / 32 columns  */
+/*    per workgroup from max_blocks, N and flags alone; no split-K, no        */
+/*    workspace, no atomics: bit-identical repeats and launch shapes), the    */
+/*    shapes (K % 32 == 0, N % 32 == 0, (N/2) % 32 == 0 with SILU_MUL) and    */
+/*    the error codes are slm_moe_gemm's, rule for rule.  The weight side:    */
+/*    w 16-byte aligned, ldw % 16 == 0, w_expert_stride % 16 == 0             */
+/*    (SLM_ERR_ALIGNMENT); ldw >= K/2, w_expert_stride >= (N - 1) * ldw +     */
+/*    K/2, w_scale not NULL, lds >= K/32, w_scale_expert_stride >=            */
+/*    (N - 1) * lds + K/32 (SLM_ERR_INVALID_ARG); w_scale, lds and            */
+/*    w_scale_expert_stride carry no alignment requirement (K/32 is 21 at     */
+/*    K = 672); one expert (N * ldw bytes, N * lds scale bytes) < 4 GiB       */
+/*    (SLM_ERR_UNSUPPORTED).  No byte outside an expert's own [N, K/2] and    */
+/*    [N, K/32] rows is read, so the padding of strided operands may hold     */
+/*    anything.  All validation before any launch; n_flat == 0 or             */
+/*    max_blocks == 0 is a no-op (csrc/moe_gemm.hip, csrc/mxfp4_cvt.h).       */
+/* ========================================================================== */
+typedef struct slm_moe_mxfp4_gemm_args {
+  const void* a;                    /* [n_flat / a_div, K] T, row stride lda (elements)           */
+  const void* w;                    /* expert 0: [N, K/2] bytes of two e2m1 codes, row stride ldw (bytes) */
+  const uint8_t* w_scale;           /* expert 0: [N, K/32] e8m0 bytes, row stride lds (bytes); required */
+  void* c;                          /* [n_flat, N] T (SILU_MUL: [n_flat, N/2]), row stride ldc    */
+  const float* row_scale;           /* [n_flat] fp32 or NULL                                      */
+  const int32_t* sorted_token_idxes;
+  const int32_t* expert_ids;
+  const int32_t* n_padded_tokens;   /* [1], read on the device                                    */
+  int64_t w_expert_stride;          /* bytes between experts, >= (N - 1) * ldw + K/2              */
+  int64_t w_scale_expert_stride;    /* bytes between experts' scales, >= (N - 1) * lds + K/32     */
+  int64_t n_flat;                   /* rows of c = T * k; the padding id                          */
+  int64_t K, N;
+  int64_t lda, ldw, ldc;
+  int32_t a_div;                    /* >= 1                                                       */
+  int32_t n_experts;
+  int32_t max_blocks;               /* sizes the grid: slm_moe_align_capacity(n_flat, E, 32)      */
+  int32_t dtype;
+  int32_t flags;                    /* 0 or SLM_MOE_SILU_MUL                                      */
+  int64_t lds;                      /* row stride of w_scale in bytes, >= K/32; everything above is
+                                       slm_moe_fp8_gemm_args, field for field (w_scale: bytes)    */
+} slm_moe_mxfp4_gemm_args;
+/* (the parameter list on its own line, as slm_moe_gemm's and slm_moe_fp8_gemm's; tests/test_moe_mxfp4_cpu.py covers
+ * this entry) */
+SLM_API int slm_moe_mxfp4_gemm
+    (const slm_moe_mxfp4_gemm_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

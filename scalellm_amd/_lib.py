@@ -188,6 +188,12 @@ class MoeFp8GemmArgs(C.Structure):
     ]
 
 
+class MoeMxfp4GemmArgs(C.Structure):
+    """struct slm_moe_mxfp4_gemm_args (include/slm_hip.h section 21): slm_moe_fp8_gemm_args, field for field (w_scale:
+    e8m0 bytes, its expert stride in bytes), plus the scales' row stride."""
+    _fields_ = MoeFp8GemmArgs._fields_ + [("lds", C.c_int64)]
+
+
 class MoeRouterArgs(C.Structure):
     """struct slm_moe_router_args (include/slm_hip.h section 17)."""
     _fields_ = [
@@ -434,6 +440,7 @@ def lib() -> C.CDLL:
         ("slm_mxfp4_linear", C.c_int, [C.POINTER(Mxfp4LinearArgs), C.c_void_p]),
         ("slm_mxfp4_linear_deferred_splits", C.c_int32, [C.POINTER(Mxfp4LinearArgs)]),
         ("slm_mxfp4_linear_plan", C.c_int, [C.POINTER(Mxfp4LinearArgs), C.POINTER(LinearPlanInfo)]),
+        ("slm_moe_mxfp4_gemm", C.c_int, [C.POINTER(MoeMxfp4GemmArgs), C.c_void_p]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

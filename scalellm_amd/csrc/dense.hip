@@ -89,8 +89,6 @@ constexpr int LIN_RING = 3;   // weight / A register rings (chunks)
 constexpr int LIN_MX_RING_1X1 = 4;   // the mxfp4 side's one-wave form (RT 1 x NW 1), see "Ring depth" above
 // -DSLM_LIN_MX_RING=R: every mxfp4 form at depth R >= 2, the build-time switch of tools/ab_mxfp4_ring.py
 
-enum WeightSide { W_T = 0, W_E4M3 = 1, W_MXFP4 = 2 };
-
 struct LinearKParams {
   static constexpr int SIDE = W_T;
   const char* a;

@@ -6,6 +6,9 @@
 
 namespace slm {
 
+// the compile-time weight side of a weight-stream kernel (KP::SIDE in dense.hip and moe_gemm.hip)
+enum WeightSide { W_T = 0, W_E4M3 = 1, W_MXFP4 = 2 };
+
 // two e4m3 codes (the low or the high half of `w`) -> a packed pair of T, exact
 template <typename T, bool HI>
 __device__ __forceinline__ uint32_t fp8x2_to_t(uint32_t w);

@@ -218,6 +218,59 @@ void moe_fp8_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w8, const
   check(slm_moe_fp8_gemm(&g, stream_of(a)), "slm_moe_fp8_gemm");
 }
 
+void moe_mxfp4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w, const torch::Tensor& w_scale,
+                            torch::Tensor& c, const torch::Tensor& sorted_token_idxes,
+                            const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
+                            const torch::Tensor& row_scale, bool silu_mul) {
+  TORCH_CHECK(a.is_cuda() && c.is_cuda() && a.dim() == 2 && c.dim() == 2 && a.stride(1) == 1 && c.stride(1) == 1,
+              "slm moe: A and C must be 2-D GPU tensors with contiguous rows");
+  TORCH_CHECK(w.is_cuda() && w.dim() == 3 && w.stride(2) == 1 && w.scalar_type() == torch::kByte,
+              "slm moe: mxfp4 expert weights must be a uint8 GPU tensor [n_experts, N, K/2] with k contiguous");
+  TORCH_CHECK(a.scalar_type() == c.scalar_type(), "slm moe: A and C must share a dtype");
+  check_i32(sorted_token_idxes, "sorted_token_idxes");
+  check_i32(expert_ids, "expert_ids");
+  check_i32(n_padded_tokens, "n_padded_tokens");
+  const int64_t E = w.size(0), N = w.size(1), K = 2 * w.size(2);
+  TORCH_CHECK(w_scale.defined() && w_scale.is_cuda() && w_scale.scalar_type() == torch::kByte && w_scale.dim() == 3 &&
+                  K % 32 == 0 && w_scale.size(0) == E && w_scale.size(1) == N && w_scale.size(2) == K / 32 &&
+                  w_scale.stride(2) == 1,
+              "slm moe: mxfp4 w_scale must be uint8 [n_experts, N, K/32] e8m0 bytes with k contiguous");
+  TORCH_CHECK(a.size(1) == K && c.size(1) == (silu_mul ? N / 2 : N) && a_div >= 1 && a.size(0) * a_div >= c.size(0),
+              "slm moe: grouped GEMM shape mismatch");
+  TORCH_CHECK(sorted_token_idxes.numel() >= expert_ids.numel() * 32,
+              "slm moe: sorted_token_idxes is shorter than expert_ids.numel() blocks of 32");
+  slm_moe_mxfp4_gemm_args g{};
+  g.a = a.data_ptr();
+  g.w = w.data_ptr();
+  g.w_scale = w_scale.const_data_ptr<uint8_t>();
+  g.c = c.data_ptr();
+  if (row_scale.defined()) {
+    TORCH_CHECK(row_scale.is_cuda() && row_scale.scalar_type() == torch::kFloat && row_scale.is_contiguous() &&
+                    row_scale.numel() == c.size(0),
+                "slm moe: row_scale must be contiguous fp32 with one entry per row of C");
+    g.row_scale = row_scale.const_data_ptr<float>();
+  }
+  g.sorted_token_idxes = sorted_token_idxes.const_data_ptr<int32_t>();
+  g.expert_ids = expert_ids.const_data_ptr<int32_t>();
+  g.n_padded_tokens = n_padded_tokens.const_data_ptr<int32_t>();
+  // a single expert's stride(0) is not meaningful: what covers the expert will do (the weights: a multiple of 16)
+  g.w_expert_stride = E > 1 ? w.stride(0) : std::max(w.stride(0), N * w.stride(1));
+  g.w_scale_expert_stride = E > 1 ? w_scale.stride(0) : std::max(w_scale.stride(0), N * w_scale.stride(1));
+  g.n_flat = c.size(0);
+  g.K = K;
+  g.N = N;
+  g.lda = a.stride(0);
+  g.ldw = w.stride(1);
+  g.ldc = c.stride(0);
+  g.lds = w_scale.stride(1);
+  g.a_div = static_cast<int32_t>(a_div);
+  g.n_experts = static_cast<int32_t>(E);
+  g.max_blocks = static_cast<int32_t>(expert_ids.numel());
+  g.dtype = dtype_code(a);
+  g.flags = silu_mul ? SLM_MOE_SILU_MUL : 0;
+  check(slm_moe_mxfp4_gemm(&g, stream_of(a)), "slm_moe_mxfp4_gemm");
+}
+
 void moe_router(const torch::Tensor& x, const torch::Tensor& gate_weight, torch::Tensor& topk_weights,
                 torch::Tensor& topk_indices, const std::string& scoring, bool renormalize,
                 const torch::Tensor& correction_bias, int64_t n_expert_groups, int64_t topk_group,

@@ -9,6 +9,7 @@
 //                              src/kernels/gemm/, is a dense fp16 / bf16 kernel; int4 experts have no counterpart).
 //   slm::moe_grouped_gemm      that dense fp16 / bf16 grouped GEMM over W[e, n, k].
 //   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm.hip).
+//   slm::moe_mxfp4_grouped_gemm  the same over OCP MXFP4 experts with e8m0 block scales (section 21, csrc/moe_gemm.hip).
 //   slm::moe_router            the fused router: gate GEMM + routing in one launch (section 17, csrc/moe_router.hip).
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
@@ -84,6 +85,14 @@ void moe_fp8_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w8, const
                           torch::Tensor& c, const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
                           const torch::Tensor& n_padded_tokens, int64_t a_div, const torch::Tensor& row_scale,
                           bool silu_mul);
+
+// moe_grouped_gemm over OCP MXFP4 experts (include/slm_hip.h section 21): w uint8 [E, N, K/2] (two e2m1 codes a byte,
+// the low nibble the lower k; expert and row strides multiples of 16), w_scale uint8 [E, N, K/32] e8m0 bytes (any
+// stride, any alignment), both required and read as the checkpoint stores them.  The rest as moe_grouped_gemm.
+void moe_mxfp4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w, const torch::Tensor& w_scale,
+                            torch::Tensor& c, const torch::Tensor& sorted_token_idxes,
+                            const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
+                            const torch::Tensor& row_scale, bool silu_mul);
 
 // logits = x [T, hidden] . gate_weight [E, hidden]^T in fp32 and their routing, in one launch: scoring "softmax"
 // (renormalize) or "grouped_sigmoid" (correction_bias, n_expert_groups, topk_group, scaling_factor); topk is

@@ -341,6 +341,16 @@ PYBIND11_MODULE(_slm_shim, m) {
         }, py::arg("a"), py::arg("w8"), py::arg("w_scale"), py::arg("c"), py::arg("sorted_token_idxes"),
         py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(),
         py::arg("silu_mul") = false);
+  m.def("moe_mxfp4_grouped_gemm",
+        [](const torch::Tensor& a, const torch::Tensor& w, const torch::Tensor& w_scale, torch::Tensor c,
+           const torch::Tensor& sorted_token_idxes, const torch::Tensor& expert_ids,
+           const torch::Tensor& n_padded_tokens, int64_t a_div, const c10::optional<torch::Tensor>& row_scale,
+           bool silu_mul) {
+          slm::moe_mxfp4_grouped_gemm(a, w, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, a_div,
+                                      row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
+        }, py::arg("a"), py::arg("w"), py::arg("w_scale"), py::arg("c"), py::arg("sorted_token_idxes"),
+        py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("a_div"), py::arg("row_scale") = py::none(),
+        py::arg("silu_mul") = false);
   m.def("moe_router",
         [](const torch::Tensor& x, const torch::Tensor& gate_weight, torch::Tensor topk_weights,
            torch::Tensor topk_indices, const std::string& scoring, bool renormalize,

@@ -1966,6 +1966,67 @@ def moe_fp8_grouped_gemm(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[to
                       fp8=True)
 
 
+def moe_mxfp4_grouped_gemm(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
+                           sorted_token_idxes: torch.Tensor, expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor,
+                           a_div: int, row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """moe_grouped_gemm over OCP MXFP4 experts (slm_hip.h section 21): C[idx] = epilogue(A[idx // a_div] .
+    T(e2m1(W[e]) * 2^(w_scale[e] - 127))^T).  `w` is uint8 [E, N, K/2] (two e2m1 codes a byte, the low nibble the lower
+    k; or torch.float4_e2m1fn_x2; or the [E, N, K/32, 16] blocks view of the same memory), the checkpoint layout, k
+    contiguous, expert and row strides may be padded (multiples of 16); `w_scale` uint8 [E, N, K/32] e8m0 bytes (or
+    torch.float8_e8m0fnu), rows contiguous, any row / expert stride and any base alignment.  Both are streamed as they
+    are and converted in registers; the block scale goes through the converter, nothing touches the accumulator.
+    silu_mul, row_scale, the aligned list and the grid: as moe_grouped_gemm."""
+    _require_gpu(a, w, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    if w_scale is None:
+        raise SlmError("moe_mxfp4_grouped_gemm needs the e8m0 block scales [n_experts, N, K/32]")
+    for t, typed, what in ((w, "float4_e2m1fn_x2", "w"), (w_scale, "float8_e8m0fnu", "w_scale")):
+        if t.dtype != torch.uint8 and t.dtype != getattr(torch, typed, None):
+            raise SlmError(f"moe_mxfp4_grouped_gemm: {what} must be uint8 bytes (or {typed}), not {t.dtype}")
+    if w.dtype != torch.uint8:
+        w = w.view(torch.uint8)
+    if w_scale.dtype != torch.uint8:
+        w_scale = w_scale.view(torch.uint8)
+    if w.dim() == 4:  # [E, N, K/32, 16]: the same bytes as [E, N, K/2]
+        if w.size(3) != MXFP4_BLOCK // 2 or w.stride(3) != 1 or w.stride(2) != MXFP4_BLOCK // 2:
+            raise SlmError(f"the blocked form is [n_experts, N, K/32, 16] with contiguous rows, not {tuple(w.shape)}")
+        w = w.as_strided((w.size(0), w.size(1), w.size(2) * w.size(3)), (w.stride(0), w.stride(1), 1),
+                         w.storage_offset())
+    if a.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or c.stride(1) != 1:
+        raise SlmError("A and C must be 2-D with contiguous rows")
+    if w.dim() != 3 or w.stride(2) != 1 or w_scale.dim() != 3 or w_scale.stride(2) != 1:
+        raise SlmError("expert weights must be [n_experts, N, K/2] and scales [n_experts, N, K/32], k contiguous")
+    E, N, K = w.size(0), w.size(1), 2 * w.size(2)
+    n_flat = c.size(0)
+    if K % MXFP4_BLOCK or tuple(w_scale.shape) != (E, N, K // MXFP4_BLOCK):
+        raise SlmError(f"w_scale must be [n_experts, N, K/32] = {(E, N, K // MXFP4_BLOCK)}, not {tuple(w_scale.shape)}")
+    if a.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a_div < 1 or a.size(0) * a_div < n_flat:
+        raise SlmError("grouped GEMM shape mismatch")
+    if a.dtype not in (torch.float16, torch.bfloat16) or c.dtype != a.dtype:
+        raise SlmError("activation and output must share one dtype, fp16 or bf16")
+    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
+    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
+        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
+                                  row_scale.numel() != n_flat):
+        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
+    g = _lib.MoeMxfp4GemmArgs()
+    g.a, g.w, g.w_scale, g.c = a.data_ptr(), w.data_ptr(), w_scale.data_ptr(), c.data_ptr()
+    g.row_scale = row_scale.data_ptr() if row_scale is not None else None
+    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
+    g.n_padded_tokens = n_padded_tokens.data_ptr()
+    # a single expert's stride(0) is not meaningful: what covers the expert will do (the weights: a multiple of 16)
+    g.w_expert_stride = w.stride(0) if E > 1 else max(w.stride(0), N * w.stride(1))
+    g.w_scale_expert_stride = w_scale.stride(0) if E > 1 else max(w_scale.stride(0), N * w_scale.stride(1))
+    g.n_flat, g.K, g.N = n_flat, K, N
+    g.lda, g.ldw, g.ldc, g.lds = a.stride(0), w.stride(1), c.stride(0), w_scale.stride(1)
+    g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
+    g.dtype = _dtype_code(a)
+    g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
+    check(_lib.lib().slm_moe_mxfp4_gemm(C.byref(g), _stream()), "slm_moe_mxfp4_gemm")
+
+
 # ---------------------------------------------------------------------------------------
 # MoE token permutation (slm_hip.h section 14; csrc/permute.hip)
 #   permute_with_index_map / unpermute_with_index_map <- llm::kernel::moe::  (permutation_index_kernel.cu)

@@ -234,7 +234,8 @@ class QuantArgs:
     weights where a layer offers them (moe.FusedMoE / ExpertParallelMoE; LlamaDecodeStep takes quant_method="fp8"
     directly); group_size, desc_act and zero_point mean nothing there and are ignored.  quant_method "mxfp4" is OCP
     MXFP4 weight-only (W4A16: e2m1 nibbles, one e8m0 scale byte per 32 k, bits = 4 and group_size = 32 by the format):
-    LlamaDecodeStep takes quant_method="mxfp4" directly (layers.{Column,Row}ParallelMxfp4Linear)."""
+    LlamaDecodeStep takes quant_method="mxfp4" directly (layers.{Column,Row}ParallelMxfp4Linear), and
+    QuantArgs("mxfp4", 4) selects moe.MoEMxfp4Experts in moe.FusedMoE / ExpertParallelMoE (the other fields ignored)."""
     quant_method: str = "awq"   # "awq" | "gptq" | "fp8" | "mxfp4"
     bits: int = 4
     group_size: int = 128

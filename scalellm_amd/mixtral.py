@@ -14,9 +14,11 @@ with the dense MLP replaced by a sparse mixture of experts (HuggingFace MixtralD
     residual + the next layer's input norm (or the final norm)                   kernels.rms_norm(residual=)
   untied lm_head, no cap -> argmax, or the fused sampling kernel
 
-quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16) or "awq" (int4): the
-four attention linears are the classes LlamaDecodeStep uses for that method, the experts the matching experts class
-of moe.py, loaded through load_state_dict under the Mixtral names experts.{e}.w1|w2|w3.*; gate.weight stays in T.
+quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16), "mxfp4" (OCP MXFP4:
+e2m1 nibbles + e8m0 block scales, W4A16, the "none" checkpoint of the same seed quantised, loaded under the Quark
+names weight / weight_scale) or "awq" (int4): the four attention linears are the classes LlamaDecodeStep uses for
+that method, the experts the matching experts class of moe.py, loaded through load_state_dict under the Mixtral names
+experts.{e}.w1|w2|w3.*; gate.weight, the embedding, the head and the norms stay in T.
 
 Out of scope: tensor- or expert-parallel Mixtral (world_size > 1 is refused), two lanes, a C++ host step.
 """
@@ -30,8 +32,9 @@ import torch
 
 from . import kernels
 from .decode import _rand_int4_linear
-from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler,
-                     InputParameters, KVCache, QuantArgs, RowParallelFp8Linear, RowParallelLinear, RowParallelQLinear)
+from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelMxfp4Linear,
+                     ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache, QuantArgs, RowParallelFp8Linear,
+                     RowParallelLinear, RowParallelMxfp4Linear, RowParallelQLinear)
 from .model_parallel import ParallelArgs
 from .moe import FusedMoE
 
@@ -78,8 +81,8 @@ class MixtralDecodeStep:
         pa = parallel_args or ParallelArgs()
         if pa.world_size > 1 or custom_allreduce is not None:
             raise ValueError("MixtralDecodeStep runs on one rank: tensor-parallel sharding of an expert is out of scope")
-        if quant_method not in ("none", "fp8", "awq"):
-            raise ValueError(f"quant_method must be 'none', 'fp8' or 'awq', not {quant_method!r}")
+        if quant_method not in ("none", "fp8", "awq", "mxfp4"):
+            raise ValueError(f"quant_method must be 'none', 'fp8', 'awq' or 'mxfp4', not {quant_method!r}")
         # keep_checkpoint: retain the CHECKPOINT-format tensors (self.ckpt[layer]: "qkv", "o" as the linears take
         # them, "moe" the state dict FusedMoE.load_state_dict took) so a parity test can rebuild the model on the CPU
         self.ckpt = [] if keep_checkpoint else None
@@ -97,7 +100,7 @@ class MixtralDecodeStep:
         handler = HipAttnHandler(sm_scale=D ** -0.5, rotary_dim=D, cos_sin=cos_sin, interleaved=False)
         self.attn = Attention(shape.n_heads, shape.n_kv_heads, D, handler)
         nq, nkv = shape.n_heads * D, shape.n_kv_heads * D
-        qa = {"none": None, "fp8": QuantArgs("fp8", 8),
+        qa = {"none": None, "fp8": QuantArgs("fp8", 8), "mxfp4": QuantArgs("mxfp4", 4),
               "awq": QuantArgs(quant_method="awq", bits=4, group_size=group_size, zero_point=True)}[quant_method]
         draw = lambda n, kk: (torch.randn(n, kk, device=dev, generator=gen) * 0.02).to(dtype)  # noqa: E731
         norm_w = lambda: (1 + 0.05 * torch.randn(H, device=dev, generator=gen)).to(dtype)  # noqa: E731
@@ -117,6 +120,7 @@ class MixtralDecodeStep:
                     L[name]._repack()
                     continue
                 Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if quant_method == "fp8" else \
+                    (ColumnParallelMxfp4Linear, RowParallelMxfp4Linear) if quant_method == "mxfp4" else \
                     (ColumnParallelLinear, RowParallelLinear)
                 L[name] = Col(K, N, False, False, pa, dtype, dev) if col else Row(K, N, False, True, pa, dtype, dev)
                 w = draw(N, K)
@@ -124,6 +128,10 @@ class MixtralDecodeStep:
                     w8, sc = kernels.quantize_fp8_weight(w)
                     ck[name] = {"weight": w8, "weight_scale": sc}
                     L[name].load_shard(w8, sc)
+                elif quant_method == "mxfp4":   # the same checkpoint quantised to MXFP4, under the Quark names
+                    w4, sc = kernels.quantize_mxfp4_weight(w)
+                    ck[name] = {"weight": w4, "weight_scale": sc}
+                    L[name].load_state_dict(ck[name])
                 else:
                     ck[name] = {"weight": w}
                     L[name].load_shard(w)
@@ -137,6 +145,8 @@ class MixtralDecodeStep:
                             sd[p + tn] = t
                     elif quant_method == "fp8":
                         sd[p + "weight"], sd[p + "weight_scale"] = kernels.quantize_fp8_weight(draw(N, K))
+                    elif quant_method == "mxfp4":
+                        sd[p + "weight"], sd[p + "weight_scale"] = kernels.quantize_mxfp4_weight(draw(N, K))
                     else:
                         sd[p + "weight"] = draw(N, K)
             L["moe"] = FusedMoE(H, inter, E, k, qa, scoring="softmax", renormalize=True, max_tokens=T, dtype=dtype,

@@ -1,6 +1,6 @@
-"""Mixture-of-experts FFN over int4 (AWQ / GPTQ), fp8 (e4m3, weight-only) or unquantised f16 / bf16 experts: routing,
-block alignment, two grouped GEMMs and the sum over a token's experts, every step a HIP kernel of libslm_hip
-(include/slm_hip.h sections 10 and 16).
+"""Mixture-of-experts FFN over int4 (AWQ / GPTQ), fp8 (e4m3, weight-only), OCP MXFP4 (weight-only) or unquantised
+f16 / bf16 experts: routing, block alignment, two grouped GEMMs and the sum over a token's experts, every step a HIP
+kernel of libslm_hip (include/slm_hip.h sections 10, 16 and 21).
 
     FusedMoE.forward(x):  router logits (fp32, torch: [T, hidden] x [hidden, E] is tiny)
                           -> moe_topk_softmax | moe_grouped_topk_sigmoid      (weights, expert ids)
@@ -234,15 +234,85 @@ class MoEFp8Experts:
                                      **epilogue)
 
 
+class MoEMxfp4Experts:
+    """The OCP MXFP4 weights of E experts, stacked in the checkpoint's own [out, in] layout as bytes of two e2m1 codes
+    (low nibble = lower k) with one e8m0 scale byte per 32 k: `gate_up` uint8 [E, 2 * intermediate, hidden / 2] (w1
+    rows, then w3 rows) + `gate_up_scale` uint8 [E, 2 * intermediate, hidden / 32]; `down` [E, hidden,
+    intermediate / 2] + `down_scale` [E, hidden, intermediate / 32].  load_state_dict takes the Quark names
+    experts.{e}.w1|w3|w2.weight (uint8, or float4_e2m1fn_x2 / the [rows, K/32, 16] blocks form) and .weight_scale
+    (uint8 or float8_e8m0fnu), both through kernels.mxfp4_bytes: any other dtype is a TypeError -- nothing is quantised
+    on load, as in the MXFP4 linears."""
+
+    def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device,
+                 expert_offset: int = 0):
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise SlmError(f"MoE experts: fp16 / bf16 activations only, got {dtype}")
+        self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
+        self.dtype, self.device = dtype, device
+        self.expert_offset = expert_offset   # expert e of this holder is experts.{expert_offset + e}.* (an EP shard)
+        self._ckpt: Dict[str, torch.Tensor] = {}
+        self.gate_up: Optional[torch.Tensor] = None
+        self.down: Optional[torch.Tensor] = None
+        self.gate_up_scale: Optional[torch.Tensor] = None
+        self.down_scale: Optional[torch.Tensor] = None
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        for e in range(self.n_experts):
+            for w in ("w1", "w2", "w3"):
+                src, dst = f"experts.{self.expert_offset + e}.{w}.", f"experts.{e}.{w}."
+                for name in ("weight", "weight_scale"):
+                    if src + name in sd:
+                        self._ckpt[dst + name] = kernels.mxfp4_bytes(sd[src + name], src + name).to(self.device)
+        self.gate_up = self.down = self.gate_up_scale = self.down_scale = None
+
+    def verify_loaded_weights(self) -> None:
+        if self.gate_up is not None:
+            return
+        for e in range(self.n_experts):
+            for w in ("w1", "w2", "w3"):
+                for name in ("weight", "weight_scale"):
+                    assert f"experts.{e}.{w}.{name}" in self._ckpt, f"experts.{e}.{w}.{name} is not loaded"
+
+    def repack(self) -> None:
+        self.verify_loaded_weights()
+        c = self._ckpt
+        H, I, B = self.hidden, self.intermediate, kernels.MXFP4_BLOCK
+        for e in range(self.n_experts):
+            for w, rows, k in (("w1", I, H), ("w3", I, H), ("w2", H, I)):
+                if tuple(c[f"experts.{e}.{w}.weight"].shape) != (rows, k // 2) or \
+                        tuple(c[f"experts.{e}.{w}.weight_scale"].shape) != (rows, k // B):
+                    raise SlmError(f"experts.{e}.{w}: weight must be [{rows}, {k // 2}] bytes and weight_scale "
+                                   f"[{rows}, {k // B}] (hidden = {H}, intermediate = {I})")
+        E = range(self.n_experts)
+        cat = lambda e, name: torch.cat([c[f"experts.{e}.w1.{name}"], c[f"experts.{e}.w3.{name}"]], dim=0)  # noqa: E731
+        self.gate_up = torch.stack([cat(e, "weight") for e in E]).contiguous()
+        self.gate_up_scale = torch.stack([cat(e, "weight_scale") for e in E]).contiguous()
+        self.down = torch.stack([c[f"experts.{e}.w2.weight"] for e in E]).contiguous()
+        self.down_scale = torch.stack([c[f"experts.{e}.w2.weight_scale"] for e in E]).contiguous()
+        self._ckpt = {}
+
+    def nbytes(self) -> int:
+        return self.gate_up.numel() + self.down.numel() + self.gate_up_scale.numel() + self.down_scale.numel()
+
+    def gemm(self, which: str, a, c, *aligned, **epilogue) -> None:
+        """the grouped GEMM over `which` = "gate_up" | "down"; the arguments after c are the kernel's"""
+        kernels.moe_mxfp4_grouped_gemm(a, getattr(self, which), getattr(self, which + "_scale"), c, *aligned,
+                                       **epilogue)
+
+
 def _make_experts(hidden: int, intermediate: int, n_experts: int, quant_args: Optional[QuantArgs], dtype, device,
                   expert_offset: int = 0):
-    """The experts holder a QuantArgs selects: None -> unquantised, "fp8" -> MoEFp8Experts, else int4."""
-    if quant_args is None or quant_args.quant_method == "fp8":
-        if quant_args is not None and quant_args.bits != 8:
+    """The experts holder a QuantArgs selects: None -> unquantised, "fp8" -> MoEFp8Experts, "mxfp4" ->
+    MoEMxfp4Experts, else int4."""
+    if quant_args is None or quant_args.quant_method in ("fp8", "mxfp4"):
+        if quant_args is not None and quant_args.quant_method == "fp8" and quant_args.bits != 8:
             raise SlmError(f"quant_method 'fp8' means 8-bit weights, got bits = {quant_args.bits}")
+        if quant_args is not None and quant_args.quant_method == "mxfp4" and quant_args.bits != 4:
+            raise SlmError(f"quant_method 'mxfp4' means 4-bit weights, got bits = {quant_args.bits}")
         if hidden % 32 or intermediate % 32:
             raise SlmError("hidden and intermediate must be multiples of 32 (K and N of the two grouped GEMMs)")
-        cls = MoEDenseExperts if quant_args is None else MoEFp8Experts
+        cls = MoEDenseExperts if quant_args is None else \
+            MoEFp8Experts if quant_args.quant_method == "fp8" else MoEMxfp4Experts
         return cls(hidden, intermediate, n_experts, dtype, device, expert_offset)
     if hidden % 128 or intermediate % 128:
         raise SlmError("hidden and intermediate must be multiples of 128 (K of the two grouped GEMMs)")
@@ -251,9 +321,10 @@ def _make_experts(hidden: int, intermediate: int, n_experts: int, quant_args: Op
 
 class FusedMoE:
     """Sparse FFN block: a router (`gate`, an unquantised [E, hidden] weight) over n_experts SwiGLU experts: int4
-    (AWQ / GPTQ) with a QuantArgs, fp8 (e4m3 weights, f16 / bf16 activations) with QuantArgs("fp8", 8) -- its other
-    fields are ignored --, unquantised f16 / bf16 with quant_args=None.  Each experts class runs its own grouped GEMM
-    (experts.gemm); the forward pass is the same six launches for all three.
+    (AWQ / GPTQ) with a QuantArgs, fp8 (e4m3 weights, f16 / bf16 activations) with QuantArgs("fp8", 8), OCP MXFP4
+    (e2m1 nibbles + e8m0 block scales, f16 / bf16 activations) with QuantArgs("mxfp4", 4) -- the other fields of
+    these two are ignored --, unquantised f16 / bf16 with quant_args=None.  Each experts class runs its own grouped
+    GEMM (experts.gemm); the forward pass is the same six launches for all four.
 
     scoring = "softmax": top-k of the softmax (renormalize = Mixtral's rule: the k weights divided by their sum);
     scoring = "grouped_sigmoid": sigmoid scores with a correction bias, group-limited top-k (n_expert_groups,
@@ -528,7 +599,8 @@ class AlltoAllTokenDispatcher(_TokenDispatcher):
 class ExpertParallelMoE:
     """FusedMoE's block with the experts sharded over an expert-parallel group: every rank routes its own tokens
     (the router weight is replicated), AlltoAllTokenDispatcher.dispatch_topk sends each (token, expert) row to the
-    expert's rank, the two grouped GEMMs run over this rank's experts [rank * L, (rank + 1) * L), and combine
+    expert's rank, the two grouped GEMMs run over this rank's experts [rank * L, (rank + 1) * L) (any of FusedMoE's
+    expert sides: quant_args as there, QuantArgs("mxfp4", 4) included), and combine
     brings the rows home and takes the weighted sum.  Rounding points: after SiLU * mul, after the down GEMM (the
     rows travel in T), after the weighted sum (fp32, one rounding) -- the weights are applied at the source rank,
     not on the down GEMM's accumulator as in FusedMoE.  Not capturable (the dispatcher's copy of the counts)."""

@@ -15,8 +15,9 @@ heads, eps = rms_norm_eps), and with n_experts > 0 the MLP replaced by Qwen3-MoE
     residual + the next layer's input norm (or the final norm)                   kernels.rms_norm(residual=)
   lm_head (the embedding itself when tie_word_embeddings) -> argmax, or the fused sampling kernel
 
-quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16) or "awq" (int4), as
-MixtralDecodeStep.  head_dim must be one the QK-norm kernel takes (64, 128, 256).
+quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16), "mxfp4" (OCP MXFP4,
+W4A16: the attention projections and the dense MLP on layers.{Column,Row}ParallelMxfp4Linear, the experts on
+moe.MoEMxfp4Experts) or "awq" (int4), as MixtralDecodeStep.  head_dim must be one the QK-norm kernel takes (64, 128, 256).
 
 Out of scope, refused: world_size > 1, a custom all-reduce.  Not offered: two lanes, a C++ host step,
 mlp_only_layers / decoder_sparse_step (with n_experts > 0 every layer is sparse), sliding-window layers, Gemma-3's
@@ -32,8 +33,9 @@ import torch
 
 from . import kernels
 from .decode import _rand_int4_linear
-from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelQLinear, HipAttnHandler,
-                     InputParameters, KVCache, QuantArgs, RowParallelFp8Linear, RowParallelLinear, RowParallelQLinear)
+from .layers import (Attention, ColumnParallelFp8Linear, ColumnParallelLinear, ColumnParallelMxfp4Linear,
+                     ColumnParallelQLinear, HipAttnHandler, InputParameters, KVCache, QuantArgs, RowParallelFp8Linear,
+                     RowParallelLinear, RowParallelMxfp4Linear, RowParallelQLinear)
 from .model_parallel import ParallelArgs
 from .moe import FusedMoE
 
@@ -91,8 +93,8 @@ class Qwen3DecodeStep:
         pa = parallel_args or ParallelArgs()
         if pa.world_size > 1 or custom_allreduce is not None:
             raise ValueError("Qwen3DecodeStep runs on one rank: tensor parallelism is out of scope")
-        if quant_method not in ("none", "fp8", "awq"):
-            raise ValueError(f"quant_method must be 'none', 'fp8' or 'awq', not {quant_method!r}")
+        if quant_method not in ("none", "fp8", "awq", "mxfp4"):
+            raise ValueError(f"quant_method must be 'none', 'fp8', 'awq' or 'mxfp4', not {quant_method!r}")
         if shape.head_dim not in (64, 128, 256):
             raise ValueError(f"head_dim {shape.head_dim}: the QK-norm prologue takes 64, 128 or 256")
         if record_routing and not shape.n_experts:
@@ -113,7 +115,7 @@ class Qwen3DecodeStep:
         inv_freq = 1.0 / (shape.rope_theta ** (torch.arange(0, D, 2, dtype=torch.float32, device=dev) / D))
         self.cos_sin = HipAttnHandler.build_cos_sin(D, shape.max_position, inv_freq)
         nq, nkv = shape.n_heads * D, shape.n_kv_heads * D
-        qa = {"none": None, "fp8": QuantArgs("fp8", 8),
+        qa = {"none": None, "fp8": QuantArgs("fp8", 8), "mxfp4": QuantArgs("mxfp4", 4),
               "awq": QuantArgs(quant_method="awq", bits=4, group_size=group_size, zero_point=True)}[quant_method]
         draw = lambda n, kk: (torch.randn(n, kk, device=dev, generator=gen) * 0.02).to(dtype)  # noqa: E731
         norm_w = lambda n=H: (1 + 0.05 * torch.randn(n, device=dev, generator=gen)).to(dtype)  # noqa: E731
@@ -137,6 +139,7 @@ class Qwen3DecodeStep:
                     L[name]._repack()
                     continue
                 Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if quant_method == "fp8" else \
+                    (ColumnParallelMxfp4Linear, RowParallelMxfp4Linear) if quant_method == "mxfp4" else \
                     (ColumnParallelLinear, RowParallelLinear)
                 L[name] = Col(K, N, False, False, pa, dtype, dev, act_mul=act) if col else \
                     Row(K, N, False, True, pa, dtype, dev)
@@ -145,6 +148,10 @@ class Qwen3DecodeStep:
                     w8, sc = kernels.quantize_fp8_weight(w)
                     ck[name] = {"weight": w8, "weight_scale": sc}
                     L[name].load_shard(w8, sc)
+                elif quant_method == "mxfp4":   # the same checkpoint quantised to MXFP4, under the Quark names
+                    w4, sc = kernels.quantize_mxfp4_weight(w)
+                    ck[name] = {"weight": w4, "weight_scale": sc}
+                    L[name].load_state_dict(ck[name])
                 else:
                     ck[name] = {"weight": w}
                     L[name].load_shard(w)
@@ -159,6 +166,8 @@ class Qwen3DecodeStep:
                                 sd[p + tn] = t
                         elif quant_method == "fp8":
                             sd[p + "weight"], sd[p + "weight_scale"] = kernels.quantize_fp8_weight(draw(N, K))
+                        elif quant_method == "mxfp4":
+                            sd[p + "weight"], sd[p + "weight_scale"] = kernels.quantize_mxfp4_weight(draw(N, K))
                         else:
                             sd[p + "weight"] = draw(N, K)
                 L["moe"] = FusedMoE(H, inter, E, k, qa, scoring="softmax", renormalize=shape.norm_topk_prob,

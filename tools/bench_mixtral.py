@@ -3,6 +3,7 @@ Everything is captured once in a hipGraph and replayed `--iters` times between d
 every figure is the median of `--repeats` such windows, listed with their spread (max - min).
 
     python tools/bench_mixtral.py [--out profiles/r19_mixtral.jsonl] [--iters 200] [--repeats 5] [--parts router,layer,step]
+    python tools/bench_mixtral.py --parts step --quants fp8,mxfp4      # the step rows of profiles/r23_moe_mxfp4.jsonl
 
   router  kernels.moe_router alone against the captured composition it replaces (x.float() @ gate_f32_t, then the
           section 10 routing kernel): Mixtral rows (E 8, hidden 4096, softmax top 2) and DeepSeek-V3-like rows (E 256,
@@ -11,8 +12,8 @@ every figure is the median of `--repeats` such windows, listed with their spread
   layer   FusedMoE(router="fused") against router="torch" at the Mixtral-8x7B layer (hidden 4096, intermediate 14336,
           E 8, k 2) for the three experts classes, T = 1 / 32 / 256, over a pool of inputs (the routing changes from
           replay to replay).
-  step    MixtralDecodeStep at the 8x7B shape cut to 8 of its 32 layers, kv 4096, batch 1 and 32, per quant_method,
-          with the fused router and with the layers' router switched to "torch".
+  step    MixtralDecodeStep at the 8x7B shape cut to 8 of its 32 layers, kv 4096, batch 1 and 32, per quant_method
+          (--quants, default none,fp8,awq), with the fused router and with the layers' router switched to "torch".
 """
 import argparse
 import dataclasses
@@ -151,7 +152,7 @@ def part_step(args, dev):
     lines = []
     shape = dataclasses.replace(MixtralShape.mixtral_8x7b(), n_layers=8)
     kv_len, block = 4096, 16
-    for quant in ("none", "fp8", "awq"):
+    for quant in args.quants.split(","):
         step = None
         for bs in (1, 32):
             tokens, positions, params, n_blocks = make_decode_inputs(bs, kv_len, block, dev, seed=bs, vocab=shape.vocab)
@@ -190,6 +191,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--pool", type=int, default=16)
     ap.add_argument("--parts", default="router,layer,step")
+    ap.add_argument("--quants", default="none,fp8,awq", help="the step part's quant_method list")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mixtral needs a GPU: there is no CPU path to time")

@@ -4,6 +4,7 @@ loop over the experts: per-expert slm_w4a16_gemm calls for int4 experts, torch.m
     python tools/bench_moe.py [--out profiles/r09_moe.jsonl] [--tokens 1,32,256] [--iters 200]
     python tools/bench_moe.py --dense [--out profiles/r12_moe_dense.jsonl]
     python tools/bench_moe.py --fp8 [--out profiles/r18_moe_fp8.jsonl]
+    python tools/bench_moe.py --mxfp4 [--out profiles/r23_moe_mxfp4.jsonl]
 
 hidden 4096, intermediate 14336, E = 8, k = 2, AWQ group 128, bf16 (random weights: 705 MB packed).  One JSON
 line per T:
@@ -32,6 +33,15 @@ experts streamed).  Both forwards are captured in graphs and replayed over the i
 windows of `iters` replays; one JSON line per T with fp8_us / dense_us (the medians; every window is listed),
 touched_bytes / streamed_bytes / frac_7tbs over the fp8 bytes (weights + scales), the dense layer's own
 dense_frac_7tbs, and fp8_vs_dense_rel_err (different rounding of nothing but the accumulator's scale multiply).
+
+--mxfp4: the same layer over OCP MXFP4 experts (FusedMoE(QuantArgs("mxfp4", 4)), slm_moe_mxfp4_gemm; 0.75 GB of nibbles
+and scale bytes): the bf16 checkpoint of --dense quantised by kernels.quantize_mxfp4_weight, and beside it, in the same
+process, the fp8 layer of --fp8 over the same bf16 checkpoint and the dense bf16 layer over the dequantised MXFP4
+weights (bit-identical output, asserted).  All three forwards are captured and replayed over the input pool in
+`--rounds` alternating windows of `iters` replays; one JSON line per T with mxfp4_us / fp8_us / dense_us (the medians;
+every window is listed, *_spread = (max - min) / median of the windows), touched_bytes / streamed_bytes / frac_7tbs
+over the MXFP4 bytes (nibbles + scale bytes), and the other two layers' own fractions.  The three layers share the
+router weights and the inputs, so they route alike and stream the same experts.
 """
 import argparse
 import json
@@ -163,6 +173,80 @@ def _main_fp8(args, dev, tokens):
     return lines
 
 
+def _mxfp4_fp8_and_dense_layers(max_tokens, dev, sides=("mxfp4", "fp8", "dense")):
+    """the --dense checkpoint as MXFP4, as fp8 (per output channel), and the dense layer over the dequantised MXFP4;
+    `sides`: which of the three to build (tools/ab_moe_mxfp4_ring.py takes the first alone)"""
+    g = torch.Generator(device=dev).manual_seed(0)
+    sd4, sd8, sd16 = {}, {}, {}
+    for e in range(NE):
+        for w, (N, K) in (("w1", (INTER, HID)), ("w3", (INTER, HID)), ("w2", (HID, INTER))):
+            key = f"experts.{e}.{w}."
+            full = (torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+            sd4[key + "weight"], sd4[key + "weight_scale"] = kernels.quantize_mxfp4_weight(full)
+            if "fp8" in sides:
+                sd8[key + "weight"], sd8[key + "weight_scale"] = kernels.quantize_fp8_weight(full, "channel")
+            if "dense" in sides:
+                sd16[key + "weight"] = kernels.dequantize_mxfp4_weight(sd4[key + "weight"], sd4[key + "weight_scale"],
+                                                                       torch.bfloat16)
+            del full
+    gate = (torch.randn(NE, HID, device=dev, generator=g) * 0.05).to(torch.bfloat16)
+    layers = []
+    for side, sd, q in (("mxfp4", sd4, QuantArgs("mxfp4", 4)), ("fp8", sd8, QuantArgs("fp8", 8)), ("dense", sd16, None)):
+        if side not in sides:
+            continue
+        sd["gate.weight"] = gate
+        layer = moe.FusedMoE(HID, INTER, NE, TOPK, quant_args=q, scoring="softmax", renormalize=True,
+                             max_tokens=max_tokens, dtype=torch.bfloat16, device=dev)
+        layer.load_state_dict(sd)
+        sd.clear()
+        layer(torch.zeros(1, HID, device=dev, dtype=torch.bfloat16))   # stack + buffers
+        layers.append(layer)
+    return layers
+
+
+def _main_mxfp4(args, dev, tokens):
+    mx4, fp8, dense = _mxfp4_fp8_and_dense_layers(max(tokens), dev)
+    mx_bytes, fp8_bytes, dense_bytes = (l.experts.nbytes() // NE for l in (mx4, fp8, dense))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    spread = lambda t: round((max(t) - min(t)) / med(t), 4)  # noqa: E731
+    lines = []
+    for T in tokens:
+        g = torch.Generator(device=dev).manual_seed(T)
+        pool = [torch.randn(T, HID, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(args.pool)]
+        run4, y4 = _captured(mx4, pool, T, dev)
+        run8, y8 = _captured(fp8, pool, T, dev)
+        run16, y16 = _captured(dense, pool, T, dev)
+        assert torch.equal(y4, y16), "the MXFP4 layer differs from the dense layer on the dequantised experts"
+        rel8 = float((y8.float() - y16.float()).abs().mean() / y16.float().abs().mean())
+        t4, t8, t16 = [], [], []
+        for _ in range(args.rounds):                    # alternating windows: drift hits all columns alike
+            t4.append(_time(run4, args.iters))
+            t8.append(_time(run8, args.iters))
+            t16.append(_time(run16, args.iters))
+        mx_us, fp8_us, dense_us = med(t4), med(t8), med(t16)
+        routed = [_routing(mx4, x)[1] for x in pool]
+        used = [int(ids.unique().numel()) for ids in routed]
+        blocks = [int(((torch.bincount(ids.reshape(-1), minlength=NE) + 31) // 32).sum()) for ids in routed]
+        n_used, n_blocks = sum(used) / len(used), sum(blocks) / len(blocks)
+        frac = lambda nbytes, us: round(nbytes * n_used / (us * 1e-6) / READ_CEILING, 4)  # noqa: E731
+        line = dict(bench="moe_mixtral_8x7b_mxfp4_bf16", T=T, topk=TOPK, n_experts=NE,
+                    mxfp4_us=round(mx_us, 2), fp8_us=round(fp8_us, 2), dense_us=round(dense_us, 2),
+                    mxfp4_over_fp8=round(mx_us / fp8_us, 4), mxfp4_over_dense=round(mx_us / dense_us, 4),
+                    mxfp4_us_windows=[round(t, 2) for t in t4], fp8_us_windows=[round(t, 2) for t in t8],
+                    dense_us_windows=[round(t, 2) for t in t16],
+                    mxfp4_spread=spread(t4), fp8_spread=spread(t8), dense_spread=spread(t16),
+                    experts_in_use=round(n_used, 2), row_blocks=round(n_blocks, 2),
+                    touched_bytes=int(mx_bytes * n_used), streamed_bytes=int(mx_bytes * n_blocks),
+                    frac_7tbs=frac(mx_bytes, mx_us),
+                    streamed_frac_7tbs=round(mx_bytes * n_blocks / (mx_us * 1e-6) / READ_CEILING, 4),
+                    fp8_frac_7tbs=frac(fp8_bytes, fp8_us), dense_frac_7tbs=frac(dense_bytes, dense_us),
+                    mxfp4_equals_dense_on_dequantised=True, fp8_vs_mxfp4_rel_err=round(rel8, 5),
+                    iters=args.iters, pool=args.pool, rounds=args.rounds)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def _routing(layer, x):
     logits = x.float() @ layer.gate_weight.float().t()
     w, ids = kernels.moe_topk_softmax(logits, TOPK, True)
@@ -224,16 +308,23 @@ def main():
     ap.add_argument("--dense", action="store_true", help="unquantised bf16 experts (slm_moe_gemm)")
     ap.add_argument("--fp8", action="store_true",
                     help="fp8 (e4m3) experts (slm_moe_fp8_gemm) beside the dense bf16 layer on the dequantised weights")
-    ap.add_argument("--rounds", type=int, default=3, help="--fp8: alternating timing windows per layer")
+    ap.add_argument("--mxfp4", action="store_true",
+                    help="MXFP4 experts (slm_moe_mxfp4_gemm) beside the fp8 layer and the dense bf16 layer on the "
+                         "dequantised weights")
+    ap.add_argument("--rounds", type=int, default=3, help="--fp8 / --mxfp4: alternating timing windows per layer")
     args = ap.parse_args()
-    if args.dense and args.fp8:
-        raise SystemExit("--dense and --fp8 are two modes: pick one (--fp8 measures the dense layer too)")
+    if args.dense + args.fp8 + args.mxfp4 > 1:
+        raise SystemExit("--dense, --fp8 and --mxfp4 are three modes: pick one (--fp8 and --mxfp4 measure the dense "
+                         "layer too)")
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda")
     tokens = [int(t) for t in args.tokens.split(",")]
     if args.fp8:
         _write(args.out, _main_fp8(args, dev, tokens))
+        return
+    if args.mxfp4:
+        _write(args.out, _main_mxfp4(args, dev, tokens))
         return
     if args.dense:
         layer = _dense_layer(max(tokens), dev)
