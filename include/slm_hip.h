@@ -127,7 +127,12 @@ typedef struct slm_attn_args {
                              * decode lanes) may issue the halves separately: 1 = everything BUT
                              * the combine pass, 2 = the combine pass only (a no-op when the plan needs none).
                              * Same arguments for both; phase 1 then phase 2 on one stream == phase 0. */
-  int32_t reserved;
+  int32_t n_slots;          /* slots the two caches hold (key_cache.size(0)), 0 = unknown.  The LDS-DMA prefill forms of
+                             * the tile kernel address the caches through a buffer descriptor, and the buffer unit
+                             * keeps slot * stride to 32 bits (attn_tile.hip): they are taken only when n_slots is
+                             * known and n_slots * slot stride <= 4 GiB for both caches; otherwise the rows run
+                             * on the register-staged form (64-bit addresses), whatever SLM_ATTN_TILE_PF says.
+                             * It only chooses between forms that compute the same bits. */
 } slm_attn_args;
 
 /* Scratch needed for `a` (depends only on host-side sizes; AttentionHandler::
@@ -140,6 +145,10 @@ SLM_API int32_t slm_paged_kv_varlen_mha_auto_splits(const slm_attn_args* a);
  * stream, dot2), 1 = attn_tile_kernel (MFMA tile form: wide GQA groups), -1 = invalid arguments.
  * A pure function of the argument block and the tuning table (what a bench labels its roofline with). */
 SLM_API int32_t slm_paged_kv_varlen_mha_decode_kernel(const slm_attn_args* a);
+/* whether the call may take the LDS-DMA prefill forms of the tile kernel: 1 = n_slots is given and both caches end
+ * within 4 GiB of their pointers, 0 = not (n_slots 0 or larger caches: register-staged forms), -1 = invalid
+ * arguments.  Host-side; what a test or a bench asserts so that a forgotten n_slots does not pass as a slower prefill. */
+SLM_API int32_t slm_paged_kv_varlen_mha_kv_near(const slm_attn_args* a);
 SLM_API int slm_paged_kv_varlen_mha(const slm_attn_args* a, void* stream);
 
 /* ========================================================================== */

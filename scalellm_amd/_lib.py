@@ -40,7 +40,7 @@ class AttnArgs(C.Structure):
         ("sm_scale", C.c_float), ("logits_soft_cap", C.c_float), ("sliding_window", C.c_int32),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("num_splits", C.c_int32), ("total_kv_len", C.c_int32),
-        ("phase", C.c_int32), ("reserved", C.c_int32),
+        ("phase", C.c_int32), ("n_slots", C.c_int32),
     ]
 
 
@@ -312,6 +312,8 @@ def lib() -> C.CDLL:
     L.slm_paged_kv_varlen_mha_auto_splits.argtypes = [C.POINTER(AttnArgs)]
     L.slm_paged_kv_varlen_mha_decode_kernel.restype = C.c_int32
     L.slm_paged_kv_varlen_mha_decode_kernel.argtypes = [C.POINTER(AttnArgs)]
+    L.slm_paged_kv_varlen_mha_kv_near.restype = C.c_int32
+    L.slm_paged_kv_varlen_mha_kv_near.argtypes = [C.POINTER(AttnArgs)]
     L.slm_build_step_inputs.restype = C.c_int
     L.slm_build_step_inputs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -954,6 +954,19 @@ SLM_API int32_t slm_paged_kv_varlen_mha_decode_kernel(const slm_attn_args* a) {
   return decode_on_tile(a) ? 1 : 0;
 }
 
+// the LDS-DMA tile forms reach rows within 4 GiB of the cache pointers only (attn_tile.hip): the host says how far
+// the caches go (slm_attn_args::n_slots; 0 = unknown: assume far)
+static bool attn_kv_near(const slm_attn_args* a) {
+  return a->n_slots > 0 && (int64_t)a->n_slots * a->k_stride[0] * 2 <= ((int64_t)1 << 32) &&
+         (int64_t)a->n_slots * a->v_stride[0] * 2 <= ((int64_t)1 << 32);
+}
+
+SLM_API int32_t slm_paged_kv_varlen_mha_kv_near(const slm_attn_args* a) {
+  AttnPlan pl;
+  if (plan_attn(a, &pl) != SLM_OK) return -1;
+  return attn_kv_near(a) ? 1 : 0;
+}
+
 SLM_API size_t slm_paged_kv_varlen_mha_workspace_bytes(const slm_attn_args* a) {
   AttnPlan pl;
   if (plan_attn(a, &pl) != SLM_OK) return 0;
@@ -1026,6 +1039,7 @@ SLM_API int slm_paged_kv_varlen_mha(const slm_attn_args* a, void* stream) {
     kp.o_part = reinterpret_cast<float*>(a->workspace);
     kp.ml_part = kp.o_part + (size_t)a->n_tokens * a->n_heads * pl.part_slots * a->head_dim;
   }
+  const bool kv_near = attn_kv_near(a);   // else no LDS-DMA tile form
   bool tile_used = false;
   const bool dec_tile = decode_on_tile(a);
   const int first_tile_rows = dec_tile ? kp.group : kp.group + 1;  // smallest row count on the tile kernel
@@ -1044,14 +1058,14 @@ SLM_API int slm_paged_kv_varlen_mha(const slm_attn_args* a, void* stream) {
     if (do_stream && first_tile_rows < 33 && !(uniform_q && max_rows > 32)) {  // (group >= 32: every multi-row sequence already has > 32 rows)
       tk.rows_lo = first_tile_rows;
       tk.rows_hi = 33;
-      rc = launch_attn_tile(tk, a->dtype, max_rows < 32 ? max_rows : 32, a->max_kv_len, st);
+      rc = launch_attn_tile(tk, a->dtype, max_rows < 32 ? max_rows : 32, kv_near, st);
       if (rc != SLM_OK) return rc;
     }
     if (do_stream && max_rows > 32) {
       // rows <= group (q_len = 1) stay with the token-major kernel also when group > 32 (MQA)
       tk.rows_lo = first_tile_rows > 33 ? first_tile_rows : 33;
       tk.rows_hi = 0x7fffffff;
-      rc = launch_attn_tile(tk, a->dtype, max_rows, a->max_kv_len, st);
+      rc = launch_attn_tile(tk, a->dtype, max_rows, kv_near, st);
       if (rc != SLM_OK) return rc;
     }
     // the token-major kernel keeps the q_len = 1 sequences

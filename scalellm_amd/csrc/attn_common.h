@@ -67,6 +67,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // Returns SLM_OK after launching, or SLM_ERR_UNSUPPORTED when the shape is not covered
 // (the caller then uses the token-major kernel).
 bool attn_tile_supported(int head_dim);
-int launch_attn_tile(const AttnKParams& kp, int dtype, int64_t max_rows, int64_t max_kv_len, hipStream_t st);
+// kv_near: every row of both caches ends within 4 GiB of its cache pointer (what the LDS-DMA forms can address)
+int launch_attn_tile(const AttnKParams& kp, int dtype, int64_t max_rows, bool kv_near, hipStream_t st);
 
 }  // namespace slm

@@ -74,7 +74,14 @@ typedef __attribute__((address_space(3))) tr_v4s tr_lds_v4s;
 //     image;
 //   * the cache slots of a tile's 64 rows are looked up ONCE per workgroup (64 threads, one row each, two
 //     tiles ahead) and handed round through LDS, instead of by every thread for its own rows.
-// Needs slot strides < 16 KiB (the descriptor's 14-bit stride field); the launcher falls back otherwise.
+// Needs slot strides < 16 KiB (the descriptor's 14-bit stride field) and caches of at most 4 GiB; the launcher
+// falls back to the register-staged form (64-bit addresses) otherwise.  The second limit was MEASURED on gfx950
+// (tests/test_far_attn_gpu.py): the buffer unit keeps index * stride + offset to 32 bits -- rows up to byte offset
+// 2^32 - 1 arrive (neither the 2^31 mark nor num_records 0x7fffffff is a limit), a row at 2^32 + x silently reads
+// the row at x, nothing is zero-filled.  The host knows how far a cache goes only from slm_attn_args::n_slots
+// (0 = unknown counts as far).  Per-lane 64-bit addresses for global_load_lds_dwordx4 instead of the descriptor
+// were built and dropped: 2 ... 8 more VGPRs, spills in the bf16 head_dim-128 pipelined forms, prefill 2 ... 17 %
+// slower, and the KV2 form then failed test_tile_kernel_two_wave_groups_per_query_tile (docs/EXPERIMENTS.md).
 // PIPE (round 5, on the DMA form): the wave is software-pipelined ACROSS tiles -- two score blocks live:
 //     A(t): S' = K[t+1] . Q^T  (16 MFMAs at head_dim 128)   ||   P = exp2(S * c - m), l += sum P   (tile t)
 //     B(t): O += V[t]^T . P    (16 MFMAs)                    ||   row max of S', lazy-rescale decision for t + 1
@@ -824,7 +831,7 @@ __global__ void __launch_bounds__(64 * NW * (KV2 ? 2 : 1)) __attribute__((amdgpu
 bool attn_tile_supported(int head_dim) { return head_dim == 64 || head_dim == 128; }
 
 // rows = largest q_len * group this launch has to cover (query rows per (sequence, kv head))
-int launch_attn_tile(const AttnKParams& kp, int dtype, int64_t rows, int64_t max_kv_len, hipStream_t st) {
+int launch_attn_tile(const AttnKParams& kp, int dtype, int64_t rows, bool kv_near, hipStream_t st) {
   if (!attn_tile_supported(kp.head_dim)) return SLM_ERR_UNSUPPORTED;
   if (rows < 1) return SLM_ERR_UNSUPPORTED;
   int nw = (int)((rows + 31) / 32);
@@ -848,9 +855,9 @@ int launch_attn_tile(const AttnKParams& kp, int dtype, int64_t rows, int64_t max
   // the same) -- and wins where the 4-wave grid leaves CUs empty: one 256-token chunk over an 8 k history 65 -> 58 us.
   // Automatic only there (fewer workgroups than CUs); SLM_ATTN_TILE_KV2: 1 = always where the form exists, 0 = never.
   const int kv2_mode = tune_get(TUNE_ATTN_TILE_KV2, -1);
-  (void)max_kv_len;
   const bool kv2 = kv2_mode > 0 || (kv2_mode < 0 && grid <= 256);
-  const bool dma = pf_mode != 4 && 2 * kp.k_ss < 16384 && 2 * kp.v_ss < 16384 && 2 * kp.k_ss > 0 && 2 * kp.v_ss > 0;
+  // ... and every row within 4 GiB of the cache pointer: the buffer unit keeps index * stride to 32 bits (header)
+  const bool dma = kv_near && pf_mode != 4 && 2 * kp.k_ss < 16384 && 2 * kp.v_ss < 16384 && 2 * kp.k_ss > 0 && 2 * kp.v_ss > 0;
 #define SLM_TILE(TT, HDD, NWW)                                                                    \
   do {                                                                                            \
     if (pf && plain) hipLaunchKernelGGL((attn_tile_kernel<TT, HDD, NWW, true, true>), g, blk, 0, st, kp, (int)tiles_per_seq); \

@@ -1,5 +1,7 @@
 // slm_llama_hip.cpp -- see slm_llama_hip.h.  Host code only (g++): every device operation is a call
 // into the layer classes of this directory or straight into the C ABI (include/slm_hip.h).
+#include <algorithm>
+#include <cstdint>
 #include "slm_llama_hip.h"
 
 #include <ATen/hip/HIPEvent.h>
@@ -368,6 +370,7 @@ void LlamaForCausalLMHip::attn(Lane& ln, size_t li, std::vector<KVCache>& kv, in
   a.sm_scale = handler_->sm_scale(); a.logits_soft_cap = handler_->logits_soft_cap();
   a.sliding_window = -1;
   a.total_kv_len = p.kv_total_len > 0 && p.kv_total_len < (int64_t(1) << 31) ? static_cast<int32_t>(p.kv_total_len) : 0;
+  a.n_slots = static_cast<int32_t>(std::min<int64_t>(std::max(kc.size(0), vc.size(0)), INT32_MAX));
   a.phase = phase;  // (1 / 2: the two lanes hand the KV-stream token on between the stream kernel and the combine pass)
   if (a.n_tokens == 0 || a.batch_size == 0) return;
   const size_t need = slm_paged_kv_varlen_mha_workspace_bytes(&a);

@@ -1,5 +1,7 @@
 // slm_torch_shim.cpp -- see slm_torch_shim.h.  Pure host code (g++), no device code: tensors are
 // unpacked to (pointer, strides, sizes) and handed to the C ABI on torch's current HIP stream.
+#include <algorithm>
+#include <cstdint>
 #include "slm_torch_shim.h"
 
 // torch-ROCm tensors carry DeviceType "cuda" (HIP masquerades as CUDA), so the guard / stream
@@ -111,6 +113,7 @@ void paged_kv_varlen_mha(torch::Tensor& out, const torch::Tensor& query,
   a.logits_soft_cap = logits_soft_cap;
   a.sliding_window = sliding_window;
   a.num_splits = 0;
+  a.n_slots = static_cast<int32_t>(std::min<int64_t>(std::max(key_cache.size(0), value_cache.size(0)), INT32_MAX));
   if (a.n_tokens == 0 || a.batch_size == 0) return;
   // The reference's signature (attn_api.h:12-27) has no total-length argument and its engine fills none: what the
   // SIZES it hands over settle is derived here -- a pure-decode batch whose flattened block table holds exactly

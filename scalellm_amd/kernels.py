@@ -255,6 +255,7 @@ def _attn_args(out, query, key_cache, value_cache, q_cu_lens, kv_cu_lens, block_
     a.sliding_window = int(sliding_window)
     a.num_splits = int(num_splits)
     a.workspace, a.workspace_bytes = None, 0
+    a.n_slots = min(max(key_cache.size(0), value_cache.size(0)), 2 ** 31 - 1)   # block-table entries are int32
     return a
 
 

@@ -208,6 +208,7 @@ def attn_args(c):
     a.max_kv_len = c.max_kv_hint if c.max_kv_hint is not None else max(c.kv_lens)
     a.sm_scale, a.logits_soft_cap, a.sliding_window = AX.sm_scale_of(c), c.softcap, c.window
     a.num_splits = c.num_splits
+    a.n_slots = AX.layout(c).n_slots
     a.workspace, a.workspace_bytes = None, 0
     return a
 

@@ -107,6 +107,9 @@ class _Call:
         else:
             ma = kernels._attn_args(*a)
             need = L.slm_paged_kv_varlen_mha_workspace_bytes(C.byref(ma))
+            # kernels._attn_args passes the slot count: caches within 4 GiB keep the LDS-DMA prefill forms
+            near = self.k.size(0) * self.k.stride(0) * 2 <= 2 ** 32
+            assert ma.n_slots == self.k.size(0) and L.slm_paged_kv_varlen_mha_kv_near(C.byref(ma)) == int(near), case.name
             if case.splits is not None:
                 assert L.slm_paged_kv_varlen_mha_auto_splits(C.byref(ma)) == case.splits, case.name
             if case.name.startswith("dec_"):
