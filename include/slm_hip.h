@@ -1719,6 +1719,79 @@ typedef struct slm_moe_mxfp4_gemm_args {
 SLM_API int slm_moe_mxfp4_gemm
     (const slm_moe_mxfp4_gemm_args* a, void* stream);
 
+/* ========================================================================== */
+/* 22. MXFP4 x MXFP4 linear (W4A4) on the block-scaled MFMA                   */
+/*    Section 20's checkpoint weights against activations that are MXFP4 as   */
+/*    well -- the arithmetic Quark's MXFP4 exports with dynamic MXFP4         */
+/*    activations are calibrated in:                                          */
+/*      a[m, k] = e2m1(Aq[m, k]) * 2^(ea[m, k / 32] - 127)                    */
+/*      w[n, k] = e2m1(W[n, k])  * 2^(ew[n, k / 32] - 127)                    */
+/*      C[m, n] = T( sum_k a[m, k] * w[n, k] + bias[n] )      ONE rounding    */
+/*    v_mfma_scale_f32_32x32x64_f8f6f4 takes the e2m1 codes as they lie in    */
+/*    memory (one MX block per lane) and the e8m0 bytes as per-lane scale     */
+/*    operands: no converts, nothing multiplied onto the accumulator.  Every  */
+/*    product is exact; the sum is the instruction's fp32 sum (exact where    */
+/*    the partial sums are representable: tests/test_w4a4_exact_gpu.py).      */
+/*    Scale bytes: e = 255 (the MX NaN) on either operand poisons its row /   */
+/*    column; everything else is a power of two, no range of exactness to     */
+/*    mind (there is no conversion to T before the sum).                      */
+/*    Activation quantiser (slm_w4a4_quantize_act; csrc/w4a4_quant.h): the    */
+/*    rule of kernels.quantize_mxfp4_weight.  Per block of 32 consecutive k,  */
+/*    e = clamp(floor(log2 amax) - 2 + 127, 1, 254), an all-zero block 127,   */
+/*    a block holding inf or NaN 255; elements x * 2^(127 - e) rounded to     */
+/*    nearest even onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturated at 6; a byte's */
+/*    low nibble is the lower k; a value that rounds to zero keeps its sign   */
+/*    bit (code 8 = -0).  The hardware converter                              */
+/*    (v_cvt_scalef32_pk_fp4_{bf16,f16}) was measured against this rule on    */
+/*    an MI355X over all 65536 patterns of both types: no difference, so it   */
+/*    does the elements; amax and e are integer work on the bit patterns.     */
+/*    One lane owns one block, ONE launch, no workspace, capturable.          */
+/*    A [M, K] T row stride lda (elements, % 8), Aq [M, K/2] bytes row stride */
+/*    ldaq (bytes, % 16), a_scale [M, K/32] bytes row stride ldas (any), K %  */
+/*    32 == 0; bases of A and Aq 16-byte aligned.                             */
+/*    The GEMM has two activation sides behind one kernel:                    */
+/*      a_scale != NULL  pre-quantised: a = Aq, lda in BYTES (>= K/2, % 16),  */
+/*                       a_scale / ldas (>= K/32, no alignment) as above      */
+/*      a_scale == NULL  T: a = A [M, K] T, lda in elements (>= K, % 8); the  */
+/*                       kernel quantises each block as it loads it, with the */
+/*                       quantiser's own arithmetic: bit-identical to the     */
+/*                       quantiser followed by the pre-quantised side under   */
+/*                       the same form, and no extra launch.                  */
+/*    W, w_scale, ldw, lds, bias, C, ldc, shapes (K % 32 == 0, N % 32 == 0,   */
+/*    N % 64 with SLM_LINEAR_SILU_MUL), flags (SLM_LINEAR_*), error codes,    */
+/*    "all validation before any launch", M == 0 (SLM_OK without a launch),   */
+/*    the K slices and the workspace ([split_k][M][N] fp32 slabs: the reduce  */
+/*    launch and every deferred consumer of section 13 work unchanged) are    */
+/*    section 20's.  The plan is section 13's function of (M, N, K, dtype,    */
+/*    flags, bias) under knobs of its own: SLM_W4A4_SPLITK / _RT / _NW; it is */
+/*    reported through slm_linear_plan_info (lds_bytes: 2 * 32 * row_tiles *  */
+/*    68), whose workspace_bytes is the size to pass: there is no workspace   */
+/*    query of its own.  Launch shape, block order, tail: csrc/w4a4.hip.      */
+/* ========================================================================== */
+typedef struct slm_w4a4_linear_args {
+  const void* a;        /* T side: [M, K] T, row stride lda (elements); pre-quantised: [M, K/2] bytes, lda in bytes */
+  const void* w;        /* [N, K/2] bytes of two e2m1 codes, row stride ldw (bytes) */
+  const void* bias;     /* [N] T or NULL                                      */
+  void* c;              /* [M, N] T ([M, N/2] with SLM_LINEAR_SILU_MUL), row stride ldc */
+  int64_t M, K, N;
+  int64_t lda, ldw, ldc;
+  int32_t dtype;        /* of bias and c (and of a on the T side)             */
+  int32_t flags;        /* SLM_LINEAR_* bits, 0 = none                        */
+  void* workspace;      /* split-K slabs                                      */
+  size_t workspace_bytes;
+  const uint8_t* w_scale; /* [N, K/32] e8m0 bytes, required                    */
+  int64_t lds;          /* row stride of w_scale in bytes, >= K/32; everything above is slm_mxfp4_linear_args */
+  const uint8_t* a_scale; /* [M, K/32] e8m0 bytes: the pre-quantised side; NULL: the T side */
+  int64_t ldas;         /* row stride of a_scale in bytes, >= K/32            */
+} slm_w4a4_linear_args;
+
+SLM_API int slm_w4a4_quantize_act(const void* a, int64_t lda, void* aq, int64_t ldaq, uint8_t* a_scale, int64_t ldas,
+                                  int64_t M, int64_t K, int32_t dtype, void* stream);
+/* As slm_linear_plan / _deferred_splits / slm_linear (section 13); the plan is a pure host function. */
+SLM_API int slm_w4a4_linear_plan(const slm_w4a4_linear_args* a, slm_linear_plan_info* out);
+SLM_API int32_t slm_w4a4_linear_deferred_splits(const slm_w4a4_linear_args* a);
+SLM_API int slm_w4a4_linear(const slm_w4a4_linear_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

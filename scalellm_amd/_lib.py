@@ -259,6 +259,12 @@ class Mxfp4LinearArgs(C.Structure):
     _fields_ = LinearArgs._fields_ + [("w_scale", C.c_void_p), ("lds", C.c_int64)]
 
 
+class W4A4LinearArgs(C.Structure):
+    """struct slm_w4a4_linear_args (include/slm_hip.h section 22): slm_mxfp4_linear_args, field for field, plus the
+    activations' e8m0 block scales (NULL: the T side) and their row stride."""
+    _fields_ = Mxfp4LinearArgs._fields_ + [("a_scale", C.c_void_p), ("ldas", C.c_int64)]
+
+
 class LinearPlanInfo(C.Structure):
     """struct slm_linear_plan_info (include/slm_hip.h section 13)."""
     _fields_ = [
@@ -443,6 +449,12 @@ def lib() -> C.CDLL:
         ("slm_mxfp4_linear_deferred_splits", C.c_int32, [C.POINTER(Mxfp4LinearArgs)]),
         ("slm_mxfp4_linear_plan", C.c_int, [C.POINTER(Mxfp4LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_mxfp4_gemm", C.c_int, [C.POINTER(MoeMxfp4GemmArgs), C.c_void_p]),
+        ("slm_w4a4_quantize_act", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+          C.c_void_p]),
+        ("slm_w4a4_linear", C.c_int, [C.POINTER(W4A4LinearArgs), C.c_void_p]),
+        ("slm_w4a4_linear_deferred_splits", C.c_int32, [C.POINTER(W4A4LinearArgs)]),
+        ("slm_w4a4_linear_plan", C.c_int, [C.POINTER(W4A4LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

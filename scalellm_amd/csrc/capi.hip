@@ -23,6 +23,7 @@ const char* const kTuneNames[TUNE_COUNT] = {
     "SLM_W4_M128_CT",       "SLM_ATTN_TILE_KV2",    "SLM_W4_XL_MODEL",      "SLM_W4_M128_ADMA",
     "SLM_W4_XL_SK",
     "SLM_LINEAR_SPLITK",    "SLM_LINEAR_RT",        "SLM_LINEAR_NW",
+    "SLM_W4A4_SPLITK",      "SLM_W4A4_RT",          "SLM_W4A4_NW",
 };
 std::atomic<int32_t> g_tune[TUNE_COUNT];
 std::once_flag g_tune_once;

@@ -1,6 +1,7 @@
 // dense_plan.h -- the launch plan of dense.hip's three entries (slm_linear, slm_fp8_linear, slm_mxfp4_linear;
 // include/slm_hip.h sections 13, 15 and 20), over any of the argument structs: slm_fp8_linear_args and
-// slm_mxfp4_linear_args are slm_linear_args, field for field, plus their scales.  Host only.
+// slm_mxfp4_linear_args are slm_linear_args, field for field, plus their scales.  w4a4.hip (section 22) takes the same
+// plan under knobs of its own.  Host only.
 #pragma once
 #include "common.h"
 #include "tuning.h"
@@ -20,7 +21,8 @@ struct LinearPlan {
 };
 
 template <typename Args>
-inline int plan_linear(const Args* a, LinearPlan* pl) {
+inline int plan_linear(const Args* a, LinearPlan* pl, TuneKey rt_key = TUNE_LINEAR_RT, TuneKey nw_key = TUNE_LINEAR_NW,
+                       TuneKey splitk_key = TUNE_LINEAR_SPLITK) {
   if (!a) return SLM_ERR_INVALID_ARG;
   if (a->M < 0 || a->K <= 0 || a->N <= 0) return SLM_ERR_INVALID_ARG;
   if (a->dtype != SLM_F16 && a->dtype != SLM_BF16) return SLM_ERR_UNSUPPORTED;
@@ -33,7 +35,7 @@ inline int plan_linear(const Args* a, LinearPlan* pl) {
 
   // row tiles per wave: the fewest of 1 / 2 / 4 that hold all rows (at most 128 per row block)
   int rt = a->M <= 32 ? 1 : a->M <= 64 ? 2 : 4;
-  const int rt_knob = tune_get(TUNE_LINEAR_RT, 0);
+  const int rt_knob = tune_get(rt_key, 0);
   if (rt_knob == 1 || rt_knob == 2 || rt_knob == 4) rt = rt_knob;
   const int64_t rows = 32 * rt;
   const int64_t row_blocks = a->M > 0 ? (a->M + rows - 1) / rows : 1;
@@ -49,7 +51,7 @@ inline int plan_linear(const Args* a, LinearPlan* pl) {
   const int narrowest = rt > (silu ? 2 : 1) ? rt : (silu ? 2 : 1);
   int nw = narrowest;
   while (nw < 4 && row_blocks * gemm_col_groups(n_tiles, nw, silu) > 2 * MI355X_CUS) nw <<= 1;
-  const int nw_knob = tune_get(TUNE_LINEAR_NW, 0);
+  const int nw_knob = tune_get(nw_key, 0);
   if (nw_knob == 1 || nw_knob == 2 || nw_knob == 4) nw = nw_knob > narrowest ? nw_knob : narrowest;
   const int64_t col_groups = gemm_col_groups(n_tiles, nw, silu);
   if (col_groups >= ((int64_t)1 << 31)) return SLM_ERR_UNSUPPORTED;
@@ -60,7 +62,7 @@ inline int plan_linear(const Args* a, LinearPlan* pl) {
     const int64_t by_grid = MI355X_CUS / (row_blocks * col_groups);
     split = (int)(by_grid < by_depth ? by_grid : by_depth);
     if (split < 1) split = 1;
-    const int sk_knob = tune_get(TUNE_LINEAR_SPLITK, 0);
+    const int sk_knob = tune_get(splitk_key, 0);
     if (sk_knob >= 1) {
       const int cap = n_chunks < 1 ? 1 : n_chunks < LIN_MAX_SPLIT ? n_chunks : LIN_MAX_SPLIT;
       split = sk_knob < cap ? sk_knob : cap;

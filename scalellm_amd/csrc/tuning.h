@@ -50,6 +50,9 @@ enum TuneKey : int {
   TUNE_LINEAR_SPLITK,     // SLM_LINEAR_SPLITK     forced K slices of the dense linear (1..16; every slice keeps >= 1 chunk)
   TUNE_LINEAR_RT,         // SLM_LINEAR_RT         forced 32-row accumulator tiles per wave of the dense linear (1/2/4)
   TUNE_LINEAR_NW,         // SLM_LINEAR_NW         forced waves per workgroup of the dense linear (1/2/4; raised to the row tiles)
+  TUNE_W4A4_SPLITK,       // SLM_W4A4_SPLITK       forced K slices of the MXFP4 x MXFP4 linear (1..16; every slice keeps >= 1 chunk)
+  TUNE_W4A4_RT,           // SLM_W4A4_RT           forced 32-row accumulator tiles per wave of the MXFP4 x MXFP4 linear (1/2/4)
+  TUNE_W4A4_NW,           // SLM_W4A4_NW           forced waves per workgroup of the MXFP4 x MXFP4 linear (1/2/4; raised to the row tiles)
   TUNE_COUNT
 };
 

@@ -1,0 +1,85 @@
+// w4a4_quant.h -- the MXFP4 activation quantiser's arithmetic (include/slm_hip.h section 22): 32 consecutive k of T
+// (one MX block, 64 bytes, four 16-B loads of ONE lane) -> 16 bytes of e2m1 codes + one e8m0 byte.  Shared by the
+// stand-alone quantiser and by the GEMM's T side (w4a4.hip), which therefore give the same bits.
+//
+// The rule is kernels.quantize_mxfp4_weight's:
+//   e = clamp(floor(log2 amax) - 2 + 127, 1, 254); an all-zero block 127; a block holding inf or NaN 255
+//   code = e2m1( RNE(x * 2^(127 - e)) saturated at 6 ), a byte's low nibble the lower k
+//  * amax and e are INTEGER work on the 16-bit patterns (|x| = pattern & 0x7fff orders like the value): packed u16
+//    maxima over the block's 16 dwords, then the exponent field.  bf16: field E -> e = max(E - 2, 1) (a subnormal
+//    amax, E = 0, is below 2^-126: the low clamp; E <= 254 gives e <= 252: the high clamp is never reached).  f16:
+//    field E > 0 -> e = E + 110; a subnormal amax = mant * 2^-24 -> e = msb(mant) + 101; so e is in [101, 140].
+//    One lane owns the block: no cross-lane step.
+//  * the elements go through v_cvt_scalef32_pk_fp4_{bf16,f16} with the scale operand 2^(e - 127): it DIVIDES by the
+//    scale, two elements per instruction, element 0 (the low half of the source dword = the lower k) into the low
+//    nibble of the selected byte.  Measured on an MI355X over all 65536 patterns of both types at scales 2^-5, 1 and 4
+//    against the rule: round to nearest even onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturation at 6 (inf included), the sign
+//    bit kept (a value that rounds to zero keeps its sign: code 8, which the rule allows) -- no difference, so
+//    nothing is redone in VALU.  A NaN element gives code 7; its block's e is 255 anyway.
+#pragma once
+#include <type_traits>
+
+#include "common.h"
+
+namespace slm {
+
+typedef uint16_t u16x2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t,
+                            __builtin_elementwise_max(__builtin_bit_cast(u16x2_t, a), __builtin_bit_cast(u16x2_t, b)));
+}
+
+// the e8m0 byte of a block whose largest |pattern| is m (15 bits)
+template <typename T>
+__device__ __forceinline__ uint32_t act_block_e8m0(uint32_t m);
+template <>
+__device__ __forceinline__ uint32_t act_block_e8m0<bf16_tag>(uint32_t m) {
+  const int E = (int)(m >> 7);
+  const int e = E - 2 > 1 ? E - 2 : 1;
+  return m == 0 ? 127u : E == 255 ? 255u : (uint32_t)e;
+}
+template <>
+__device__ __forceinline__ uint32_t act_block_e8m0<f16_tag>(uint32_t m) {
+  const uint32_t E = m >> 10;
+  const uint32_t sub = 132u - (uint32_t)__builtin_clz(m | 1u);  // msb(mant) + 101 = (31 - clz) + 101
+  return m == 0 ? 127u : E == 31 ? 255u : E > 0 ? E + 110u : sub;
+}
+
+// two T (one dword) / scale -> byte B of `old`
+template <typename T, int B>
+__device__ __forceinline__ uint32_t t2_to_fp4(uint32_t old, uint32_t pair, float scale) {
+  if constexpr (std::is_same<T, bf16_tag>::value)
+    return __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(old, __builtin_bit_cast(bf16x2_t, pair), scale, B);
+  else
+    return __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(old, __builtin_bit_cast(f16x2_t, pair), scale, B);
+}
+
+// one MX block: x[q] holds k = 8 q .. 8 q + 7 of the block.  Returns the 16 code bytes, e8m0 byte in `e8`
+template <typename T>
+__device__ __forceinline__ u32x4 quantize_act_block(const u32x4 (&x)[4], uint32_t& e8) {
+  uint32_t mx = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    mx = pk_max_u16(mx, x[q].x & 0x7fff7fffu);
+    mx = pk_max_u16(mx, x[q].y & 0x7fff7fffu);
+    mx = pk_max_u16(mx, x[q].z & 0x7fff7fffu);
+    mx = pk_max_u16(mx, x[q].w & 0x7fff7fffu);
+  }
+  const uint32_t m = (mx & 0xffffu) > (mx >> 16) ? (mx & 0xffffu) : (mx >> 16);
+  e8 = act_block_e8m0<T>(m);
+  const float scale = __builtin_bit_cast(float, e8 << 23);  // 2^(e - 127); e = 255: inf, the codes mean nothing
+  u32x4 r;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    uint32_t d = 0;
+    d = t2_to_fp4<T, 0>(d, x[q].x, scale);
+    d = t2_to_fp4<T, 1>(d, x[q].y, scale);
+    d = t2_to_fp4<T, 2>(d, x[q].z, scale);
+    d = t2_to_fp4<T, 3>(d, x[q].w, scale);
+    r[q] = d;
+  }
+  return r;
+}
+
+}  // namespace slm

@@ -175,8 +175,14 @@ class LlamaDecodeStep:
                  parallel_args: Optional[ParallelArgs] = None, quant_method: str = "awq",
                  group_size: int = 128, dtype=torch.bfloat16, device="cuda", seed: int = 0,
                  kv_fill: str = "none", custom_allreduce=None, keep_checkpoint: bool = False,
-                 gptq_sym: bool = False, fuse_silu: bool = True, desc_act: bool = False, bits: int = 4):
+                 gptq_sym: bool = False, fuse_silu: bool = True, desc_act: bool = False, bits: int = 4,
+                 act_quant: Optional[str] = None):
         pa = parallel_args or ParallelArgs()
+        # act_quant "mxfp4" (with quant_method "mxfp4" only): the four linears quantise their activations to MXFP4 as
+        # they load them and run the block-scaled MFMA (kernels.w4a4_linear): W4A4, no launch more than W4A16
+        if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
+            raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
+        self.act_quant = act_quant
         # quant_method "none": unquantised weights [N, K] of `dtype` (randn * 0.02 from the common seed), the four
         # linears are layers.{Column,Row}ParallelLinear over slm_linear; everything else of the step is shared
         # quant_method "fp8": that same checkpoint quantised per output channel to e4m3 (kernels.quantize_fp8_weight),
@@ -322,10 +328,11 @@ class LlamaDecodeStep:
         Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if self.fp8 else \
             (ColumnParallelMxfp4Linear, RowParallelMxfp4Linear) if self.mxfp4 else \
             (ColumnParallelLinear, RowParallelLinear)
-        L["qkv"] = Col(H, qkv_n * tp, False, False, pa, dtype, dev)
-        L["o"] = Row(q_full, H, False, True, pa, dtype, dev)
-        L["gate_up"] = Col(H, 2 * inter, False, False, pa, dtype, dev, act_mul="silu" if fuse_silu else None)
-        L["down"] = Row(inter, H, False, True, pa, dtype, dev)
+        aq = {"act_quant": self.act_quant} if self.act_quant else {}
+        L["qkv"] = Col(H, qkv_n * tp, False, False, pa, dtype, dev, **aq)
+        L["o"] = Row(q_full, H, False, True, pa, dtype, dev, **aq)
+        L["gate_up"] = Col(H, 2 * inter, False, False, pa, dtype, dev, act_mul="silu" if fuse_silu else None, **aq)
+        L["down"] = Row(inter, H, False, True, pa, dtype, dev, **aq)
         qkv_rows = [(r * nh * D, (r + 1) * nh * D), (q_full + kv_head0 * D, q_full + (kv_head0 + nkv) * D),
                     (q_full + kv_full + kv_head0 * D, q_full + kv_full + (kv_head0 + nkv) * D)]
         gu_rows = [(r * inter // tp, (r + 1) * inter // tp), (inter + r * inter // tp, inter + (r + 1) * inter // tp)]

@@ -887,14 +887,15 @@ def linear_plan(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Op
 
 
 def _run_linear(entry: str, g, dev: torch.device, defer_reduce: bool) -> DeferredPartials:
-    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear / slm_mxfp4_linear (`entry`) over the
+    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear / slm_mxfp4_linear / slm_w4a4_linear
+    (`entry`) over the
     argument block g"""
     L = _lib.lib()
     if g.M == 0:
         return DeferredPartials()
     deferred = getattr(L, entry + "_deferred_splits")(C.byref(g)) if defer_reduce else 0
-    # (section 20 declares no _workspace_bytes query: the plan carries the size)
-    need = _linear_plan(entry, g).workspace_bytes if entry == "slm_mxfp4_linear" else \
+    # (sections 20 and 22 declare no _workspace_bytes query: the plan carries the size)
+    need = _linear_plan(entry, g).workspace_bytes if entry in ("slm_mxfp4_linear", "slm_w4a4_linear") else \
         getattr(L, entry + "_workspace_bytes")(C.byref(g))
     ws = None
     if need:
@@ -1084,6 +1085,75 @@ def mxfp4_linear(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: tor
     linear()."""
     return _run_linear("slm_mxfp4_linear", _mxfp4_args(a, w, w_scale, c, bias, defer_reduce, silu_mul), a.device,
                        defer_reduce)
+
+
+# ---------------------------------------------------------------------------------------
+# MXFP4 x MXFP4 linear on the block-scaled MFMA (W4A4): slm_hip.h section 22
+# ---------------------------------------------------------------------------------------
+def quantize_mxfp4_act(a: torch.Tensor, aq: Optional[torch.Tensor] = None, a_scale: Optional[torch.Tensor] = None):
+    """Dynamic MXFP4 quantisation of activations A [M, K] (f16 / bf16, K % 32 == 0, rows contiguous) on the GPU, one
+    launch: (aq uint8 [M, K/2], a_scale uint8 [M, K/32]) under quantize_mxfp4_weight's rule (shared exponent
+    floor(log2 amax) - 2, round to nearest even, saturation at 6, low nibble = lower k); a block holding inf or NaN
+    gets the scale byte 255 and a value that rounds to zero may keep its sign bit (code 8).  `aq` / `a_scale` may be
+    given (row strides: a multiple of 16 / any)."""
+    _require_gpu(a, aq, a_scale)
+    if a.dim() != 2 or a.stride(1) != 1 or a.size(1) % MXFP4_BLOCK:
+        raise SlmError("quantize_mxfp4_act takes A [M, K] with contiguous rows and K % 32 == 0")
+    M, K = a.shape
+    if aq is None:
+        aq = torch.empty(M, K // 2, dtype=torch.uint8, device=a.device)
+    if a_scale is None:
+        a_scale = torch.empty(M, K // MXFP4_BLOCK, dtype=torch.uint8, device=a.device)
+    for t, cols, what in ((aq, K // 2, "aq"), (a_scale, K // MXFP4_BLOCK, "a_scale")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (M, cols) or t.stride(1) != 1:
+            raise SlmError(f"{what} must be uint8 [{M}, {cols}] with contiguous rows")
+    check(_lib.lib().slm_w4a4_quantize_act(a.data_ptr(), a.stride(0), aq.data_ptr(), aq.stride(0), a_scale.data_ptr(),
+                                           a_scale.stride(0), M, K, _dtype_code(a), _stream()), "slm_w4a4_quantize_act")
+    return aq, a_scale
+
+
+def _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce: bool, silu_mul: bool):
+    """Checks and argument block of w4a4_linear() and its plan query: the mxfp4_linear block (over T activations, or
+    with a_scale over their code bytes) plus the activations' block scales"""
+    if a_scale is None:
+        g0 = _mxfp4_args(a, w, w_scale, c, bias, defer_reduce, silu_mul)
+    else:
+        _require_gpu(a, a_scale)
+        if a.dtype != torch.uint8 or a_scale.dtype != torch.uint8 or a.dim() != 2 or a_scale.dim() != 2 or \
+                a.stride(1) != 1 or a_scale.stride(1) != 1 or \
+                tuple(a_scale.shape) != (a.size(0), 2 * a.size(1) // MXFP4_BLOCK):
+            raise SlmError("pre-quantised activations are uint8 [M, K/2] with uint8 scales [M, K/32], contiguous rows")
+        # (the shape checks of _mxfp4_args run over a [M, K] view of `c`'s dtype: only its sizes are read)
+        g0 = _mxfp4_args(c.new_empty(1, 2 * a.size(1)).expand(a.size(0), -1), w, w_scale, c, bias, defer_reduce, silu_mul)
+    g = _lib.W4A4LinearArgs()
+    for name, _ in _lib.Mxfp4LinearArgs._fields_:
+        setattr(g, name, getattr(g0, name))
+    if a_scale is not None:
+        g.a, g.lda = a.data_ptr(), a.stride(0)
+        g.a_scale, g.ldas = a_scale.data_ptr(), a_scale.stride(0)
+    else:
+        g.a_scale, g.ldas = None, 0
+    return g
+
+
+def w4a4_linear_plan(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
+                     bias: Optional[torch.Tensor] = None, defer_reduce: bool = False, silu_mul: bool = False,
+                     a_scale: Optional[torch.Tensor] = None) -> "_lib.LinearPlanInfo":
+    """The launch w4a4_linear() would give these very arguments now (slm_w4a4_linear_plan, under the SLM_W4A4_*
+    knobs); a host-side query."""
+    return _linear_plan("slm_w4a4_linear", _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce, silu_mul))
+
+
+def w4a4_linear(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, silu_mul: bool = False, defer_reduce: bool = False,
+                a_scale: Optional[torch.Tensor] = None) -> DeferredPartials:
+    """MXFP4 x MXFP4 linear on the block-scaled MFMA: C[M, N] = T(sum_k a[m, k] w[n, k] + bias), a and w the
+    dequantised values of two MXFP4 tensors, fp32 accumulate, one rounding.  `w` / `w_scale` are mxfp4_linear's
+    checkpoint tensors.  Activations: `a` in f16 / bf16 [M, K], quantised by the kernel as it loads them (a_scale
+    None) -- or the quantize_mxfp4_act pair, `a` uint8 [M, K/2] with `a_scale` uint8 [M, K/32]; the two give the same
+    bits.  defer_reduce, silu_mul and the returned handle: as linear()."""
+    return _run_linear("slm_w4a4_linear", _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce, silu_mul),
+                       c.device, defer_reduce)
 
 
 # ---------------------------------------------------------------------------------------

@@ -705,9 +705,20 @@ class _Mxfp4LinearMixin:
     [N, K/2] (a byte's low nibble is the lower k) -- or the same bytes as [N, K/32, 16] (gpt-oss `*_blocks`) or
     torch.float4_e2m1fn_x2 -- and `weight_scale` its e8m0 bytes, uint8 or torch.float8_e8m0fnu [N, K/32]; both are
     kept as bytes and streamed as they are (kernels.mxfp4_linear).  A weight of any other dtype is an error --
-    quantising is the checkpoint's job (kernels.quantize_mxfp4_weight), not a side effect of loading."""
+    quantising is the checkpoint's job (kernels.quantize_mxfp4_weight), not a side effect of loading.
+
+    act_quant=None is W4A16 (kernels.mxfp4_linear).  act_quant="mxfp4" quantises the activations to MXFP4 as they are
+    loaded, dynamically per block of 32 k, and runs the block-scaled MFMA (kernels.w4a4_linear, its T side: the same
+    single launch) -- the arithmetic of checkpoints calibrated with MXFP4 activations."""
 
     weight_scale: Optional[torch.Tensor] = None
+    act_quant: Optional[str] = None
+
+    def __init__(self, *args, act_quant: Optional[str] = None, **kw):
+        if act_quant not in (None, "mxfp4"):
+            raise ValueError(f"act_quant must be None or 'mxfp4', not {act_quant!r}")
+        super().__init__(*args, **kw)
+        self.act_quant = act_quant
 
     def _set(self, name: str, t: torch.Tensor) -> None:
         if name == "weight":
@@ -753,8 +764,9 @@ class _Mxfp4LinearMixin:
         n_out = self.local_out // 2 if self.paired else self.local_out
         if out is None:
             out = torch.empty(x2.size(0), n_out, dtype=x.dtype, device=x.device)
-        self.deferred = kernels.mxfp4_linear(x2, self.weight, self.weight_scale, out, bias,
-                                             defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
+        run = kernels.w4a4_linear if self.act_quant == "mxfp4" else kernels.mxfp4_linear
+        self.deferred = run(x2, self.weight, self.weight_scale, out, bias,
+                            defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
         self.deferred_splits = int(self.deferred)
         return out
 
@@ -804,8 +816,10 @@ class RowParallelMxfp4Linear(_Mxfp4LinearMixin, RowParallelLinear):
     belongs to 32 k of its row), so the K shard must be a multiple of 32.  With world_size > 1: GEMM, all-reduce,
     then the bias."""
 
-    def __init__(self, in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device):
-        super().__init__(in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device)
+    def __init__(self, in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device,
+                 act_quant: Optional[str] = None):
+        super().__init__(in_features, out_features, bias, input_is_parallelized, parallel_args, dtype, device,
+                         act_quant=act_quant)
         if self.local_in % 32:
             raise ValueError(f"mxfp4 row-parallel linear: the K shard {self.local_in} (in_features {in_features} / "
                              f"world_size {parallel_args.world_size}) must be a multiple of the MX block, 32")
