@@ -1792,6 +1792,74 @@ SLM_API int slm_w4a4_linear_plan(const slm_w4a4_linear_args* a, slm_linear_plan_
 SLM_API int32_t slm_w4a4_linear_deferred_splits(const slm_w4a4_linear_args* a);
 SLM_API int slm_w4a4_linear(const slm_w4a4_linear_args* a, void* stream);
 
+/* ========================================================================== */
+/* 23. MXFP4 x MXFP4 mixture-of-experts: grouped W4A4 GEMM                    */
+/*    slm_moe_mxfp4_gemm (section 21) in section 22's arithmetic.  For every  */
+/*    32-row block b of the aligned token list, e = expert_ids[b], idx =      */
+/*    sorted[b * 32 + r]:                                                     */
+/*      a[m, k]   = e2m1(Aq[m, k])   * 2^(ea[m, k / 32] - 127)                */
+/*      w_e[n, k] = e2m1(W_e[n, k])  * 2^(s_e[n, k / 32] - 127)               */
+/*      C[idx, n] = T( (sum_k a[idx / a_div, k] * w_e[n, k]) * row_scale[idx])*/
+/*    ONE rounding.  The experts are section 21's tensors and rules exactly   */
+/*    (w, w_scale, ldw, lds, both expert strides in bytes; code strides % 16, */
+/*    scale strides without alignment; no byte outside an expert's own rows   */
+/*    is read).  The activations are PRE-QUANTISED only: a is [n_flat /       */
+/*    a_div, K/2] code bytes, row stride lda in BYTES (>= K/2, % 16, base     */
+/*    16-byte aligned), a_scale [.., K/32] e8m0 bytes, row stride ldas (>=    */
+/*    K/32, no alignment), required: slm_w4a4_quantize_act's output, made     */
+/*    once per token (the rule is per row, so it commutes with the gather).   */
+/*    One wave computes one 32 x 32 tile over the whole K with section 22's   */
+/*    MFMA sequence at split_k = 1: an expert's rows are slm_w4a4_linear      */
+/*    (pre-quantised side, SLM_W4A4_SPLITK = 1) on those rows bit for bit,    */
+/*    for every launch shape.                                                 */
+/*    flags: 0; SLM_MOE_SILU_MUL (section 21's: the bits of the plain call    */
+/*    followed by slm_silu_mul; not with row_scale); SLM_MOE_SILU_MUL |       */
+/*    SLM_MOE_QUANT_OUT: the SiLU * mul output is not stored in T but as the  */
+/*    next GEMM's MXFP4 input -- c is [n_flat, N/4] code BYTES with ldc in    */
+/*    bytes (>= N/4, % 16, base 16-byte aligned), c_scale [n_flat, N/64]      */
+/*    e8m0 bytes with row stride ldcs (>= N/64, any): byte for byte           */
+/*    slm_w4a4_quantize_act run on the SLM_MOE_SILU_MUL output (one 32 x 32   */
+/*    output tile is one MX block per row).  SLM_MOE_QUANT_OUT without        */
+/*    SLM_MOE_SILU_MUL, or with row_scale: SLM_ERR_INVALID_ARG.               */
+/*    T outputs are stored 8 bytes at a time: c 8-byte aligned, ldc % 4 == 0  */
+/*    (SLM_ERR_ALIGNMENT).  The aligned-list contract, dead blocks, padding   */
+/*    rows (never stored), the launch shape (from max_blocks, N and flags     */
+/*    alone; no split-K, no workspace, no atomics), the shapes (K % 32 == 0,  */
+/*    N % 32 == 0, (N/2) % 32 == 0 with SILU_MUL), the error codes, "all      */
+/*    validation before any launch" and the no-op (n_flat == 0 or             */
+/*    max_blocks == 0) are section 21's (csrc/w4a4_moe.hip).                  */
+/* ========================================================================== */
+#define SLM_MOE_QUANT_OUT 4         /* slm_moe_w4a4_gemm only, with SLM_MOE_SILU_MUL: c is MXFP4    */
+typedef struct slm_moe_w4a4_gemm_args {
+  const void* a;                    /* [n_flat / a_div, K/2] bytes of two e2m1 codes, row stride lda (BYTES) */
+  const void* w;                    /* expert 0: [N, K/2] bytes of two e2m1 codes, row stride ldw (bytes) */
+  const uint8_t* w_scale;           /* expert 0: [N, K/32] e8m0 bytes, row stride lds (bytes); required */
+  void* c;                          /* [n_flat, N] T (SILU_MUL: [n_flat, N/2]; QUANT_OUT: [n_flat, N/4] bytes) */
+  const float* row_scale;           /* [n_flat] fp32 or NULL                                      */
+  const int32_t* sorted_token_idxes;
+  const int32_t* expert_ids;
+  const int32_t* n_padded_tokens;   /* [1], read on the device                                    */
+  int64_t w_expert_stride;          /* bytes between experts, >= (N - 1) * ldw + K/2              */
+  int64_t w_scale_expert_stride;    /* bytes between experts' scales, >= (N - 1) * lds + K/32     */
+  int64_t n_flat;                   /* rows of c = T * k; the padding id                          */
+  int64_t K, N;
+  int64_t lda, ldw, ldc;            /* lda bytes; ldc elements of T, bytes with QUANT_OUT         */
+  int32_t a_div;                    /* >= 1                                                       */
+  int32_t n_experts;
+  int32_t max_blocks;               /* sizes the grid: slm_moe_align_capacity(n_flat, E, 32)      */
+  int32_t dtype;                    /* of c (and of the quantiser the QUANT_OUT bytes equal)      */
+  int32_t flags;                    /* 0, SLM_MOE_SILU_MUL, or SLM_MOE_SILU_MUL | SLM_MOE_QUANT_OUT */
+  int64_t lds;                      /* row stride of w_scale in bytes, >= K/32; everything above is
+                                       slm_moe_mxfp4_gemm_args, field for field                   */
+  const uint8_t* a_scale;           /* [n_flat / a_div, K/32] e8m0 bytes; required                */
+  int64_t ldas;                     /* row stride of a_scale in bytes, >= K/32                    */
+  uint8_t* c_scale;                 /* QUANT_OUT: [n_flat, N/64] e8m0 bytes                       */
+  int64_t ldcs;                     /* row stride of c_scale in bytes, >= N/64                    */
+} slm_moe_w4a4_gemm_args;
+/* (the parameter list on its own line, as section 21's; tests/test_moe_w4a4_cpu.py covers this entry) */
+SLM_API int slm_moe_w4a4_gemm
+    (const slm_moe_w4a4_gemm_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,13 @@ class MoeMxfp4GemmArgs(C.Structure):
     _fields_ = MoeFp8GemmArgs._fields_ + [("lds", C.c_int64)]
 
 
+class MoeW4A4GemmArgs(C.Structure):
+    """struct slm_moe_w4a4_gemm_args (include/slm_hip.h section 23): slm_moe_mxfp4_gemm_args, field for field (a: code
+    bytes, lda in bytes), plus the activations' e8m0 block scales and the quantised output's scale bytes."""
+    _fields_ = MoeMxfp4GemmArgs._fields_ + [("a_scale", C.c_void_p), ("ldas", C.c_int64),
+                                            ("c_scale", C.c_void_p), ("ldcs", C.c_int64)]
+
+
 class MoeRouterArgs(C.Structure):
     """struct slm_moe_router_args (include/slm_hip.h section 17)."""
     _fields_ = [
@@ -285,6 +292,7 @@ SLM_LINEAR_SILU_MUL = 2
 SLM_LINEAR_SHARES_CHIP = 4
 
 SLM_MOE_SILU_MUL = 2    # slm_moe_gemm flags
+SLM_MOE_QUANT_OUT = 4   # slm_moe_w4a4_gemm only, with SLM_MOE_SILU_MUL: the output as MXFP4 codes + scale bytes
 SLM_MOE_GEMM_BLOCK = 32  # rows per block of the grouped GEMM: the align step's block_size
 
 
@@ -449,6 +457,7 @@ def lib() -> C.CDLL:
         ("slm_mxfp4_linear_deferred_splits", C.c_int32, [C.POINTER(Mxfp4LinearArgs)]),
         ("slm_mxfp4_linear_plan", C.c_int, [C.POINTER(Mxfp4LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_mxfp4_gemm", C.c_int, [C.POINTER(MoeMxfp4GemmArgs), C.c_void_p]),
+        ("slm_moe_w4a4_gemm", C.c_int, [C.POINTER(MoeW4A4GemmArgs), C.c_void_p]),
         ("slm_w4a4_quantize_act", C.c_int,
          [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
           C.c_void_p]),

@@ -10,6 +10,7 @@
 //   slm::moe_grouped_gemm      that dense fp16 / bf16 grouped GEMM over W[e, n, k].
 //   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm.hip).
 //   slm::moe_mxfp4_grouped_gemm  the same over OCP MXFP4 experts with e8m0 block scales (section 21, csrc/moe_gemm.hip).
+//   slm::moe_w4a4_grouped_gemm   MXFP4 experts against MXFP4 activations, W4A4 (section 23, csrc/w4a4_moe.hip).
 //   slm::moe_router            the fused router: gate GEMM + routing in one launch (section 17, csrc/moe_router.hip).
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
@@ -93,6 +94,17 @@ void moe_mxfp4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& w, cons
                             torch::Tensor& c, const torch::Tensor& sorted_token_idxes,
                             const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
                             const torch::Tensor& row_scale, bool silu_mul);
+
+// moe_mxfp4_grouped_gemm against MXFP4 activations on the block-scaled MFMA (include/slm_hip.h section 23,
+// csrc/w4a4_moe.hip): a uint8 [rows, K/2] (row stride a multiple of 16) and a_scale uint8 [rows, K/32], the pair the
+// activation quantiser writes.  c is T [n_flat, N] ([n_flat, N/2] with silu_mul) -- or, with c_scale defined (needs
+// silu_mul, no row_scale): the SiLU * mul output as the next GEMM's input, c uint8 [n_flat, N/4] and c_scale uint8
+// [n_flat, N/64], rounded to quant_dtype (kHalf / kBFloat16) before it is quantised.
+void moe_w4a4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& a_scale, const torch::Tensor& w,
+                           const torch::Tensor& w_scale, torch::Tensor& c, const torch::Tensor& sorted_token_idxes,
+                           const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
+                           const torch::Tensor& row_scale, bool silu_mul, const torch::Tensor& c_scale,
+                           torch::ScalarType quant_dtype);
 
 // logits = x [T, hidden] . gate_weight [E, hidden]^T in fp32 and their routing, in one launch: scoring "softmax"
 // (renormalize) or "grouped_sigmoid" (correction_bias, n_expert_groups, topk_group, scaling_factor); topk is

@@ -1,6 +1,7 @@
 // w4a4_quant.h -- the MXFP4 activation quantiser's arithmetic (include/slm_hip.h section 22): 32 consecutive k of T
 // (one MX block, 64 bytes, four 16-B loads of ONE lane) -> 16 bytes of e2m1 codes + one e8m0 byte.  Shared by the
-// stand-alone quantiser and by the GEMM's T side (w4a4.hip), which therefore give the same bits.
+// stand-alone quantiser, by the GEMM's T side (w4a4.hip) and by the grouped GEMM's quantising SiLU * mul epilogue
+// (w4a4_moe.hip), which therefore give the same bits.
 //
 // The rule is kernels.quantize_mxfp4_weight's:
 //   e = clamp(floor(log2 amax) - 2 + 127, 1, 254); an all-zero block 127; a block holding inf or NaN 255
@@ -55,30 +56,43 @@ __device__ __forceinline__ uint32_t t2_to_fp4(uint32_t old, uint32_t pair, float
     return __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(old, __builtin_bit_cast(f16x2_t, pair), scale, B);
 }
 
+// The two halves of the rule, for callers whose block does not sit in one lane's four 16-B loads (the quantising
+// epilogue of w4a4_moe.hip holds a row's block in two lanes).
+// amax: packed u16 maxima of |pattern| over 8 elements (four dwords) joined to `mx`; act_amax15 folds the two halves
+__device__ __forceinline__ uint32_t act_amax_pk(uint32_t mx, const u32x4 x) {
+  mx = pk_max_u16(mx, x.x & 0x7fff7fffu);
+  mx = pk_max_u16(mx, x.y & 0x7fff7fffu);
+  mx = pk_max_u16(mx, x.z & 0x7fff7fffu);
+  mx = pk_max_u16(mx, x.w & 0x7fff7fffu);
+  return mx;
+}
+__device__ __forceinline__ uint32_t act_amax15(uint32_t mx) {
+  return (mx & 0xffffu) > (mx >> 16) ? (mx & 0xffffu) : (mx >> 16);
+}
+// 2^(e - 127), the converter's scale operand; e = 255: inf, the codes mean nothing
+__device__ __forceinline__ float act_cvt_scale(uint32_t e8) { return __builtin_bit_cast(float, e8 << 23); }
+// convert: 8 consecutive k (four dwords of T pairs) / scale -> one dword of codes
+template <typename T>
+__device__ __forceinline__ uint32_t act_cvt8(const u32x4 x, float scale) {
+  uint32_t d = 0;
+  d = t2_to_fp4<T, 0>(d, x.x, scale);
+  d = t2_to_fp4<T, 1>(d, x.y, scale);
+  d = t2_to_fp4<T, 2>(d, x.z, scale);
+  d = t2_to_fp4<T, 3>(d, x.w, scale);
+  return d;
+}
+
 // one MX block: x[q] holds k = 8 q .. 8 q + 7 of the block.  Returns the 16 code bytes, e8m0 byte in `e8`
 template <typename T>
 __device__ __forceinline__ u32x4 quantize_act_block(const u32x4 (&x)[4], uint32_t& e8) {
   uint32_t mx = 0;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    mx = pk_max_u16(mx, x[q].x & 0x7fff7fffu);
-    mx = pk_max_u16(mx, x[q].y & 0x7fff7fffu);
-    mx = pk_max_u16(mx, x[q].z & 0x7fff7fffu);
-    mx = pk_max_u16(mx, x[q].w & 0x7fff7fffu);
-  }
-  const uint32_t m = (mx & 0xffffu) > (mx >> 16) ? (mx & 0xffffu) : (mx >> 16);
-  e8 = act_block_e8m0<T>(m);
-  const float scale = __builtin_bit_cast(float, e8 << 23);  // 2^(e - 127); e = 255: inf, the codes mean nothing
+  for (int q = 0; q < 4; ++q) mx = act_amax_pk(mx, x[q]);
+  e8 = act_block_e8m0<T>(act_amax15(mx));
+  const float scale = act_cvt_scale(e8);
   u32x4 r;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    uint32_t d = 0;
-    d = t2_to_fp4<T, 0>(d, x[q].x, scale);
-    d = t2_to_fp4<T, 1>(d, x[q].y, scale);
-    d = t2_to_fp4<T, 2>(d, x[q].z, scale);
-    d = t2_to_fp4<T, 3>(d, x[q].w, scale);
-    r[q] = d;
-  }
+  for (int q = 0; q < 4; ++q) r[q] = act_cvt8<T>(x[q], scale);
   return r;
 }
 

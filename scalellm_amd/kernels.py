@@ -2098,6 +2098,69 @@ def moe_mxfp4_grouped_gemm(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tens
     check(_lib.lib().slm_moe_mxfp4_gemm(C.byref(g), _stream()), "slm_moe_mxfp4_gemm")
 
 
+def moe_w4a4_grouped_gemm(a: torch.Tensor, a_scale: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor,
+                          c: torch.Tensor, sorted_token_idxes: torch.Tensor, expert_ids: torch.Tensor,
+                          n_padded_tokens: torch.Tensor, a_div: int, row_scale: Optional[torch.Tensor] = None,
+                          silu_mul: bool = False, c_scale: Optional[torch.Tensor] = None,
+                          dtype: Optional[torch.dtype] = None) -> None:
+    """moe_mxfp4_grouped_gemm with MXFP4 activations on the block-scaled MFMA (slm_hip.h section 23): `a` uint8
+    [rows, K/2] and `a_scale` uint8 [rows, K/32] are quantize_mxfp4_act's pair (row strides: a multiple of 16 / any),
+    `w` / `w_scale` the experts of moe_mxfp4_grouped_gemm (uint8 [E, N, K/2] and [E, N, K/32]).  `c` is f16 / bf16
+    [n_flat, N] ([n_flat, N/2] with silu_mul; row stride a multiple of 4) -- or, with `c_scale` (needs silu_mul): the
+    SiLU * mul output quantised as the next GEMM's input, `c` uint8 [n_flat, N/4] (row stride a multiple of 16) and
+    `c_scale` uint8 [n_flat, N/64], byte for byte quantize_mxfp4_act of the silu_mul output in `dtype` (fp16 or bf16:
+    the T the tile is rounded to before it is quantised; required with c_scale, since no tensor carries it).
+    row_scale, the aligned list and the grid: as moe_grouped_gemm."""
+    _require_gpu(a, a_scale, w, w_scale, c, c_scale, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    for t, what in ((a, "a"), (a_scale, "a_scale"), (w, "w"), (w_scale, "w_scale")):
+        if t is None or t.dtype != torch.uint8:
+            raise SlmError(f"moe_w4a4_grouped_gemm: {what} must be uint8 bytes")
+    if a.dim() != 2 or a_scale.dim() != 2 or c.dim() != 2 or a.stride(1) != 1 or a_scale.stride(1) != 1 or \
+            c.stride(1) != 1:
+        raise SlmError("A, its scales and C must be 2-D with contiguous rows")
+    if w.dim() != 3 or w.stride(2) != 1 or w_scale.dim() != 3 or w_scale.stride(2) != 1:
+        raise SlmError("expert weights must be [n_experts, N, K/2] and scales [n_experts, N, K/32], k contiguous")
+    E, N, K = w.size(0), w.size(1), 2 * w.size(2)
+    n_flat = c.size(0)
+    if K % MXFP4_BLOCK or tuple(w_scale.shape) != (E, N, K // MXFP4_BLOCK):
+        raise SlmError(f"w_scale must be [n_experts, N, K/32] = {(E, N, K // MXFP4_BLOCK)}, not {tuple(w_scale.shape)}")
+    if a.size(1) != K // 2 or tuple(a_scale.shape) != (a.size(0), K // MXFP4_BLOCK) or a_div < 1 or \
+            a.size(0) * a_div < n_flat:
+        raise SlmError("grouped GEMM shape mismatch (A is [rows, K/2] bytes with scales [rows, K/32])")
+    quant = c_scale is not None
+    if quant:
+        if not silu_mul or row_scale is not None or dtype not in (torch.float16, torch.bfloat16):
+            raise SlmError("a quantised output (c_scale) needs silu_mul=True, no row_scale and dtype = fp16 or bf16")
+        if c.dtype != torch.uint8 or c_scale.dtype != torch.uint8 or c_scale.dim() != 2 or c_scale.stride(1) != 1 or \
+                N % 64 or tuple(c.shape) != (n_flat, N // 4) or tuple(c_scale.shape) != (n_flat, N // 64):
+            raise SlmError("the quantised output is uint8 [n_flat, N/4] with scales uint8 [n_flat, N/64]")
+    elif c.dtype not in (torch.float16, torch.bfloat16) or c.size(1) != (N // 2 if silu_mul else N) or \
+            dtype not in (None, c.dtype):
+        raise SlmError("C must be fp16 or bf16 [n_flat, N] ([n_flat, N/2] with silu_mul)")
+    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
+    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
+        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
+                                  row_scale.numel() != n_flat):
+        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
+    g = _lib.MoeW4A4GemmArgs()
+    g.a, g.a_scale, g.w, g.w_scale, g.c = a.data_ptr(), a_scale.data_ptr(), w.data_ptr(), w_scale.data_ptr(), c.data_ptr()
+    g.c_scale, g.ldcs = (c_scale.data_ptr(), c_scale.stride(0)) if quant else (None, 0)
+    g.row_scale = row_scale.data_ptr() if row_scale is not None else None
+    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
+    g.n_padded_tokens = n_padded_tokens.data_ptr()
+    g.w_expert_stride = w.stride(0) if E > 1 else max(w.stride(0), N * w.stride(1))
+    g.w_scale_expert_stride = w_scale.stride(0) if E > 1 else max(w_scale.stride(0), N * w_scale.stride(1))
+    g.n_flat, g.K, g.N = n_flat, K, N
+    g.lda, g.ldas, g.ldw, g.ldc, g.lds = a.stride(0), a_scale.stride(0), w.stride(1), c.stride(0), w_scale.stride(1)
+    g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
+    g.dtype = SLM_F16 if (dtype if quant else c.dtype) == torch.float16 else SLM_BF16
+    g.flags = (_lib.SLM_MOE_SILU_MUL if silu_mul else 0) | (_lib.SLM_MOE_QUANT_OUT if quant else 0)
+    check(_lib.lib().slm_moe_w4a4_gemm(C.byref(g), _stream()), "slm_moe_w4a4_gemm")
+
+
 # ---------------------------------------------------------------------------------------
 # MoE token permutation (slm_hip.h section 14; csrc/permute.hip)
 #   permute_with_index_map / unpermute_with_index_map <- llm::kernel::moe::  (permutation_index_kernel.cu)

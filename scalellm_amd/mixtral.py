@@ -77,12 +77,18 @@ class MixtralDecodeStep:
     def __init__(self, shape: MixtralShape, max_batch_tokens: int, n_blocks: int, block_size: int,
                  parallel_args: Optional[ParallelArgs] = None, quant_method: str = "none", group_size: int = 128,
                  dtype=torch.bfloat16, device="cuda", seed: int = 0, custom_allreduce=None,
-                 keep_checkpoint: bool = False, record_routing: bool = False):
+                 keep_checkpoint: bool = False, record_routing: bool = False, act_quant: Optional[str] = None):
         pa = parallel_args or ParallelArgs()
         if pa.world_size > 1 or custom_allreduce is not None:
             raise ValueError("MixtralDecodeStep runs on one rank: tensor-parallel sharding of an expert is out of scope")
         if quant_method not in ("none", "fp8", "awq", "mxfp4"):
             raise ValueError(f"quant_method must be 'none', 'fp8', 'awq' or 'mxfp4', not {quant_method!r}")
+        # act_quant "mxfp4" (with quant_method "mxfp4" only): MXFP4 activations too (W4A4) -- the linears quantise theirs
+        # as they load them (layers.*Mxfp4Linear(act_quant=...)), the experts run FusedMoE(act_quant=...)
+        if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
+            raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
+        self.act_quant = act_quant
+        aq = {"act_quant": act_quant} if act_quant else {}
         # keep_checkpoint: retain the CHECKPOINT-format tensors (self.ckpt[layer]: "qkv", "o" as the linears take
         # them, "moe" the state dict FusedMoE.load_state_dict took) so a parity test can rebuild the model on the CPU
         self.ckpt = [] if keep_checkpoint else None
@@ -122,7 +128,8 @@ class MixtralDecodeStep:
                 Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if quant_method == "fp8" else \
                     (ColumnParallelMxfp4Linear, RowParallelMxfp4Linear) if quant_method == "mxfp4" else \
                     (ColumnParallelLinear, RowParallelLinear)
-                L[name] = Col(K, N, False, False, pa, dtype, dev) if col else Row(K, N, False, True, pa, dtype, dev)
+                L[name] = Col(K, N, False, False, pa, dtype, dev, **aq) if col else \
+                    Row(K, N, False, True, pa, dtype, dev, **aq)
                 w = draw(N, K)
                 if quant_method == "fp8":
                     w8, sc = kernels.quantize_fp8_weight(w)
@@ -150,7 +157,7 @@ class MixtralDecodeStep:
                     else:
                         sd[p + "weight"] = draw(N, K)
             L["moe"] = FusedMoE(H, inter, E, k, qa, scoring="softmax", renormalize=True, max_tokens=T, dtype=dtype,
-                                device=dev, router="fused")
+                                device=dev, router="fused", **aq)
             L["moe"].load_state_dict(sd)
             L["moe"].experts.repack()
             ck["moe"] = sd

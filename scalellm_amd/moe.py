@@ -1,6 +1,6 @@
 """Mixture-of-experts FFN over int4 (AWQ / GPTQ), fp8 (e4m3, weight-only), OCP MXFP4 (weight-only) or unquantised
 f16 / bf16 experts: routing, block alignment, two grouped GEMMs and the sum over a token's experts, every step a HIP
-kernel of libslm_hip (include/slm_hip.h sections 10, 16 and 21).
+kernel of libslm_hip (include/slm_hip.h sections 10, 16, 21 and 23).
 
     FusedMoE.forward(x):  router logits (fp32, torch: [T, hidden] x [hidden, E] is tiny)
                           -> moe_topk_softmax | moe_grouped_topk_sigmoid      (weights, expert ids)
@@ -9,6 +9,10 @@ kernel of libslm_hip (include/slm_hip.h sections 10, 16 and 21).
                           -> grouped GEMM gate_up, SiLU * mul epilogue        [T * k, intermediate]
                           -> grouped GEMM down, routing weight on the fp32 accumulator [T * k, hidden]
                           -> moe_sum                                           [T, hidden]
+
+With MXFP4 experts and act_quant="mxfp4" the activations are MXFP4 too (W4A4, section 23): x is quantised once per
+token (kernels.quantize_mxfp4_act), the gate_up GEMM's SiLU * mul epilogue writes the down GEMM's input as MXFP4
+codes and scale bytes, and both GEMMs run on the block-scaled MFMA: seven launches instead of six.
 
 All buffers are sized at construction by the capacity rule (slm_moe_align_capacity) for max_tokens rows, nothing on
 the path reads a device value on the host, and a smaller batch runs in views of the same buffers: forward() can be
@@ -241,14 +245,17 @@ class MoEMxfp4Experts:
     intermediate / 2] + `down_scale` [E, hidden, intermediate / 32].  load_state_dict takes the Quark names
     experts.{e}.w1|w3|w2.weight (uint8, or float4_e2m1fn_x2 / the [rows, K/32, 16] blocks form) and .weight_scale
     (uint8 or float8_e8m0fnu), both through kernels.mxfp4_bytes: any other dtype is a TypeError -- nothing is quantised
-    on load, as in the MXFP4 linears."""
+    on load, as in the MXFP4 linears.  act_quant="mxfp4": the same tensors under the same names, multiplied against
+    MXFP4 activations (gemm_w4a4: kernels.moe_w4a4_grouped_gemm); gemm() stays the W4A16 path."""
 
     def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device,
-                 expert_offset: int = 0):
+                 expert_offset: int = 0, act_quant: Optional[str] = None):
         if dtype not in (torch.float16, torch.bfloat16):
             raise SlmError(f"MoE experts: fp16 / bf16 activations only, got {dtype}")
+        if act_quant not in (None, "mxfp4"):
+            raise SlmError(f"unknown act_quant {act_quant!r}: None or 'mxfp4'")
         self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
-        self.dtype, self.device = dtype, device
+        self.dtype, self.device, self.act_quant = dtype, device, act_quant
         self.expert_offset = expert_offset   # expert e of this holder is experts.{expert_offset + e}.* (an EP shard)
         self._ckpt: Dict[str, torch.Tensor] = {}
         self.gate_up: Optional[torch.Tensor] = None
@@ -299,11 +306,42 @@ class MoEMxfp4Experts:
         kernels.moe_mxfp4_grouped_gemm(a, getattr(self, which), getattr(self, which + "_scale"), c, *aligned,
                                        **epilogue)
 
+    def gemm_w4a4(self, which: str, a, a_scale, c, *aligned, **epilogue) -> None:
+        """gemm() over MXFP4 activations (a, a_scale: quantize_mxfp4_act's pair, or a quantised gate_up output)"""
+        kernels.moe_w4a4_grouped_gemm(a, a_scale, getattr(self, which), getattr(self, which + "_scale"), c, *aligned,
+                                      **epilogue)
+
+    def ffn_w4a4(self, x2, bufs, n, down, srt, eids, n_padded, a_div: int, row_scale=None) -> None:
+        """quantise x2 [rows, hidden] -> gate_up (SiLU * mul, quantised output) -> down [n, hidden], in `bufs`'
+        xq / xs / actq / acts (w4a4_buffers)"""
+        xq, xs = bufs["xq"][:x2.size(0)], bufs["xs"][:x2.size(0)]
+        actq, acts = bufs["actq"][:n], bufs["acts"][:n]
+        kernels.quantize_mxfp4_act(x2, xq, xs)
+        self.gemm_w4a4("gate_up", xq, xs, actq, srt, eids, n_padded, a_div=a_div, silu_mul=True, c_scale=acts,
+                       dtype=self.dtype)
+        self.gemm_w4a4("down", actq, acts, down, srt, eids, n_padded, a_div=1, row_scale=row_scale)
+
+    def w4a4_buffers(self, rows: int, n_flat: int) -> Dict[str, torch.Tensor]:
+        """the MXFP4 images of `rows` rows of x and `n_flat` rows of the SiLU * mul output"""
+        u8, dev, B = torch.uint8, self.device, kernels.MXFP4_BLOCK
+        return dict(xq=torch.empty(rows, self.hidden // 2, dtype=u8, device=dev),
+                    xs=torch.empty(rows, self.hidden // B, dtype=u8, device=dev),
+                    actq=torch.empty(n_flat, self.intermediate // 2, dtype=u8, device=dev),
+                    acts=torch.empty(n_flat, self.intermediate // B, dtype=u8, device=dev))
+
 
 def _make_experts(hidden: int, intermediate: int, n_experts: int, quant_args: Optional[QuantArgs], dtype, device,
-                  expert_offset: int = 0):
+                  expert_offset: int = 0, act_quant: Optional[str] = None):
     """The experts holder a QuantArgs selects: None -> unquantised, "fp8" -> MoEFp8Experts, "mxfp4" ->
-    MoEMxfp4Experts, else int4."""
+    MoEMxfp4Experts, else int4.  act_quant ("mxfp4": MXFP4 activations) needs QuantArgs("mxfp4", 4)."""
+    if act_quant is not None:
+        if act_quant != "mxfp4":
+            raise SlmError(f"unknown act_quant {act_quant!r}: None or 'mxfp4'")
+        if quant_args is None or quant_args.quant_method != "mxfp4" or quant_args.bits != 4:
+            raise SlmError("act_quant='mxfp4' needs MXFP4 experts: QuantArgs('mxfp4', 4)")
+        if hidden % 32 or intermediate % 32:
+            raise SlmError("hidden and intermediate must be multiples of 32 (K and N of the two grouped GEMMs)")
+        return MoEMxfp4Experts(hidden, intermediate, n_experts, dtype, device, expert_offset, act_quant)
     if quant_args is None or quant_args.quant_method in ("fp8", "mxfp4"):
         if quant_args is not None and quant_args.quant_method == "fp8" and quant_args.bits != 8:
             raise SlmError(f"quant_method 'fp8' means 8-bit weights, got bits = {quant_args.bits}")
@@ -324,7 +362,9 @@ class FusedMoE:
     (AWQ / GPTQ) with a QuantArgs, fp8 (e4m3 weights, f16 / bf16 activations) with QuantArgs("fp8", 8), OCP MXFP4
     (e2m1 nibbles + e8m0 block scales, f16 / bf16 activations) with QuantArgs("mxfp4", 4) -- the other fields of
     these two are ignored --, unquantised f16 / bf16 with quant_args=None.  Each experts class runs its own grouped
-    GEMM (experts.gemm); the forward pass is the same six launches for all four.
+    GEMM (experts.gemm); the forward pass is the same six launches for all four.  act_quant="mxfp4" (MXFP4 experts
+    only) runs both GEMMs against MXFP4 activations: router, align, quantise x, gate_up with SiLU * mul and a
+    quantised output, down with the routing weight, sum -- seven launches, every buffer sized once.
 
     scoring = "softmax": top-k of the softmax (renormalize = Mixtral's rule: the k weights divided by their sum);
     scoring = "grouped_sigmoid": sigmoid scores with a correction bias, group-limited top-k (n_expert_groups,
@@ -334,7 +374,7 @@ class FusedMoE:
                  quant_args: Optional[QuantArgs] = None,
                  scoring: str = "softmax", renormalize: bool = True, n_expert_groups: int = 1, topk_group: int = 1,
                  scaling_factor: float = 1.0, max_tokens: int = 256, dtype: torch.dtype = torch.bfloat16,
-                 device="cuda", router: str = "torch"):
+                 device="cuda", router: str = "torch", act_quant: Optional[str] = None):
         if scoring not in ("softmax", "grouped_sigmoid"):
             raise SlmError(f"unknown scoring {scoring}")
         if router not in ("torch", "fused"):
@@ -346,11 +386,16 @@ class FusedMoE:
         self.scoring, self.renormalize = scoring, renormalize
         self.n_expert_groups, self.topk_group, self.scaling_factor = n_expert_groups, topk_group, scaling_factor
         self.max_tokens, self.dtype, self.device = max_tokens, dtype, device
-        self.experts = _make_experts(hidden, intermediate, n_experts, quant_args, dtype, device)
+        self.experts = _make_experts(hidden, intermediate, n_experts, quant_args, dtype, device, act_quant=act_quant)
         self.gate_weight: Optional[torch.Tensor] = None       # [E, hidden]
         self.correction_bias: Optional[torch.Tensor] = None   # [E] fp32 (grouped_sigmoid)
         self._gate_f32_t: Optional[torch.Tensor] = None       # [hidden, E] fp32, built on the first forward
         self._buf = None
+
+    @property
+    def act_quant(self) -> Optional[str]:
+        """"mxfp4" when the experts multiply against MXFP4 activations (the experts holder carries it)"""
+        return getattr(self.experts, "act_quant", None)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         if "gate.weight" in sd:
@@ -374,6 +419,9 @@ class FusedMoE:
                 act=torch.empty(n_flat, self.intermediate, dtype=self.dtype, device=dev),
                 down=torch.empty(n_flat, self.hidden, dtype=self.dtype, device=dev),
             )
+            if self.act_quant:   # x and the SiLU * mul output as MXFP4 instead of `act`
+                del self._buf["act"]
+                self._buf.update(self.experts.w4a4_buffers(self.max_tokens, n_flat))
         return self._buf
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -406,7 +454,7 @@ class FusedMoE:
         max_padded, max_blocks = kernels.moe_align_capacity(n_flat, self.n_experts, kernels.MOE_GEMM_BLOCK)
         weights, ids = b["weights"][:n_flat].view(T, k), b["ids"][:n_flat].view(T, k)
         srt, eids = b["sorted"][:max_padded], b["expert_ids"][:max_blocks]
-        act, down = b["act"][:n_flat], b["down"][:n_flat]
+        down = b["down"][:n_flat]
 
         if self.scoring != "softmax" and self.correction_bias is None:
             raise SlmError("gate.e_score_correction_bias is not loaded")
@@ -426,8 +474,12 @@ class FusedMoE:
                 kernels.moe_grouped_topk_sigmoid(logits, self.correction_bias, self.n_expert_groups, self.topk_group,
                                                  k, self.scaling_factor, weights, ids)
         kernels.moe_align_block(ids, self.n_experts, kernels.MOE_GEMM_BLOCK, srt, eids, b["n_padded"])
-        self.experts.gemm("gate_up", x2, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
-        self.experts.gemm("down", act, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
+        if self.act_quant:
+            self.experts.ffn_w4a4(x2, b, n_flat, down, srt, eids, b["n_padded"], k, row_scale=weights.view(-1))
+        else:
+            act = b["act"][:n_flat]
+            self.experts.gemm("gate_up", x2, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
+            self.experts.gemm("down", act, down, srt, eids, b["n_padded"], a_div=1, row_scale=weights.view(-1))
         if shared_out is None:
             kernels.moe_sum(down.view(T, k, self.hidden), out.view(T, self.hidden))
         else:
@@ -608,7 +660,8 @@ class ExpertParallelMoE:
     def __init__(self, hidden: int, intermediate: int, n_experts: int, topk: int, process_group,
                  quant_args: Optional[QuantArgs] = None, scoring: str = "softmax", renormalize: bool = True,
                  n_expert_groups: int = 1, topk_group: int = 1, scaling_factor: float = 1.0,
-                 dtype: torch.dtype = torch.bfloat16, device="cuda", router: str = "torch"):
+                 dtype: torch.dtype = torch.bfloat16, device="cuda", router: str = "torch",
+                 act_quant: Optional[str] = None):
         if scoring not in ("softmax", "grouped_sigmoid"):
             raise SlmError(f"unknown scoring {scoring}")
         if router not in ("torch", "fused"):
@@ -623,10 +676,16 @@ class ExpertParallelMoE:
         self.n_expert_groups, self.topk_group, self.scaling_factor = n_expert_groups, topk_group, scaling_factor
         self.dtype, self.device = dtype, device
         offset = process_group.rank * L
-        self.experts = _make_experts(hidden, intermediate, L, quant_args, dtype, device, expert_offset=offset)
+        self.experts = _make_experts(hidden, intermediate, L, quant_args, dtype, device, expert_offset=offset,
+                                     act_quant=act_quant)
         self.gate_weight: Optional[torch.Tensor] = None
         self.correction_bias: Optional[torch.Tensor] = None
         self._gate_f32_t: Optional[torch.Tensor] = None
+
+    @property
+    def act_quant(self) -> Optional[str]:
+        """"mxfp4" when the experts multiply against MXFP4 activations (the experts holder carries it)"""
+        return getattr(self.experts, "act_quant", None)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         if "gate.weight" in sd:
@@ -649,6 +708,9 @@ class ExpertParallelMoE:
         eids = torch.empty(max_blocks, dtype=i32, device=dev)
         n_padded = torch.zeros(1, dtype=i32, device=dev)
         kernels.moe_align_block(row_expert, L, kernels.MOE_GEMM_BLOCK, srt, eids, n_padded)
+        if self.act_quant:
+            self.experts.ffn_w4a4(rows, self.experts.w4a4_buffers(n, n), n, down, srt, eids, n_padded, 1)
+            return down
         act = torch.empty(n, self.intermediate, dtype=rows.dtype, device=dev)
         self.experts.gemm("gate_up", rows, act, srt, eids, n_padded, a_div=1, silu_mul=True)
         self.experts.gemm("down", act, down, srt, eids, n_padded, a_div=1)

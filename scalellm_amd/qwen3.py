@@ -89,12 +89,18 @@ class Qwen3DecodeStep:
     def __init__(self, shape: Qwen3Shape, max_batch_tokens: int, n_blocks: int, block_size: int,
                  parallel_args: Optional[ParallelArgs] = None, quant_method: str = "none", group_size: int = 128,
                  dtype=torch.bfloat16, device="cuda", seed: int = 0, custom_allreduce=None,
-                 keep_checkpoint: bool = False, record_routing: bool = False):
+                 keep_checkpoint: bool = False, record_routing: bool = False, act_quant: Optional[str] = None):
         pa = parallel_args or ParallelArgs()
         if pa.world_size > 1 or custom_allreduce is not None:
             raise ValueError("Qwen3DecodeStep runs on one rank: tensor parallelism is out of scope")
         if quant_method not in ("none", "fp8", "awq", "mxfp4"):
             raise ValueError(f"quant_method must be 'none', 'fp8', 'awq' or 'mxfp4', not {quant_method!r}")
+        # act_quant "mxfp4" (with quant_method "mxfp4" only): MXFP4 activations too (W4A4) -- the linears quantise theirs
+        # as they load them (layers.*Mxfp4Linear(act_quant=...)), the experts run FusedMoE(act_quant=...)
+        if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
+            raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
+        self.act_quant = act_quant
+        aq = {"act_quant": act_quant} if act_quant else {}
         if shape.head_dim not in (64, 128, 256):
             raise ValueError(f"head_dim {shape.head_dim}: the QK-norm prologue takes 64, 128 or 256")
         if record_routing and not shape.n_experts:
@@ -141,8 +147,8 @@ class Qwen3DecodeStep:
                 Col, Row = (ColumnParallelFp8Linear, RowParallelFp8Linear) if quant_method == "fp8" else \
                     (ColumnParallelMxfp4Linear, RowParallelMxfp4Linear) if quant_method == "mxfp4" else \
                     (ColumnParallelLinear, RowParallelLinear)
-                L[name] = Col(K, N, False, False, pa, dtype, dev, act_mul=act) if col else \
-                    Row(K, N, False, True, pa, dtype, dev)
+                L[name] = Col(K, N, False, False, pa, dtype, dev, act_mul=act, **aq) if col else \
+                    Row(K, N, False, True, pa, dtype, dev, **aq)
                 w = draw(N, K)
                 if quant_method == "fp8":
                     w8, sc = kernels.quantize_fp8_weight(w)
@@ -171,7 +177,7 @@ class Qwen3DecodeStep:
                         else:
                             sd[p + "weight"] = draw(N, K)
                 L["moe"] = FusedMoE(H, inter, E, k, qa, scoring="softmax", renormalize=shape.norm_topk_prob,
-                                    max_tokens=T, dtype=dtype, device=dev, router="fused")
+                                    max_tokens=T, dtype=dtype, device=dev, router="fused", **aq)
                 L["moe"].load_state_dict(sd)
                 L["moe"].experts.repack()
                 ck["moe"] = sd

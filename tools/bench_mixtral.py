@@ -158,7 +158,9 @@ def part_step(args, dev):
             tokens, positions, params, n_blocks = make_decode_inputs(bs, kv_len, block, dev, seed=bs, vocab=shape.vocab)
             if step is None:
                 nb = make_decode_inputs(32, kv_len, block, dev, vocab=shape.vocab)[3]
-                step = MixtralDecodeStep(shape, 32, nb, block, quant_method=quant, device=dev)
+                # "mxfp4+a4": MXFP4 weights AND activations (act_quant="mxfp4", W4A4)
+                aq = {"act_quant": "mxfp4"} if quant.endswith("+a4") else {}
+                step = MixtralDecodeStep(shape, 32, nb, block, quant_method=quant.split("+")[0], device=dev, **aq)
                 for L in step.layers:
                     for t in L["kv"].get_kv_cache():
                         t.normal_()
@@ -191,7 +193,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--pool", type=int, default=16)
     ap.add_argument("--parts", default="router,layer,step")
-    ap.add_argument("--quants", default="none,fp8,awq", help="the step part's quant_method list")
+    ap.add_argument("--quants", default="none,fp8,awq",
+                    help="the step part's quant_method list; 'mxfp4+a4' is mxfp4 with act_quant='mxfp4' (W4A4)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mixtral needs a GPU: there is no CPU path to time")

@@ -5,6 +5,7 @@ loop over the experts: per-expert slm_w4a16_gemm calls for int4 experts, torch.m
     python tools/bench_moe.py --dense [--out profiles/r12_moe_dense.jsonl]
     python tools/bench_moe.py --fp8 [--out profiles/r18_moe_fp8.jsonl]
     python tools/bench_moe.py --mxfp4 [--out profiles/r23_moe_mxfp4.jsonl]
+    python tools/bench_moe.py --w4a4 [--out profiles/r25_moe_w4a4.jsonl]
 
 hidden 4096, intermediate 14336, E = 8, k = 2, AWQ group 128, bf16 (random weights: 705 MB packed).  One JSON
 line per T:
@@ -42,6 +43,12 @@ weights (bit-identical output, asserted).  All three forwards are captured and r
 every window is listed, *_spread = (max - min) / median of the windows), touched_bytes / streamed_bytes / frac_7tbs
 over the MXFP4 bytes (nibbles + scale bytes), and the other two layers' own fractions.  The three layers share the
 router weights and the inputs, so they route alike and stream the same experts.
+
+--w4a4: the MXFP4 experts of --mxfp4 against MXFP4 activations (FusedMoE(QuantArgs("mxfp4", 4), act_quant="mxfp4"),
+slm_moe_w4a4_gemm: seven launches, x quantised once per token, the gate_up epilogue writing the down GEMM's input as
+MXFP4) beside the W4A16 layer over the SAME expert tensors and the fp8 layer of --fp8, one process, alternating
+windows: one JSON line per T with w4a4_us / mxfp4_us / fp8_us, their windows and spreads, w4a4_over_mxfp4, the byte
+fractions, and w4a4_vs_mxfp4_rel_err (what quantising the activations costs on random, uncalibrated data).
 """
 import argparse
 import json
@@ -247,6 +254,49 @@ def _main_mxfp4(args, dev, tokens):
     return lines
 
 
+def _main_w4a4(args, dev, tokens):
+    mx4, fp8 = _mxfp4_fp8_and_dense_layers(max(tokens), dev, sides=("mxfp4", "fp8"))
+    w4a4 = moe.FusedMoE(HID, INTER, NE, TOPK, quant_args=QuantArgs("mxfp4", 4), scoring="softmax", renormalize=True,
+                        max_tokens=max(tokens), dtype=torch.bfloat16, device=dev, act_quant="mxfp4")
+    w4a4.gate_weight = mx4.gate_weight
+    for name in ("gate_up", "down", "gate_up_scale", "down_scale"):   # the same tensors: nothing is copied
+        setattr(w4a4.experts, name, getattr(mx4.experts, name))
+    mx_bytes, fp8_bytes = mx4.experts.nbytes() // NE, fp8.experts.nbytes() // NE
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    spread = lambda t: round((max(t) - min(t)) / med(t), 4)  # noqa: E731
+    lines = []
+    for T in tokens:
+        g = torch.Generator(device=dev).manual_seed(T)
+        pool = [torch.randn(T, HID, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(args.pool)]
+        runs = {"w4a4": _captured(w4a4, pool, T, dev), "mxfp4": _captured(mx4, pool, T, dev),
+                "fp8": _captured(fp8, pool, T, dev)}
+        y44, y416 = runs["w4a4"][1].float(), runs["mxfp4"][1].float()
+        rel = float((y44 - y416).abs().mean() / y416.abs().mean())
+        times = {k: [] for k in runs}
+        for _ in range(args.rounds):                    # alternating windows: drift hits all columns alike
+            for k, (run, _) in runs.items():
+                times[k].append(_time(run, args.iters))
+        us = {k: med(t) for k, t in times.items()}
+        routed = [_routing(mx4, x)[1] for x in pool]
+        used = [int(ids.unique().numel()) for ids in routed]
+        blocks = [int(((torch.bincount(ids.reshape(-1), minlength=NE) + 31) // 32).sum()) for ids in routed]
+        n_used, n_blocks = sum(used) / len(used), sum(blocks) / len(blocks)
+        frac = lambda nbytes, t: round(nbytes * n_used / (t * 1e-6) / READ_CEILING, 4)  # noqa: E731
+        line = dict(bench="moe_mixtral_8x7b_w4a4_bf16", T=T, topk=TOPK, n_experts=NE)
+        for k in runs:
+            line[k + "_us"] = round(us[k], 2)
+            line[k + "_us_windows"] = [round(t, 2) for t in times[k]]
+            line[k + "_spread"] = spread(times[k])
+        line.update(w4a4_over_mxfp4=round(us["w4a4"] / us["mxfp4"], 4), w4a4_over_fp8=round(us["w4a4"] / us["fp8"], 4),
+                    experts_in_use=round(n_used, 2), row_blocks=round(n_blocks, 2),
+                    touched_bytes=int(mx_bytes * n_used), frac_7tbs=frac(mx_bytes, us["w4a4"]),
+                    mxfp4_frac_7tbs=frac(mx_bytes, us["mxfp4"]), fp8_frac_7tbs=frac(fp8_bytes, us["fp8"]),
+                    w4a4_vs_mxfp4_rel_err=round(rel, 5), iters=args.iters, pool=args.pool, rounds=args.rounds)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def _routing(layer, x):
     logits = x.float() @ layer.gate_weight.float().t()
     w, ids = kernels.moe_topk_softmax(logits, TOPK, True)
@@ -311,11 +361,15 @@ def main():
     ap.add_argument("--mxfp4", action="store_true",
                     help="MXFP4 experts (slm_moe_mxfp4_gemm) beside the fp8 layer and the dense bf16 layer on the "
                          "dequantised weights")
-    ap.add_argument("--rounds", type=int, default=3, help="--fp8 / --mxfp4: alternating timing windows per layer")
+    ap.add_argument("--w4a4", action="store_true",
+                    help="MXFP4 experts against MXFP4 activations (slm_moe_w4a4_gemm) beside the W4A16 layer over the "
+                         "same tensors and the fp8 layer")
+    ap.add_argument("--rounds", type=int, default=3,
+                    help="--fp8 / --mxfp4 / --w4a4: alternating timing windows per layer")
     args = ap.parse_args()
-    if args.dense + args.fp8 + args.mxfp4 > 1:
-        raise SystemExit("--dense, --fp8 and --mxfp4 are three modes: pick one (--fp8 and --mxfp4 measure the dense "
-                         "layer too)")
+    if args.dense + args.fp8 + args.mxfp4 + args.w4a4 > 1:
+        raise SystemExit("--dense, --fp8, --mxfp4 and --w4a4 are four modes: pick one (--fp8 and --mxfp4 measure the "
+                         "dense layer too)")
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda")
@@ -325,6 +379,9 @@ def main():
         return
     if args.mxfp4:
         _write(args.out, _main_mxfp4(args, dev, tokens))
+        return
+    if args.w4a4:
+        _write(args.out, _main_w4a4(args, dev, tokens))
         return
     if args.dense:
         layer = _dense_layer(max(tokens), dev)
