@@ -1860,6 +1860,55 @@ typedef struct slm_moe_w4a4_gemm_args {
 SLM_API int slm_moe_w4a4_gemm
     (const slm_moe_w4a4_gemm_args* a, void* stream);
 
+/* ========================================================================== */
+/* 24. MXFP4 activations from the producers: RMSNorm and the dense SiLU * mul  */
+/*    GEMM epilogue write the next W4A4 GEMM's pre-quantised side             */
+/*    Section 22's T side quantises inside the multiplying wave; these two    */
+/*    entries move the quantiser into the kernel that produces the            */
+/*    activations, so the consumer takes 16 B + 1 B per block and does no     */
+/*    VALU work on them.  Both are BYTE FOR BYTE what the existing launches   */
+/*    compose (the arithmetic is shared through csrc/common.h and             */
+/*    csrc/w4a4_quant.h), so nothing calibrated changes.                      */
+/*                                                                            */
+/*    slm_rms_norm_mxfp4 / slm_rms_norm_mxfp4_splitk (csrc/norm_quant.hip):   */
+/*    slm_rms_norm / slm_rms_norm_splitk (section 3) with the output as       */
+/*    MXFP4: aq [n_tokens, dim/2] code bytes, row stride ldaq (bytes, >=      */
+/*    dim/2, % 16, base 16-byte aligned), a_scale [n_tokens, dim/32] e8m0     */
+/*    bytes, row stride ldas (>= dim/32, any) -- exactly                      */
+/*    slm_w4a4_quantize_act run on that call's output; no byte outside        */
+/*    [0, dim/2) / [0, dim/32) of a row is written.  out_t != NULL also       */
+/*    receives that call's T row [n_tokens, dim] (contiguous), bit for bit;   */
+/*    residual (or NULL) is read and updated exactly as there.  x, weight,    */
+/*    residual, partials, out_t: contiguous, 16-byte aligned.                 */
+/*    dim % 32 == 0, dim <= 16384, f16 / bf16 (else SLM_ERR_UNSUPPORTED);     */
+/*    missing aq / a_scale / x (partials) / weight, n_splits < 1, ldaq <      */
+/*    dim/2, ldas < dim/32: SLM_ERR_INVALID_ARG; alignment:                   */
+/*    SLM_ERR_ALIGNMENT.  All validation before any launch; n_tokens == 0 is  */
+/*    SLM_OK without one.  ONE launch, no workspace, capturable.              */
+/*                                                                            */
+/*    slm_w4a4q_linear (csrc/w4a4.hip): slm_w4a4_linear with                  */
+/*    SLM_LINEAR_SILU_MUL whose output is not stored in T but as MXFP4:       */
+/*    a->c is [M, N/4] code BYTES with a->ldc in bytes (>= N/4, % 16, base    */
+/*    16-byte aligned), c_scale [M, N/64] e8m0 bytes with row stride ldcs     */
+/*    (>= N/64, any): byte for byte slm_w4a4_quantize_act run on what         */
+/*    slm_w4a4_linear writes for the same arguments under the same plan (one  */
+/*    32 x 32 output tile is one MX block per row).  Both activation sides.   */
+/*    Without SLM_LINEAR_SILU_MUL, with bias, with SLM_LINEAR_DEFER_REDUCE or */
+/*    with c_scale == NULL: SLM_ERR_INVALID_ARG.  Everything else (shapes,    */
+/*    strides of a / w / scales, error codes, M == 0) is section 22's; the    */
+/*    plan is slm_w4a4_linear_plan's for those arguments (split_k = 1: no     */
+/*    workspace).                                                             */
+/* ========================================================================== */
+SLM_API int slm_rms_norm_mxfp4(void* aq, int64_t ldaq, uint8_t* a_scale, int64_t ldas, void* out_t /* or NULL */,
+                               const void* x, const void* weight, void* residual /* or NULL */, int64_t n_tokens,
+                               int64_t dim, float eps, int32_t dtype, void* stream);
+SLM_API int slm_rms_norm_mxfp4_splitk(void* aq, int64_t ldaq, uint8_t* a_scale, int64_t ldas, void* out_t /* or NULL */,
+                                      const float* partials /* [n_splits, n_tokens, dim] */, int32_t n_splits,
+                                      const void* weight, void* residual /* or NULL */, int64_t n_tokens, int64_t dim,
+                                      float eps, int32_t dtype, void* stream);
+SLM_API int slm_w4a4q_linear(const slm_w4a4_linear_args* a, uint8_t* c_scale, int64_t ldcs, void* stream);
+SLM_API int slm_w4a4q_linear_plan(const slm_w4a4_linear_args* a, slm_linear_plan_info* out);
+
 #ifdef __cplusplus
 }
 #endif

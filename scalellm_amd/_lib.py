@@ -464,6 +464,15 @@ def lib() -> C.CDLL:
         ("slm_w4a4_linear", C.c_int, [C.POINTER(W4A4LinearArgs), C.c_void_p]),
         ("slm_w4a4_linear_deferred_splits", C.c_int32, [C.POINTER(W4A4LinearArgs)]),
         ("slm_w4a4_linear_plan", C.c_int, [C.POINTER(W4A4LinearArgs), C.POINTER(LinearPlanInfo)]),
+        # section 24: (aq, ldaq, a_scale, ldas, out_t, x | partials, n_splits, weight, residual, n_tokens, dim, eps, ...)
+        ("slm_rms_norm_mxfp4", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+          C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
+        ("slm_rms_norm_mxfp4_splitk", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+          C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
+        ("slm_w4a4q_linear", C.c_int, [C.POINTER(W4A4LinearArgs), C.c_void_p, C.c_int64, C.c_void_p]),
+        ("slm_w4a4q_linear_plan", C.c_int, [C.POINTER(W4A4LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

@@ -36,6 +36,10 @@
 // Forms: RT = 1 / 2 / 4 row tiles per wave, NW = 1 / 2 / 4 >= RT waves, the K split and SiLU * mul exactly as
 // dense.hip's (dense_plan.h under the knobs SLM_W4A4_RT / _NW / _SPLITK).  A wave's arithmetic does not depend on the
 // form; repeats are bit-identical (no atomics, fixed order).
+//
+// slm_w4a4q_linear (section 24): the SiLU * mul form whose gate wave writes its output tile as MXFP4 -- one 32 x 32
+// tile is one MX block per row (w4a4_quant.h: quantize_tile_row, shared with w4a4_moe.hip).  A compile-time variant
+// (QOUT) of the kernel below: the instantiations of slm_w4a4_linear keep their registers.
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <type_traits>
 
@@ -67,6 +71,8 @@ struct W4A4KParams {
   int split_k;
   int silu;
   int slice_chunk[LIN_MAX_SPLIT + 1];
+  uint8_t* c_scale;  // QOUT: [M, N / 64] e8m0 bytes; c is then [M, N / 4] code bytes and ldc counts bytes
+  int64_t ldcs;
 };
 
 // D = A . B + C over 64 k: e2m1 codes of one MX block per lane and operand, their e8m0 bytes in byte 0 of sa / sb
@@ -80,8 +86,11 @@ __device__ __forceinline__ f32x16 mfma_mx4(const u32x4 a, const uint32_t sa, con
 // byte offset of (row, block) in a stage's code image
 __device__ __forceinline__ int a_code_off(int row, int blk) { return row * 64 + ((blk ^ ((row >> 2) & 3)) << 4); }
 
-template <typename T, int RT, int NW, bool AQ>
+// QOUT (slm_w4a4q_linear: always SiLU * mul, split_k = 1, no bias): the gate wave stores its output tile's rows as MX
+// blocks, not as T
+template <typename T, int RT, int NW, bool AQ, bool QOUT = false>
 __global__ void __launch_bounds__(NW * 64) w4a4_linear_kernel(const W4A4KParams p) {
+  static_assert(!QOUT || NW >= 2, "the quantising epilogue is the SiLU pair's");
   constexpr int RING = W4A4_RING;
   constexpr int NT = NW * 64;
   constexpr int ROWS = RT * 32;
@@ -285,7 +294,7 @@ __global__ void __launch_bounds__(NW * 64) w4a4_linear_kernel(const W4A4KParams 
   // ---- epilogue (dense.hip's).  C^T layout: lane (m = lane & 31, kh), registers 4 j .. 4 j + 3 = columns
   // 8 j + 4 kh + {0..3}
   const int ncol0 = nt * 32 + 4 * kh;  // + 8 j
-  if (p.part) {  // a K slice: the fp32 slab, no bias, no rounding
+  if (!QOUT && p.part) {  // a K slice: the fp32 slab, no bias, no rounding
     if (!nvalid) return;
     float* slab = p.part + (int64_t)ks * p.M * p.N;
 #pragma unroll
@@ -306,7 +315,7 @@ __global__ void __launch_bounds__(NW * 64) w4a4_linear_kernel(const W4A4KParams 
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     f32x4 b = {0.f, 0.f, 0.f, 0.f};
-    if (p.bias) {
+    if (!QOUT && p.bias) {
       const u32x2 bv = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(p.bias) + ncol0 + 8 * j);
       b.x = lo_f32<T>(bv.x); b.y = hi_f32<T>(bv.x); b.z = lo_f32<T>(bv.y); b.w = hi_f32<T>(bv.y);
     }
@@ -318,7 +327,7 @@ __global__ void __launch_bounds__(NW * 64) w4a4_linear_kernel(const W4A4KParams 
   }
   uint16_t* cbase = reinterpret_cast<uint16_t*>(p.c);
   if constexpr (NW >= 2) {
-    if (p.silu) {
+    if (QOUT || p.silu) {
       // the up wave hands its T-rounded tiles to the gate wave through the (now idle) stages; same lane, same (t, j)
       u32x2* ex = reinterpret_cast<u32x2*>(smem) + (wave >> 1) * (RT * 4 * 64);
       if (wave & 1) {
@@ -329,6 +338,28 @@ __global__ void __launch_bounds__(NW * 64) w4a4_linear_kernel(const W4A4KParams 
       }
       __syncthreads();
       if ((wave & 1) || !nvalid) return;
+      if constexpr (QOUT) {
+        // the tile's row as one MX block (w4a4_quant.h); all 64 lanes take part in the exchanges, rows beyond M
+        // (clamped duplicates of row M - 1) are only kept from storing
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+          const int gm = row0 + t * 32 + mrow;
+          u32x2 r[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const u32x2 g = packed[t][j], u = ex[(t * 4 + j) * 64 + lane];
+            r[j].x = pack2<T>(silu_mul1(lo_f32<T>(g.x), lo_f32<T>(u.x)), silu_mul1(hi_f32<T>(g.x), hi_f32<T>(u.x)));
+            r[j].y = pack2<T>(silu_mul1(lo_f32<T>(g.y), lo_f32<T>(u.y)), silu_mul1(hi_f32<T>(g.y), hi_f32<T>(u.y)));
+          }
+          uint32_t e8;
+          const u32x2 codes = quantize_tile_row<T>(r, kh, e8);
+          if (gm < p.M) {
+            *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(p.c) + (int64_t)gm * p.ldc + nt * 16 + kh * 8) = codes;
+            if (kh == 0) p.c_scale[(int64_t)gm * p.ldcs + nt] = (uint8_t)e8;
+          }
+        }
+        return;
+      }
 #pragma unroll
       for (int t = 0; t < RT; ++t) {
         const int gm = row0 + t * 32 + mrow;
@@ -384,6 +415,13 @@ static int plan_w4a4(const slm_w4a4_linear_args* a, LinearPlan* pl) {
 
 template <typename T, int RT, int NW>
 static void launch_w4a4(const W4A4KParams& kp, bool aq, dim3 grid, hipStream_t st) {
+  if constexpr (NW >= 2) {
+    if (kp.c_scale) {
+      if (aq) hipLaunchKernelGGL((w4a4_linear_kernel<T, RT, NW, true, true>), grid, dim3(NW * 64), 0, st, kp);
+      else hipLaunchKernelGGL((w4a4_linear_kernel<T, RT, NW, false, true>), grid, dim3(NW * 64), 0, st, kp);
+      return;
+    }
+  }
   if (aq) hipLaunchKernelGGL((w4a4_linear_kernel<T, RT, NW, true>), grid, dim3(NW * 64), 0, st, kp);
   else hipLaunchKernelGGL((w4a4_linear_kernel<T, RT, NW, false>), grid, dim3(NW * 64), 0, st, kp);
 }
@@ -398,21 +436,31 @@ static void launch_w4a4_form(const W4A4KParams& kp, bool aq, int rt, int nw, dim
   else launch_w4a4<T, 1, 1>(kp, aq, grid, st);
 }
 
-static int run_w4a4(const slm_w4a4_linear_args* a, void* stream) {
+// the flags slm_w4a4q_linear takes: SiLU * mul, no bias, no deferred reduce
+static int check_w4a4q(const slm_w4a4_linear_args* a) {
+  if (!a) return SLM_ERR_INVALID_ARG;
+  if (!(a->flags & SLM_LINEAR_SILU_MUL) || (a->flags & SLM_LINEAR_DEFER_REDUCE) || a->bias) return SLM_ERR_INVALID_ARG;
+  return SLM_OK;
+}
+
+// c_scale != NULL: slm_w4a4q_linear (c: code bytes, ldc in bytes)
+static int run_w4a4(const slm_w4a4_linear_args* a, uint8_t* c_scale, int64_t ldcs, bool qout, void* stream) {
   LinearPlan pl;
-  const int rc = plan_w4a4(a, &pl);
+  int rc = qout ? check_w4a4q(a) : SLM_OK;
+  if (rc == SLM_OK) rc = plan_w4a4(a, &pl);
   if (rc != SLM_OK) return rc;
   if (a->M == 0) return SLM_OK;
+  if (qout && !c_scale) return SLM_ERR_INVALID_ARG;
   const bool aq = a->a_scale != nullptr;
   const bool silu = (a->flags & SLM_LINEAR_SILU_MUL) != 0;
   const bool defer = (a->flags & SLM_LINEAR_DEFER_REDUCE) && !a->bias && pl.split_k > 1;
   if (!a->a || !a->w || !a->c || !a->w_scale) return SLM_ERR_INVALID_ARG;
   // lda counts T on the T side and bytes (two codes) on the pre-quantised side; ldw bytes
   if (a->lda < (aq ? a->K / 2 : a->K) || a->ldw < a->K / 2 || a->lds < a->K / 32 || (aq && a->ldas < a->K / 32) ||
-      a->ldc < (silu ? a->N / 2 : a->N))
+      a->ldc < (qout ? a->N / 4 : silu ? a->N / 2 : a->N) || (qout && ldcs < a->N / 64))
     return SLM_ERR_INVALID_ARG;
   // every row of A, W and C starts on a 16-B boundary
-  if (!aligned16(a->a) || a->lda % (aq ? 16 : 8) || !aligned16(a->w) || a->ldw % 16 || !aligned16(a->c) || a->ldc % 8 ||
+  if (!aligned16(a->a) || a->lda % (aq ? 16 : 8) || !aligned16(a->w) || a->ldw % 16 || !aligned16(a->c) || a->ldc % (qout ? 16 : 8) ||
       (reinterpret_cast<uintptr_t>(a->bias) & 7u) || !aligned16(a->workspace))
     return SLM_ERR_ALIGNMENT;
   if (pl.ws_bytes > 0 && (!a->workspace || a->workspace_bytes < pl.ws_bytes)) return SLM_ERR_WORKSPACE;
@@ -432,6 +480,8 @@ static int run_w4a4(const slm_w4a4_linear_args* a, void* stream) {
   kp.tail_units = pl.tail_units;
   kp.split_k = pl.split_k;
   kp.silu = silu ? 1 : 0;
+  kp.c_scale = qout ? c_scale : nullptr;
+  kp.ldcs = ldcs;
   for (int j = 0; j <= LIN_MAX_SPLIT; ++j) kp.slice_chunk[j] = pl.slice_chunk[j];
   hip_clear_error();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -488,6 +538,17 @@ SLM_API int32_t slm_w4a4_linear_deferred_splits(const slm_w4a4_linear_args* a) {
              ? pl.split_k : 0;
 }
 
-SLM_API int slm_w4a4_linear(const slm_w4a4_linear_args* a, void* stream) { return slm::run_w4a4(a, stream); }
+SLM_API int slm_w4a4_linear(const slm_w4a4_linear_args* a, void* stream) {
+  return slm::run_w4a4(a, nullptr, 0, false, stream);
+}
+
+SLM_API int slm_w4a4q_linear_plan(const slm_w4a4_linear_args* a, slm_linear_plan_info* out) {
+  const int rc = slm::check_w4a4q(a);
+  return rc == SLM_OK ? slm_w4a4_linear_plan(a, out) : rc;
+}
+
+SLM_API int slm_w4a4q_linear(const slm_w4a4_linear_args* a, uint8_t* c_scale, int64_t ldcs, void* stream) {
+  return slm::run_w4a4(a, c_scale, ldcs, true, stream);
+}
 
 }  // extern "C"

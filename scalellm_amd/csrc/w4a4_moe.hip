@@ -97,8 +97,6 @@ __device__ __forceinline__ f32x16 mw4_mfma(const u32x4 a, const uint32_t sa, con
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c, 4, 4, 0, (int)sa, 0, (int)sb);
 }
 
-__device__ __forceinline__ uint32_t xor32(uint32_t v) { return (uint32_t)__shfl_xor((int)v, 32); }
-
 template <typename T, int NW>
 __global__ void __launch_bounds__(NW * 64) moe_w4a4_kernel(const MoeW4A4KParams p) {
   constexpr int RING = MW4_RING;
@@ -320,20 +318,10 @@ __global__ void __launch_bounds__(NW * 64) moe_w4a4_kernel(const MoeW4A4KParams 
         }
         return;
       }
-      // the tile's row as one MX block.  amax over the lane's 16 columns, then across the halves (all 64 lanes take
-      // part in the exchanges: padding rows are only kept from storing)
-      uint32_t mx = act_amax_pk(0u, u32x4{r[0].x, r[0].y, r[1].x, r[1].y});
-      mx = act_amax_pk(mx, u32x4{r[2].x, r[2].y, r[3].x, r[3].y});
-      mx = pk_max_u16(mx, xor32(mx));
-      const uint32_t e8 = act_block_e8m0<T>(act_amax15(mx));
-      const float scale = act_cvt_scale(e8);
-      // half 0 keeps registers 0, 1 and takes the partner's 0, 1 (columns 4 .. 7, 12 .. 15); half 1 keeps 2, 3 and takes
-      // the partner's 2, 3 (columns 16 .. 19, 24 .. 27): 16 consecutive columns from 16 kh
-      const u32x2 s0 = kh ? r[0] : r[2], s1 = kh ? r[1] : r[3];
-      const u32x2 t0 = {xor32(s0.x), xor32(s0.y)}, t1 = {xor32(s1.x), xor32(s1.y)};
-      const u32x4 q0 = kh ? u32x4{t0.x, t0.y, r[2].x, r[2].y} : u32x4{r[0].x, r[0].y, t0.x, t0.y};
-      const u32x4 q1 = kh ? u32x4{t1.x, t1.y, r[3].x, r[3].y} : u32x4{r[1].x, r[1].y, t1.x, t1.y};
-      const u32x2 codes = {act_cvt8<T>(q0, scale), act_cvt8<T>(q1, scale)};
+      // the tile's row as one MX block (all 64 lanes take part in the exchanges: padding rows are only kept from
+      // storing)
+      uint32_t e8;
+      const u32x2 codes = quantize_tile_row<T>(r, kh, e8);
       if (live_row) {
         *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(p.c) + (int64_t)fi * p.ldc + nt * 16 + kh * 8) = codes;
         if (kh == 0) p.c_scale[(int64_t)fi * p.ldcs + nt] = (uint8_t)e8;

@@ -1,7 +1,8 @@
 // w4a4_quant.h -- the MXFP4 activation quantiser's arithmetic (include/slm_hip.h section 22): 32 consecutive k of T
 // (one MX block, 64 bytes, four 16-B loads of ONE lane) -> 16 bytes of e2m1 codes + one e8m0 byte.  Shared by the
-// stand-alone quantiser, by the GEMM's T side (w4a4.hip) and by the grouped GEMM's quantising SiLU * mul epilogue
-// (w4a4_moe.hip), which therefore give the same bits.
+// stand-alone quantiser, by the GEMM's T side (w4a4.hip), by the quantising SiLU * mul epilogues of the grouped and the
+// dense GEMM (w4a4_moe.hip, w4a4.hip: quantize_tile_row) and by the RMSNorm that writes MXFP4 (norm_quant.hip), which
+// therefore give the same bits.
 //
 // The rule is kernels.quantize_mxfp4_weight's:
 //   e = clamp(floor(log2 amax) - 2 + 127, 1, 254); an all-zero block 127; a block holding inf or NaN 255
@@ -80,6 +81,27 @@ __device__ __forceinline__ uint32_t act_cvt8(const u32x4 x, float scale) {
   d = t2_to_fp4<T, 2>(d, x.z, scale);
   d = t2_to_fp4<T, 3>(d, x.w, scale);
   return d;
+}
+
+// The quantising SiLU * mul epilogue of the W4A4 GEMMs (w4a4_moe.hip, w4a4.hip): a 32 x 32 output tile in the C^T
+// accumulator layout is one MX block per row, held by the two lanes (m, kh = 0 / 1): r[j] = the T pairs of columns
+// 8 j + 4 kh + {0..3}.  amax over the lane's 16 columns, then across the halves; then half 0 keeps r[0], r[1] and takes
+// the partner's (columns 4 .. 7, 12 .. 15), half 1 keeps r[2], r[3] and takes the partner's (columns 16 .. 19,
+// 24 .. 27): 16 consecutive columns from 16 kh, returned as their 8 code bytes (bytes 8 kh .. 8 kh + 7 of the block);
+// both lanes get the block's e8m0 byte.  All 64 lanes must call it.
+__device__ __forceinline__ uint32_t xor32(uint32_t v) { return (uint32_t)__shfl_xor((int)v, 32); }
+template <typename T>
+__device__ __forceinline__ u32x2 quantize_tile_row(const u32x2 (&r)[4], const int kh, uint32_t& e8) {
+  uint32_t mx = act_amax_pk(0u, u32x4{r[0].x, r[0].y, r[1].x, r[1].y});
+  mx = act_amax_pk(mx, u32x4{r[2].x, r[2].y, r[3].x, r[3].y});
+  mx = pk_max_u16(mx, xor32(mx));
+  e8 = act_block_e8m0<T>(act_amax15(mx));
+  const float scale = act_cvt_scale(e8);
+  const u32x2 s0 = kh ? r[0] : r[2], s1 = kh ? r[1] : r[3];
+  const u32x2 t0 = {xor32(s0.x), xor32(s0.y)}, t1 = {xor32(s1.x), xor32(s1.y)};
+  const u32x4 q0 = kh ? u32x4{t0.x, t0.y, r[2].x, r[2].y} : u32x4{r[0].x, r[0].y, t0.x, t0.y};
+  const u32x4 q1 = kh ? u32x4{t1.x, t1.y, r[3].x, r[3].y} : u32x4{r[1].x, r[1].y, t1.x, t1.y};
+  return u32x2{act_cvt8<T>(q0, scale), act_cvt8<T>(q1, scale)};
 }
 
 // one MX block: x[q] holds k = 8 q .. 8 q + 7 of the block.  Returns the 16 code bytes, e8m0 byte in `e8`

@@ -176,13 +176,20 @@ class LlamaDecodeStep:
                  group_size: int = 128, dtype=torch.bfloat16, device="cuda", seed: int = 0,
                  kv_fill: str = "none", custom_allreduce=None, keep_checkpoint: bool = False,
                  gptq_sym: bool = False, fuse_silu: bool = True, desc_act: bool = False, bits: int = 4,
-                 act_quant: Optional[str] = None):
+                 act_quant: Optional[str] = None, fuse_act_quant: bool = False):
         pa = parallel_args or ParallelArgs()
         # act_quant "mxfp4" (with quant_method "mxfp4" only): the four linears quantise their activations to MXFP4 as
         # they load them and run the block-scaled MFMA (kernels.w4a4_linear): W4A4, no launch more than W4A16
         if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
             raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
         self.act_quant = act_quant
+        # fuse_act_quant (act_quant "mxfp4" only, off by default): the producers quantise -- the RMSNorm in front of
+        # qkv and gate_up writes MXFP4 (kernels.rms_norm_mxfp4), the gate_up GEMM's SiLU * mul epilogue writes MXFP4
+        # (w4a4_linear(c_scale=...)) -- and qkv, gate_up and down take their pre-quantised side.  The bits of the step
+        # are unchanged (slm_hip.h section 24); o_proj (fed by the attention) and the final norm stay as they are.
+        if fuse_act_quant and (act_quant != "mxfp4" or custom_allreduce is not None):
+            raise ValueError("fuse_act_quant needs act_quant='mxfp4' and no custom_allreduce (its fused norm writes T)")
+        self.fuse_act_quant = bool(fuse_act_quant)
         # quant_method "none": unquantised weights [N, K] of `dtype` (randn * 0.02 from the common seed), the four
         # linears are layers.{Column,Row}ParallelLinear over slm_linear; everything else of the step is shared
         # quant_method "fp8": that same checkpoint quantised per output channel to e4m3 (kernels.quantize_fp8_weight),
@@ -308,6 +315,11 @@ class LlamaDecodeStep:
                         attn=e(T, self.n_heads, D),
                         o=e(T, H), gate_up=None if fuse_silu else e(T, 2 * shape.intermediate // tp),
                         act=e(T, shape.intermediate // tp), down=e(T, H))
+        if self.fuse_act_quant:  # the MXFP4 rows beside normed / act: codes and e8m0 bytes, allocated once
+            u8 = lambda *s: torch.empty(*s, dtype=torch.uint8, device=self.device)  # noqa: E731
+            inter = shape.intermediate // tp
+            self.buf.update(normed_q=u8(T, H // 2), normed_s=u8(T, H // 32), act_q=u8(T, inter // 2),
+                            act_s=u8(T, inter // 32))
         if kv_fill != "none":
             self.fill_kv(kv_fill, gen)
 
@@ -452,7 +464,7 @@ class LlamaDecodeStep:
     # ------------------------------------------------------------------------------------------
     class _Lane:
         __slots__ = ("idx", "r0", "r1", "T", "positions", "params", "resid", "alt", "normed", "qkv",
-                     "attn", "act", "gate_up", "o_buf", "down_buf", "pend", "fold", "stream", "q", "ar")
+                     "attn", "act", "gate_up", "o_buf", "down_buf", "pend", "fold", "stream", "q", "ar", "normed_q", "act_q")
 
     def _tp_lanes_ok(self) -> bool:
         """May a tensor-parallel rank run its reductions on two streams at once?"""
@@ -612,6 +624,8 @@ class LlamaDecodeStep:
             ln.alt = b["resid_alt"][:T] if fold else None
             ln.qkv, ln.attn, ln.act = b["qkv"][r0:r1], b["attn"][r0:r1], b["act"][r0:r1]
             ln.gate_up = b["gate_up"][r0:r1] if b["gate_up"] is not None else None
+            ln.normed_q = (b["normed_q"][r0:r1], b["normed_s"][r0:r1]) if self.fuse_act_quant else None
+            ln.act_q = (b["act_q"][r0:r1], b["act_s"][r0:r1]) if self.fuse_act_quant else None
             if ar is not None and len(ranges) == 2:
                 # the lane's own all-reduce instance: its partial sums go to rows [0, n) of ITS buffers
                 ln.ar = self.custom_ars[i]
@@ -633,11 +647,17 @@ class LlamaDecodeStep:
             st = self._lane_bufs[key] = {"q_cu": z(), "kv_cu": z()}
         return st
 
-    def _run_norm(self, ln, pend) -> None:
+    def _run_norm(self, ln, pend, final: bool = False) -> None:
+        """`final`: the norm in front of the lm_head, which reads T whatever the linears take"""
         x, deferred, res, weight = pend
+        if self.fuse_act_quant and not final:
+            kernels.rms_norm_mxfp4(x, weight, self.shape.rms_eps, residual=res, partials=deferred,
+                                   aq=ln.normed_q[0], a_scale=ln.normed_q[1])
+            return
         kernels.rms_norm(ln.normed, x, weight, self.shape.rms_eps, residual=res, partials=deferred)
 
-    def _reduce_add_norm(self, ln, i: int, partial: torch.Tensor, weight: torch.Tensor, deferred=None):
+    def _reduce_add_norm(self, ln, i: int, partial: torch.Tensor, weight: torch.Tensor, deferred=None,
+                         final: bool = False):
         """normed = RMSNorm(all-reduce(partial) + resid) * weight, resid updated
         (reduce_from_model_parallel_region + rms_norm_residual, or the fused launch).
         Returns the norm still to be run when it may fold into its consumer, else None."""
@@ -649,16 +669,17 @@ class LlamaDecodeStep:
         pend = (partial, deferred, ln.resid, weight)
         if ln.fold:
             return pend
-        self._run_norm(ln, pend)
+        self._run_norm(ln, pend, final)
         return None
 
     def _norm_then(self, ln, lin, pend, out, defer_splitk=False):
         """lin(RMSNorm(pend)): in one launch when the projection takes the norm as its prologue."""
+        normed = ln.normed_q if self.fuse_act_quant else ln.normed
         if pend is None:
-            return lin.forward(ln.normed, out=out, defer_splitk=defer_splitk)
+            return lin.forward(normed, out=out, defer_splitk=defer_splitk)
         if not lin.norm_supported(ln.T, defer_splitk):
             self._run_norm(ln, pend)
-            return lin.forward(ln.normed, out=out, defer_splitk=defer_splitk)
+            return lin.forward(normed, out=out, defer_splitk=defer_splitk)
         x, deferred, res, weight = pend
         pro = kernels.NormPrologue(weight, self.shape.rms_eps, residual=res, partials=deferred,
                                    residual_out=ln.alt if res is not None else None)
@@ -692,14 +713,17 @@ class LlamaDecodeStep:
         defer = pa.world_size == 1 and self.defer_splitk
         delta = L["o"].forward(attn, out=ln.o_buf, reduce=False, defer_splitk=defer)
         pend = self._reduce_add_norm(ln, 0, delta, L["post_norm"], L["o"].deferred if defer else None)
-        if L["gate_up"].paired:  # SiLU*mul in the GEMM epilogue
-            self._norm_then(ln, L["gate_up"], pend, ln.act)
+        act = ln.act
+        if L["gate_up"].paired:  # SiLU*mul in the GEMM epilogue; fuse_act_quant: which also quantises for down
+            act = ln.act_q if self.fuse_act_quant else ln.act
+            self._norm_then(ln, L["gate_up"], pend, act)
         else:
             gu = self._norm_then(ln, L["gate_up"], pend, ln.gate_up)
             kernels.silu_and_mul(ln.act, gu)
-        delta = L["down"].forward(ln.act, out=ln.down_buf, reduce=False, defer_splitk=defer)
-        nxt = self.layers[li + 1]["in_norm"] if li + 1 < len(self.layers) else self.final_norm
-        ln.pend = self._reduce_add_norm(ln, 1, delta, nxt, L["down"].deferred if defer else None)
+        delta = L["down"].forward(act, out=ln.down_buf, reduce=False, defer_splitk=defer)
+        last = li + 1 == len(self.layers)
+        nxt = self.final_norm if last else self.layers[li + 1]["in_norm"]
+        ln.pend = self._reduce_add_norm(ln, 1, delta, nxt, L["down"].deferred if defer else None, final=last)
 
     def _first_norm(self, ln) -> None:
         # A norm that has not run yet: (x, deferred slabs of x or None, residual or None, weight).
@@ -748,7 +772,7 @@ class LlamaDecodeStep:
                         self._pre_attn(ln, li + 1)
         with on(l1):
             if l1.pend is not None:
-                self._run_norm(l1, l1.pend)
+                self._run_norm(l1, l1.pend, final=True)
                 l1.pend = None
         join = torch.cuda.Event()
         join.record(side)
@@ -771,7 +795,7 @@ class LlamaDecodeStep:
                 self._post_attn(ln, li)
         for ln in lanes:
             if ln.pend is not None:  # the final norm has no projection of ours behind it
-                self._run_norm(ln, ln.pend)
+                self._run_norm(ln, ln.pend, final=True)
 
     def _trunk(self, tokens: torch.Tensor, positions: torch.Tensor, params: InputParameters):
         """Embedding and the decoder stack: the final-norm output of all T rows ([T, hidden], a view of the

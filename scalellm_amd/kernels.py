@@ -1112,9 +1112,23 @@ def quantize_mxfp4_act(a: torch.Tensor, aq: Optional[torch.Tensor] = None, a_sca
     return aq, a_scale
 
 
-def _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce: bool, silu_mul: bool):
+def _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce: bool, silu_mul: bool, c_scale=None, dtype=None):
     """Checks and argument block of w4a4_linear() and its plan query: the mxfp4_linear block (over T activations, or
-    with a_scale over their code bytes) plus the activations' block scales"""
+    with a_scale over their code bytes) plus the activations' block scales.  With c_scale (slm_w4a4q_linear) `c` holds
+    code bytes: the block is built over a T stand-in of the SiLU * mul output, then pointed at `c`."""
+    c_codes = None
+    if c_scale is not None:
+        _require_gpu(c, c_scale)
+        if not silu_mul or defer_reduce or bias is not None:
+            raise SlmError("c_scale (MXFP4 output) needs silu_mul=True, no bias and no defer_reduce")
+        dt = a.dtype if a_scale is None else dtype
+        if dt not in (torch.float16, torch.bfloat16):
+            raise SlmError("MXFP4 output from pre-quantised activations needs dtype=torch.float16 / torch.bfloat16")
+        if c.dtype != torch.uint8 or c_scale.dtype != torch.uint8 or c.dim() != 2 or c_scale.dim() != 2 or \
+                c.stride(1) != 1 or c_scale.stride(1) != 1 or c.size(1) % (MXFP4_BLOCK // 2) or \
+                tuple(c_scale.shape) != (c.size(0), c.size(1) // (MXFP4_BLOCK // 2)):
+            raise SlmError("MXFP4 output is uint8 codes [M, N/4] with uint8 scales [M, N/64], contiguous rows")
+        c_codes, c = c, torch.empty(1, 2 * c.size(1), dtype=dt, device=c.device).expand(c.size(0), -1)
     if a_scale is None:
         g0 = _mxfp4_args(a, w, w_scale, c, bias, defer_reduce, silu_mul)
     else:
@@ -1133,27 +1147,79 @@ def _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce: bool, silu_mul: bo
         g.a_scale, g.ldas = a_scale.data_ptr(), a_scale.stride(0)
     else:
         g.a_scale, g.ldas = None, 0
+    if c_codes is not None:
+        g.c, g.ldc = c_codes.data_ptr(), c_codes.stride(0)
     return g
 
 
 def w4a4_linear_plan(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
                      bias: Optional[torch.Tensor] = None, defer_reduce: bool = False, silu_mul: bool = False,
-                     a_scale: Optional[torch.Tensor] = None) -> "_lib.LinearPlanInfo":
+                     a_scale: Optional[torch.Tensor] = None, c_scale: Optional[torch.Tensor] = None,
+                     dtype: Optional[torch.dtype] = None) -> "_lib.LinearPlanInfo":
     """The launch w4a4_linear() would give these very arguments now (slm_w4a4_linear_plan, under the SLM_W4A4_*
-    knobs); a host-side query."""
-    return _linear_plan("slm_w4a4_linear", _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce, silu_mul))
+    knobs; with c_scale slm_w4a4q_linear_plan); a host-side query."""
+    g = _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce, silu_mul, c_scale, dtype)
+    return _linear_plan("slm_w4a4_linear" if c_scale is None else "slm_w4a4q_linear", g)
 
 
 def w4a4_linear(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
                 bias: Optional[torch.Tensor] = None, silu_mul: bool = False, defer_reduce: bool = False,
-                a_scale: Optional[torch.Tensor] = None) -> DeferredPartials:
+                a_scale: Optional[torch.Tensor] = None, c_scale: Optional[torch.Tensor] = None,
+                dtype: Optional[torch.dtype] = None) -> DeferredPartials:
     """MXFP4 x MXFP4 linear on the block-scaled MFMA: C[M, N] = T(sum_k a[m, k] w[n, k] + bias), a and w the
     dequantised values of two MXFP4 tensors, fp32 accumulate, one rounding.  `w` / `w_scale` are mxfp4_linear's
     checkpoint tensors.  Activations: `a` in f16 / bf16 [M, K], quantised by the kernel as it loads them (a_scale
     None) -- or the quantize_mxfp4_act pair, `a` uint8 [M, K/2] with `a_scale` uint8 [M, K/32]; the two give the same
-    bits.  defer_reduce, silu_mul and the returned handle: as linear()."""
-    return _run_linear("slm_w4a4_linear", _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce, silu_mul),
-                       c.device, defer_reduce)
+    bits.  defer_reduce, silu_mul and the returned handle: as linear().
+
+    c_scale (with silu_mul=True, no bias, no defer_reduce; anything else raises SlmError): the SiLU * mul output is
+    written as the next GEMM's MXFP4 input -- `c` uint8 [M, N/4] codes (row stride a multiple of 16), `c_scale` uint8
+    [M, N/64] -- byte for byte quantize_mxfp4_act of what the call without c_scale writes (slm_w4a4q_linear).  With
+    pre-quantised `a` no tensor carries the type that output is rounded to in between: name it with `dtype`."""
+    g = _w4a4_args(a, a_scale, w, w_scale, c, bias, defer_reduce, silu_mul, c_scale, dtype)
+    if c_scale is not None:
+        if g.M:
+            check(_lib.lib().slm_w4a4q_linear(C.byref(g), c_scale.data_ptr(), c_scale.stride(0), _stream()),
+                  "slm_w4a4q_linear")
+        return DeferredPartials()
+    return _run_linear("slm_w4a4_linear", g, c.device, defer_reduce)
+
+
+def rms_norm_mxfp4(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None,
+                   partials: Optional[DeferredPartials] = None, aq: Optional[torch.Tensor] = None,
+                   a_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """rms_norm() whose output is the next W4A4 GEMM's pre-quantised side, in one launch: (aq uint8 [T, dim/2],
+    a_scale uint8 [T, dim/32]), byte for byte quantize_mxfp4_act(rms_norm(...)) (slm_rms_norm_mxfp4[_splitk]).
+    dim % 32 == 0.  residual and partials: as rms_norm (the residual is updated the same way; with a truthy handle
+    `x` was not written and only gives shape and dtype).  `aq` / `a_scale` may be given (row strides: a multiple of
+    16 / any); `out` (contiguous, like x) also receives rms_norm's own T output, bit for bit."""
+    L = _lib.lib()
+    _require_gpu(x, weight, residual, aq, a_scale, out)
+    if not (x.is_contiguous() and weight.is_contiguous()) or (residual is not None and not residual.is_contiguous()) \
+            or (out is not None and not (out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype)):
+        raise SlmError("rms_norm_mxfp4 needs contiguous tensors (out: x's shape and dtype)")
+    dim = x.size(-1)
+    T = x.numel() // dim
+    if dim % MXFP4_BLOCK:
+        raise SlmError("rms_norm_mxfp4 needs dim % 32 == 0")
+    if aq is None:
+        aq = torch.empty(T, dim // 2, dtype=torch.uint8, device=x.device)
+    if a_scale is None:
+        a_scale = torch.empty(T, dim // MXFP4_BLOCK, dtype=torch.uint8, device=x.device)
+    for t, cols, what in ((aq, dim // 2, "aq"), (a_scale, dim // MXFP4_BLOCK, "a_scale")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (T, cols) or t.stride(1) != 1:
+            raise SlmError(f"{what} must be uint8 [{T}, {cols}] with contiguous rows")
+    head = (aq.data_ptr(), aq.stride(0), a_scale.data_ptr(), a_scale.stride(0), out.data_ptr() if out is not None else None)
+    tail = (weight.data_ptr(), residual.data_ptr() if residual is not None else None, T, dim, float(eps), _dtype_code(x),
+            _stream())
+    if partials:
+        if not isinstance(partials, DeferredPartials):
+            raise SlmError("rms_norm_mxfp4(partials=...) takes the handle a defer_reduce=True GEMM returned")
+        partials.check(x.device, x.numel(), "rms_norm_mxfp4(partials=...)")
+        check(L.slm_rms_norm_mxfp4_splitk(*head, partials.ptr, partials.splits, *tail), "slm_rms_norm_mxfp4_splitk")
+    else:
+        check(L.slm_rms_norm_mxfp4(*head, x.data_ptr(), *tail), "slm_rms_norm_mxfp4")
+    return aq, a_scale
 
 
 # ---------------------------------------------------------------------------------------

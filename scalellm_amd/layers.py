@@ -709,7 +709,9 @@ class _Mxfp4LinearMixin:
 
     act_quant=None is W4A16 (kernels.mxfp4_linear).  act_quant="mxfp4" quantises the activations to MXFP4 as they are
     loaded, dynamically per block of 32 k, and runs the block-scaled MFMA (kernels.w4a4_linear, its T side: the same
-    single launch) -- the arithmetic of checkpoints calibrated with MXFP4 activations."""
+    single launch) -- the arithmetic of checkpoints calibrated with MXFP4 activations.  There the input may also be
+    the pair (aq, a_scale) a producer already quantised, and a paired layer's `out` the pair (codes, scales)
+    (_linear_fused_quant): the same bits, with the quantiser out of the multiplying wave."""
 
     weight_scale: Optional[torch.Tensor] = None
     act_quant: Optional[str] = None
@@ -760,13 +762,38 @@ class _Mxfp4LinearMixin:
     def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor],
                 defer_splitk: bool = False) -> torch.Tensor:
         self.verify_loaded_weights()
-        x2 = x.reshape(-1, x.size(-1))
         n_out = self.local_out // 2 if self.paired else self.local_out
+        if isinstance(x, tuple) or isinstance(out, tuple):
+            return self._linear_fused_quant(x, bias, out, n_out, defer_splitk)
+        x2 = x.reshape(-1, x.size(-1))
         if out is None:
             out = torch.empty(x2.size(0), n_out, dtype=x.dtype, device=x.device)
         run = kernels.w4a4_linear if self.act_quant == "mxfp4" else kernels.mxfp4_linear
         self.deferred = run(x2, self.weight, self.weight_scale, out, bias,
                             defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
+        self.deferred_splits = int(self.deferred)
+        return out
+
+    def _linear_fused_quant(self, x, bias, out, n_out: int, defer_splitk: bool):
+        """act_quant="mxfp4" with the quantiser in the neighbours (slm_hip.h section 24).  `x` may be the pair (aq
+        uint8 [M, K/2], a_scale uint8 [M, K/32]) a producer left (kernels.rms_norm_mxfp4, quantize_mxfp4_act, a paired
+        layer): the GEMM takes its pre-quantised side.  On a paired (gate | up) layer `out` may be the pair (codes
+        uint8 [M, N/4], scales uint8 [M, N/64]), N = this layer's rows: the SiLU * mul output is written as the next
+        layer's MXFP4 input and the pair is returned.  The bits are those of the plain call forms."""
+        if self.act_quant != "mxfp4":
+            raise ValueError("MXFP4 activations in or out need act_quant='mxfp4'")
+        a, a_scale = x if isinstance(x, tuple) else (x.reshape(-1, x.size(-1)), None)
+        if isinstance(out, tuple):
+            if not self.paired:
+                raise ValueError("only a paired (act_mul='silu') layer can write its output as MXFP4")
+            kernels.w4a4_linear(a, self.weight, self.weight_scale, out[0], bias, silu_mul=True, a_scale=a_scale,
+                                c_scale=out[1], dtype=self.dtype)
+            self.deferred, self.deferred_splits = kernels.DeferredPartials(), 0
+            return out
+        if out is None:
+            out = torch.empty(a.size(0), n_out, dtype=self.dtype, device=a.device)
+        self.deferred = kernels.w4a4_linear(a, self.weight, self.weight_scale, out, bias, a_scale=a_scale,
+                                            defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
         self.deferred_splits = int(self.deferred)
         return out
 
