@@ -1909,6 +1909,72 @@ SLM_API int slm_rms_norm_mxfp4_splitk(void* aq, int64_t ldaq, uint8_t* a_scale, 
 SLM_API int slm_w4a4q_linear(const slm_w4a4_linear_args* a, uint8_t* c_scale, int64_t ldcs, void* stream);
 SLM_API int slm_w4a4q_linear_plan(const slm_w4a4_linear_args* a, slm_linear_plan_info* out);
 
+/* ========================================================================== */
+/* 25. fp8 x fp8 linear (W8A8) on the 32x32x64 fp8 MFMA                       */
+/*    Section 15's checkpoint weights (e4m3, one scale per output channel)    */
+/*    against e4m3 activations with one scale per token -- the "FP8 dynamic"  */
+/*    arithmetic of compressed-tensors, Quark and vLLM exports:               */
+/*      a[m, k] = e4m3(Aq[m, k]),  w[n, k] = e4m3(W[n, k])   (OCP e4m3fn)     */
+/*      acc_s   = sum over k in K slice s of a[m, k] * w[n, k]                */
+/*                (fp32; every product is exact)                              */
+/*      y_s     = (acc_s * a_scale[m]) * w_scale[n]    two fp32 multiplies,   */
+/*                this order, never contracted                                */
+/*      C[m, n] = T( y_0 + y_1 + ... (slice order) + bias[n] )  ONE rounding  */
+/*    v_mfma_f32_32x32x64_f8f6f4 takes the e4m3 bytes of both operands as     */
+/*    they lie in memory: no converts.  The NaN codes 0x7F / 0xFF poison      */
+/*    their row / column.                                                     */
+/*    Activation quantiser (slm_w8a8_quantize_act): A [M, K] T (row stride    */
+/*    lda elements, % 8, base 16-byte aligned) -> Aq [M, K] bytes (row stride */
+/*    ldaq bytes, >= K, % 16, base 16-byte aligned) and a_scale [M] fp32.     */
+/*    Dynamic form (static_scale == NULL), per row: s = amax / 448 (IEEE fp32 */
+/*    division), an all-zero row s = 1.0, a row holding inf or NaN s = NaN    */
+/*    and every code 0x7F; elements fp32(x) / s (IEEE fp32 division) clamped  */
+/*    to +-448 and rounded to nearest even onto e4m3fn -- exactly             */
+/*    (x.float() / s).clamp(-448, 448).to(torch.float8_e4m3fn); a value that  */
+/*    rounds to zero keeps its sign.  Static form (static_scale: one fp32 on  */
+/*    the device, a checkpoint's input_scale): the same rule per element with */
+/*    s = *static_scale, and a_scale[m] = s for every row, so the GEMM has    */
+/*    one form.  K % 32 == 0, K <= 32768 (else SLM_ERR_UNSUPPORTED): the row  */
+/*    is read once and held in registers between the amax and the convert.    */
+/*    ONE launch, no workspace, capturable; M == 0 is SLM_OK without one.     */
+/*    The GEMM: slm_w8a8_linear_args is slm_fp8_linear_args field for field   */
+/*    (a: e4m3 BYTES, lda in bytes, >= K, % 16, base 16-byte aligned; dtype:  */
+/*    the type of bias and c) plus a_scale ([M] fp32, NULL = 1.0).  W, ldw,   */
+/*    w_scale ([N] fp32, 16-byte aligned, NULL = 1.0), bias, C, ldc, shapes   */
+/*    (K % 32 == 0, N % 32 == 0, N % 64 with SLM_LINEAR_SILU_MUL), flags      */
+/*    (SLM_LINEAR_*), error codes, "all validation before any launch",        */
+/*    M == 0, the K slices and the workspace ([split_k][M][N] fp32 slabs,     */
+/*    ALREADY scaled by both scale vectors: the reduce launch and every       */
+/*    deferred consumer of section 13 work unchanged) are section 15's.  The  */
+/*    plan is section 13's function of (M, N, K, dtype, flags, bias) under    */
+/*    knobs of its own: SLM_W8A8_SPLITK / _RT / _NW; it is reported through   */
+/*    slm_linear_plan_info (lds_bytes: 2 * 32 * row_tiles * 128), whose       */
+/*    workspace_bytes is the size to pass: there is no workspace query of its */
+/*    own.  Launch shape, unit order, tail: csrc/w8a8.hip.                    */
+/* ========================================================================== */
+typedef struct slm_w8a8_linear_args {
+  const void* a;        /* [M, K] e4m3fn bytes, row stride lda (bytes)        */
+  const void* w;        /* [N, K] e4m3fn bytes, row stride ldw                */
+  const void* bias;     /* [N] T or NULL                                      */
+  void* c;              /* [M, N] T ([M, N/2] with SLM_LINEAR_SILU_MUL), row stride ldc */
+  int64_t M, K, N;
+  int64_t lda, ldw, ldc;
+  int32_t dtype;        /* of bias and c                                      */
+  int32_t flags;        /* SLM_LINEAR_* bits, 0 = none                        */
+  void* workspace;      /* split-K slabs                                      */
+  size_t workspace_bytes;
+  const float* w_scale; /* [N] fp32 or NULL (= 1.0); everything above is slm_fp8_linear_args, field for field */
+  const float* a_scale; /* [M] fp32 or NULL (= 1.0): one scale per token      */
+} slm_w8a8_linear_args;
+
+SLM_API int slm_w8a8_quantize_act(const void* a, int64_t lda, void* aq, int64_t ldaq, float* a_scale,
+                                  const float* static_scale /* or NULL */, int64_t M, int64_t K, int32_t dtype,
+                                  void* stream);
+/* As slm_linear_plan / _deferred_splits / slm_linear (section 13); the plan is a pure host function. */
+SLM_API int slm_w8a8_linear_plan(const slm_w8a8_linear_args* a, slm_linear_plan_info* out);
+SLM_API int32_t slm_w8a8_linear_deferred_splits(const slm_w8a8_linear_args* a);
+SLM_API int slm_w8a8_linear(const slm_w8a8_linear_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

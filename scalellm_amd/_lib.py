@@ -272,6 +272,12 @@ class W4A4LinearArgs(C.Structure):
     _fields_ = Mxfp4LinearArgs._fields_ + [("a_scale", C.c_void_p), ("ldas", C.c_int64)]
 
 
+class W8A8LinearArgs(C.Structure):
+    """struct slm_w8a8_linear_args (include/slm_hip.h section 25): slm_fp8_linear_args, field for field (a: e4m3 bytes,
+    lda in bytes), plus the activations' per-token scales (NULL: 1.0)."""
+    _fields_ = Fp8LinearArgs._fields_ + [("a_scale", C.c_void_p)]
+
+
 class LinearPlanInfo(C.Structure):
     """struct slm_linear_plan_info (include/slm_hip.h section 13)."""
     _fields_ = [
@@ -473,6 +479,13 @@ def lib() -> C.CDLL:
           C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_void_p]),
         ("slm_w4a4q_linear", C.c_int, [C.POINTER(W4A4LinearArgs), C.c_void_p, C.c_int64, C.c_void_p]),
         ("slm_w4a4q_linear_plan", C.c_int, [C.POINTER(W4A4LinearArgs), C.POINTER(LinearPlanInfo)]),
+        # section 25: (a, lda, aq, ldaq, a_scale, static_scale, M, K, dtype, stream)
+        ("slm_w8a8_quantize_act", C.c_int,
+         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+          C.c_void_p]),
+        ("slm_w8a8_linear", C.c_int, [C.POINTER(W8A8LinearArgs), C.c_void_p]),
+        ("slm_w8a8_linear_deferred_splits", C.c_int32, [C.POINTER(W8A8LinearArgs)]),
+        ("slm_w8a8_linear_plan", C.c_int, [C.POINTER(W8A8LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

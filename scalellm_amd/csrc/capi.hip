@@ -24,6 +24,7 @@ const char* const kTuneNames[TUNE_COUNT] = {
     "SLM_W4_XL_SK",
     "SLM_LINEAR_SPLITK",    "SLM_LINEAR_RT",        "SLM_LINEAR_NW",
     "SLM_W4A4_SPLITK",      "SLM_W4A4_RT",          "SLM_W4A4_NW",
+    "SLM_W8A8_SPLITK",      "SLM_W8A8_RT",          "SLM_W8A8_NW",
 };
 std::atomic<int32_t> g_tune[TUNE_COUNT];
 std::once_flag g_tune_once;

@@ -1,7 +1,7 @@
 // dense_plan.h -- the launch plan of dense.hip's three entries (slm_linear, slm_fp8_linear, slm_mxfp4_linear;
 // include/slm_hip.h sections 13, 15 and 20), over any of the argument structs: slm_fp8_linear_args and
-// slm_mxfp4_linear_args are slm_linear_args, field for field, plus their scales.  w4a4.hip (section 22) takes the same
-// plan under knobs of its own.  Host only.
+// slm_mxfp4_linear_args are slm_linear_args, field for field, plus their scales.  w4a4.hip (section 22) and w8a8.hip
+// (section 25) take the same plan under knobs of their own.  Host only.
 #pragma once
 #include "common.h"
 #include "tuning.h"

@@ -53,6 +53,9 @@ enum TuneKey : int {
   TUNE_W4A4_SPLITK,       // SLM_W4A4_SPLITK       forced K slices of the MXFP4 x MXFP4 linear (1..16; every slice keeps >= 1 chunk)
   TUNE_W4A4_RT,           // SLM_W4A4_RT           forced 32-row accumulator tiles per wave of the MXFP4 x MXFP4 linear (1/2/4)
   TUNE_W4A4_NW,           // SLM_W4A4_NW           forced waves per workgroup of the MXFP4 x MXFP4 linear (1/2/4; raised to the row tiles)
+  TUNE_W8A8_SPLITK,       // SLM_W8A8_SPLITK       forced K slices of the fp8 x fp8 linear (1..16; every slice keeps >= 1 chunk)
+  TUNE_W8A8_RT,           // SLM_W8A8_RT           forced 32-row accumulator tiles per wave of the fp8 x fp8 linear (1/2/4)
+  TUNE_W8A8_NW,           // SLM_W8A8_NW           forced waves per workgroup of the fp8 x fp8 linear (1/2/4; raised to the row tiles)
   TUNE_COUNT
 };
 

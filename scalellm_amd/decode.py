@@ -180,8 +180,12 @@ class LlamaDecodeStep:
         pa = parallel_args or ParallelArgs()
         # act_quant "mxfp4" (with quant_method "mxfp4" only): the four linears quantise their activations to MXFP4 as
         # they load them and run the block-scaled MFMA (kernels.w4a4_linear): W4A4, no launch more than W4A16
-        if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
-            raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
+        # act_quant "fp8" (with quant_method "fp8" only): every linear quantises its input to e4m3 with one dynamic scale
+        # per token (kernels.quantize_fp8_act: one launch per distinct input) and runs the fp8 MFMA
+        # (kernels.w8a8_linear): W8A8
+        if act_quant is not None and (act_quant not in ("mxfp4", "fp8") or quant_method != act_quant):
+            raise ValueError(f"act_quant={act_quant!r} must be None, 'mxfp4' (with quant_method='mxfp4') or 'fp8' "
+                             "(with quant_method='fp8')")
         self.act_quant = act_quant
         # fuse_act_quant (act_quant "mxfp4" only, off by default): the producers quantise -- the RMSNorm in front of
         # qkv and gate_up writes MXFP4 (kernels.rms_norm_mxfp4), the gate_up GEMM's SiLU * mul epilogue writes MXFP4

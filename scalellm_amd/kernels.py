@@ -887,15 +887,15 @@ def linear_plan(a: torch.Tensor, weight: torch.Tensor, c: torch.Tensor, bias: Op
 
 
 def _run_linear(entry: str, g, dev: torch.device, defer_reduce: bool) -> DeferredPartials:
-    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear / slm_mxfp4_linear / slm_w4a4_linear
-    (`entry`) over the
-    argument block g"""
+    """Workspace, launch and deferred-slab handle of slm_linear / slm_fp8_linear / slm_mxfp4_linear / slm_w4a4_linear /
+    slm_w8a8_linear (`entry`) over the argument block g"""
     L = _lib.lib()
     if g.M == 0:
         return DeferredPartials()
     deferred = getattr(L, entry + "_deferred_splits")(C.byref(g)) if defer_reduce else 0
-    # (sections 20 and 22 declare no _workspace_bytes query: the plan carries the size)
-    need = _linear_plan(entry, g).workspace_bytes if entry in ("slm_mxfp4_linear", "slm_w4a4_linear") else \
+    # (sections 20, 22 and 25 declare no _workspace_bytes query: the plan carries the size)
+    need = _linear_plan(entry, g).workspace_bytes \
+        if entry in ("slm_mxfp4_linear", "slm_w4a4_linear", "slm_w8a8_linear") else \
         getattr(L, entry + "_workspace_bytes")(C.byref(g))
     ws = None
     if need:
@@ -965,6 +965,90 @@ def fp8_linear(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[torch.Tensor
     registers; `w_scale` fp32 [N] or None (1.0).  defer_reduce, silu_mul and the returned handle: as linear()."""
     return _run_linear("slm_fp8_linear", _linear_args(a, w8, w_scale, c, bias, defer_reduce, silu_mul, fp8=True),
                        a.device, defer_reduce)
+
+
+# ---------------------------------------------------------------------------------------
+# fp8 x fp8 linear on the 32x32x64 fp8 MFMA (W8A8): slm_hip.h section 25
+# ---------------------------------------------------------------------------------------
+def quantize_fp8_act(a: torch.Tensor, static_scale: Optional[torch.Tensor] = None, aq: Optional[torch.Tensor] = None,
+                     a_scale: Optional[torch.Tensor] = None):
+    """Per-token fp8 quantisation of activations A [M, K] (f16 / bf16, K % 32 == 0, K <= 32768, rows contiguous) on
+    the GPU, one launch that reads every row once: (aq float8_e4m3fn [M, K], a_scale fp32 [M]).  Dynamic form: per row
+    s = amax / 448 (an all-zero row 1.0, a row holding inf or NaN: NaN and every code 0x7F) and
+    aq = (a.float() / s).clamp(-448, 448).to(float8_e4m3fn), bit for bit.  `static_scale` (one fp32 on the device: a
+    checkpoint's input_scale) replaces s for every row; a_scale is then that value repeated, so w8a8_linear has one
+    form.  `aq` (float8_e4m3fn or uint8, row stride a multiple of 16) / `a_scale` may be given."""
+    _require_gpu(a, static_scale, aq, a_scale)
+    if a.dim() != 2 or a.stride(1) != 1 or a.size(1) % 32:
+        raise SlmError("quantize_fp8_act takes A [M, K] with contiguous rows and K % 32 == 0")
+    M, K = a.shape
+    if static_scale is not None and (static_scale.dtype != torch.float32 or static_scale.numel() != 1):
+        raise SlmError("static_scale must be one fp32 value on the device")
+    if aq is None:
+        aq = torch.empty(M, K, dtype=torch.float8_e4m3fn, device=a.device)
+    if a_scale is None:
+        a_scale = torch.empty(M, dtype=torch.float32, device=a.device)
+    if aq.dtype not in (torch.float8_e4m3fn, torch.uint8) or tuple(aq.shape) != (M, K) or aq.stride(1) != 1:
+        raise SlmError(f"aq must be float8_e4m3fn (or uint8) [{M}, {K}] with contiguous rows")
+    if a_scale.dtype != torch.float32 or tuple(a_scale.shape) != (M,) or not a_scale.is_contiguous():
+        raise SlmError(f"a_scale must be a contiguous fp32 [{M}] tensor")
+    check(_lib.lib().slm_w8a8_quantize_act(a.data_ptr(), a.stride(0), aq.data_ptr(), aq.stride(0), a_scale.data_ptr(),
+                                           static_scale.data_ptr() if static_scale is not None else None, M, K,
+                                           _dtype_code(a), _stream()), "slm_w8a8_quantize_act")
+    return aq, a_scale
+
+
+def _w8a8_args(aq, a_scale, w8, w_scale, c, bias, defer_reduce: bool, silu_mul: bool):
+    """Checks and argument block of w8a8_linear() and its plan query; nothing is allocated"""
+    _require_gpu(aq, a_scale, w8, w_scale, c, bias)
+    if silu_mul and defer_reduce:
+        raise SlmError("silu_mul and defer_reduce cannot be combined")
+    fp8 = (torch.float8_e4m3fn, torch.uint8)
+    if aq.dtype not in fp8 or w8.dtype not in fp8:
+        raise SlmError(f"w8a8_linear takes float8_e4m3fn activations and weights (or their bytes), not {aq.dtype} / {w8.dtype}")
+    if aq.dim() != 2 or c.dim() != 2 or w8.dim() != 2 or aq.stride(1) != 1 or c.stride(1) != 1 or w8.stride(1) != 1:
+        raise SlmError("Aq [M, K], W [N, K] and C [M, N] must be 2-D with contiguous rows")
+    (M, K), N = aq.shape, w8.size(0)
+    if w8.size(1) != K or tuple(c.shape) != (M, N // 2 if silu_mul else N):
+        raise SlmError("w8a8_linear shape mismatch")
+    if c.dtype not in (torch.float16, torch.bfloat16) or (bias is not None and bias.dtype != c.dtype):
+        raise SlmError("the output is f16 / bf16 and the bias shares its dtype")
+    if bias is not None and (bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous()):
+        raise SlmError("bias must be a contiguous [N] tensor")
+    for t, n, what in ((a_scale, M, "a_scale must be a contiguous fp32 [M] tensor"),
+                       (w_scale, N, "w_scale must be a contiguous fp32 [N] tensor (expand a per-tensor scale on the host)")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise SlmError(what)
+    g = _lib.W8A8LinearArgs()
+    g.a, g.w, g.c = aq.data_ptr(), w8.data_ptr(), c.data_ptr()
+    g.bias, g.a_scale, g.w_scale = (t.data_ptr() if t is not None else None for t in (bias, a_scale, w_scale))
+    g.M, g.K, g.N = M, K, N
+    g.lda, g.ldw, g.ldc = aq.stride(0), w8.stride(0), c.stride(0)
+    g.dtype = _dtype_code(c)
+    g.flags = (_lib.SLM_LINEAR_SHARES_CHIP if _chip_flag() else 0) | (_lib.SLM_LINEAR_SILU_MUL if silu_mul else 0) | \
+        (_lib.SLM_LINEAR_DEFER_REDUCE if defer_reduce else 0)
+    g.workspace, g.workspace_bytes = None, 0
+    return g
+
+
+def w8a8_linear_plan(aq: torch.Tensor, a_scale: Optional[torch.Tensor], w8: torch.Tensor,
+                     w_scale: Optional[torch.Tensor], c: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                     silu_mul: bool = False, defer_reduce: bool = False) -> "_lib.LinearPlanInfo":
+    """The launch w8a8_linear() would give these very arguments now (slm_w8a8_linear_plan, under the SLM_W8A8_*
+    knobs); a host-side query."""
+    return _linear_plan("slm_w8a8_linear", _w8a8_args(aq, a_scale, w8, w_scale, c, bias, defer_reduce, silu_mul))
+
+
+def w8a8_linear(aq: torch.Tensor, a_scale: Optional[torch.Tensor], w8: torch.Tensor, w_scale: Optional[torch.Tensor],
+                c: torch.Tensor, bias: Optional[torch.Tensor] = None, silu_mul: bool = False,
+                defer_reduce: bool = False) -> DeferredPartials:
+    """fp8 x fp8 linear on the fp8 MFMA: C[M, N] = T(((e4m3(Aq[M, K]) . e4m3(W8[N, K])^T) * a_scale[M]) * w_scale[N] +
+    bias), fp32 accumulate, the two scales applied to the fp32 sum in that order, one rounding to `c`'s dtype.  `aq` /
+    `a_scale` are quantize_fp8_act's pair (float8_e4m3fn [M, K], row stride a multiple of 16; fp32 [M] or None = 1.0),
+    `w8` / `w_scale` fp8_linear's checkpoint tensors; nothing is converted.  defer_reduce, silu_mul and the returned
+    handle: as linear()."""
+    return _run_linear("slm_w8a8_linear", _w8a8_args(aq, a_scale, w8, w_scale, c, bias, defer_reduce, silu_mul),
+                       c.device, defer_reduce)
 
 
 # ---------------------------------------------------------------------------------------

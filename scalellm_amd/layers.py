@@ -579,11 +579,41 @@ class _Fp8LinearMixin:
     """What the two fp8 classes add to _LinearBase: `weight` is the checkpoint's float8_e4m3fn tensor, kept as bytes
     and never converted (kernels.fp8_linear streams it as it is); `weight_scale` arrives 0-d, [1], [N] or [N, 1]
     in any float dtype and is kept as fp32 [local_out], one scale per output channel (a per-tensor scale is
-    expanded, in a fused load per shard).  An `input_scale` key is ignored: activations stay f16 / bf16.  A weight
-    of any other dtype is an error -- quantising is the checkpoint's job (kernels.quantize_fp8_weight), not a
-    side effect of loading."""
+    expanded, in a fused load per shard).  A weight of any other dtype is an error -- quantising is the checkpoint's
+    job (kernels.quantize_fp8_weight), not a side effect of loading.
+
+    act_quant=None is W8A16 (kernels.fp8_linear): activations stay f16 / bf16 and an `input_scale` key is ignored.
+    act_quant="fp8" quantises the activations to e4m3 with one scale per token (kernels.quantize_fp8_act, one launch)
+    and runs the fp8 MFMA (kernels.w8a8_linear): W8A8, the arithmetic of "FP8 dynamic" checkpoints.  A loaded
+    `input_scale` (one value; the shards of a fused load bring one each and the largest is kept, as vLLM does) selects
+    the static form: that scale for every token."""
 
     weight_scale: Optional[torch.Tensor] = None
+    input_scale: Optional[torch.Tensor] = None
+    act_quant: Optional[str] = None
+
+    def __init__(self, *args, act_quant: Optional[str] = None, **kw):
+        if act_quant not in (None, "fp8"):
+            raise ValueError(f"act_quant must be None or 'fp8', not {act_quant!r}")
+        super().__init__(*args, **kw)
+        self.act_quant = act_quant
+        self._input_scale_keys = set()
+
+    def _load_input_scale(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        """W8A8 only: the checkpoint's static activation scale, fp32 [1] on the device"""
+        if self.act_quant != "fp8":
+            return
+        for key in [p + "input_scale" for p in (prefixes or [""])]:
+            if key not in sd:
+                continue
+            t = sd[key]
+            if key in self._input_scale_keys:   # as weight_scale: a second checkpoint never mixes into the first
+                raise RuntimeError(f"{key} is loaded twice")
+            self._input_scale_keys.add(key)
+            if not t.is_floating_point() or t.numel() != 1:
+                raise ValueError(f"{key} must be one float value, not {tuple(t.shape)} {t.dtype}")
+            t = t.reshape(1).to(device=self.device, dtype=torch.float32)
+            self.input_scale = t if self.input_scale is None else torch.maximum(self.input_scale, t)
 
     def _set(self, name: str, t: torch.Tensor) -> None:
         if name == "weight":
@@ -621,11 +651,13 @@ class _Fp8LinearMixin:
         self._set("weight_scale", self._shard(full, dim, "weight_scale"))
 
     def load_shard(self, weight: torch.Tensor, weight_scale: torch.Tensor,  # noqa: D401
-                   bias: Optional[torch.Tensor] = None) -> None:
+                   bias: Optional[torch.Tensor] = None, input_scale: Optional[torch.Tensor] = None) -> None:
         """THIS rank's shard, already cut: float8_e4m3fn weight [local_out, local_in] and its scale
-        (per tensor or [local_out])."""
+        (per tensor or [local_out]); with act_quant="fp8" also the checkpoint's input_scale, if it has one."""
         if self.weight_scale is not None:
             raise RuntimeError("weight_scale is loaded twice")
+        if input_scale is not None:
+            self._load_input_scale({"input_scale": input_scale})
         super().load_shard(weight, bias)
         self._set("weight_scale", self._channel_scale(weight_scale, self.local_out, "weight_scale"))
 
@@ -641,8 +673,13 @@ class _Fp8LinearMixin:
         n_out = self.local_out // 2 if self.paired else self.local_out
         if out is None:
             out = torch.empty(x2.size(0), n_out, dtype=x.dtype, device=x.device)
-        self.deferred = kernels.fp8_linear(x2, self.weight, self.weight_scale, out, bias,
-                                           defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
+        if self.act_quant == "fp8":
+            aq, a_scale = kernels.quantize_fp8_act(x2, self.input_scale)
+            self.deferred = kernels.w8a8_linear(aq, a_scale, self.weight, self.weight_scale, out, bias,
+                                                defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
+        else:
+            self.deferred = kernels.fp8_linear(x2, self.weight, self.weight_scale, out, bias,
+                                               defer_reduce=defer_splitk and not self.paired, silu_mul=self.paired)
         self.deferred_splits = int(self.deferred)
         return out
 
@@ -653,6 +690,7 @@ class ColumnParallelFp8Linear(_Fp8LinearMixin, ColumnParallelLinear):
     gate | up keep their per-tensor scales."""
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
+        self._load_input_scale(sd, prefixes)
         if not prefixes:
             self._load_one(sd, "weight", 0)
             self._load_scale(sd, self.out_features, 0)
@@ -691,6 +729,7 @@ class RowParallelFp8Linear(_Fp8LinearMixin, RowParallelLinear):
     def load_state_dict(self, sd: Dict[str, torch.Tensor], prefixes=None) -> None:
         if prefixes:
             raise ValueError("row-parallel linears are never fused (parallel_linear.h:28-33)")
+        self._load_input_scale(sd)
         self._load_one(sd, "weight", 1)
         self._load_scale(sd, self.out_features, -1)
         if self.has_bias:
