@@ -1975,6 +1975,65 @@ SLM_API int slm_w8a8_linear_plan(const slm_w8a8_linear_args* a, slm_linear_plan_
 SLM_API int32_t slm_w8a8_linear_deferred_splits(const slm_w8a8_linear_args* a);
 SLM_API int slm_w8a8_linear(const slm_w8a8_linear_args* a, void* stream);
 
+/* ========================================================================== */
+/* 26. fp8 x fp8 mixture-of-experts: grouped W8A8 GEMM                        */
+/*    The grouped GEMM of section 16 in section 25's arithmetic.  For every   */
+/*    32-row block b of the aligned token list, e = expert_ids[b], idx =      */
+/*    sorted[b * 32 + r], m = idx / a_div:                                    */
+/*      acc       = sum over k of e4m3(Aq[m, k]) * e4m3(W_e[n, k])            */
+/*                  (fp32; every product is exact)                            */
+/*      y         = (acc * a_scale[m]) * w_scale[e, n]   two fp32 multiplies, */
+/*                  this order, never contracted                              */
+/*      C[idx, n] = T( y * row_scale[idx] )              ONE rounding         */
+/*    The experts are section 16's tensors and rules exactly (w, w_scale,     */
+/*    ldw, both expert strides, NULL w_scale = 1.0).  The activations are     */
+/*    PRE-QUANTISED only: a is [n_flat / a_div, K] e4m3 BYTES, row stride lda */
+/*    in BYTES (>= K, % 16, base 16-byte aligned); a_scale is [n_flat /       */
+/*    a_div] fp32 (4-byte aligned), NULL = 1.0, indexed by the same gathered  */
+/*    row m as a: slm_w8a8_quantize_act's pair, made once per token (the rule */
+/*    is per row, so it commutes with the gather).  The NaN codes 0x7F / 0xFF */
+/*    poison their row or column.                                             */
+/*    One wave computes one 32 x 32 tile over the whole K with section 25's   */
+/*    MFMA sequence at one row tile and split_k = 1: an expert's rows are     */
+/*    slm_w8a8_linear (SLM_W8A8_SPLITK = 1) on those rows bit for bit, for    */
+/*    every launch shape.                                                     */
+/*    flags: 0 or SLM_MOE_SILU_MUL (section 16's: the bits of the plain call  */
+/*    followed by slm_silu_mul; not with row_scale).                          */
+/*    C is stored 8 bytes at a time: c 8-byte aligned, ldc % 4 == 0           */
+/*    (SLM_ERR_ALIGNMENT), as section 23.  The aligned-list contract, dead    */
+/*    blocks, padding rows (never stored), the launch shape (from max_blocks, */
+/*    N and flags alone; no split-K, no workspace, no atomics), the shapes    */
+/*    (K % 32 == 0, N % 32 == 0, (N/2) % 32 == 0 with SILU_MUL), the weight   */
+/*    side's alignment and stride rules, the error codes, "all validation     */
+/*    before any launch" and the no-op (n_flat == 0 or max_blocks == 0) are   */
+/*    section 16's (csrc/w8a8_moe.hip).                                       */
+/* ========================================================================== */
+typedef struct slm_moe_w8a8_gemm_args {
+  const void* a;                    /* [n_flat / a_div, K] e4m3fn bytes, row stride lda (BYTES)   */
+  const void* w;                    /* expert 0: [N, K] float8_e4m3fn bytes, row stride ldw (bytes) */
+  const float* w_scale;             /* [n_experts, N] fp32, expert stride w_scale_expert_stride, or NULL (1.0) */
+  void* c;                          /* [n_flat, N] T (SILU_MUL: [n_flat, N/2]), row stride ldc    */
+  const float* row_scale;           /* [n_flat] fp32 or NULL                                      */
+  const int32_t* sorted_token_idxes;
+  const int32_t* expert_ids;
+  const int32_t* n_padded_tokens;   /* [1], read on the device                                    */
+  int64_t w_expert_stride;          /* bytes between experts, >= (N - 1) * ldw + K                */
+  int64_t w_scale_expert_stride;    /* floats between experts' scales, >= N                       */
+  int64_t n_flat;                   /* rows of c = T * k; the padding id                          */
+  int64_t K, N;
+  int64_t lda, ldw, ldc;            /* lda, ldw bytes; ldc elements of T                          */
+  int32_t a_div;                    /* >= 1                                                       */
+  int32_t n_experts;
+  int32_t max_blocks;               /* sizes the grid: slm_moe_align_capacity(n_flat, E, 32)      */
+  int32_t dtype;                    /* of c                                                       */
+  int32_t flags;                    /* 0 or SLM_MOE_SILU_MUL; everything above is
+                                       slm_moe_fp8_gemm_args, field for field                     */
+  const float* a_scale;             /* [n_flat / a_div] fp32 or NULL (= 1.0): one scale per token */
+} slm_moe_w8a8_gemm_args;
+/* (the parameter list on its own line, as section 16's; tests/test_moe_w8a8_cpu.py covers this entry) */
+SLM_API int slm_moe_w8a8_gemm
+    (const slm_moe_w8a8_gemm_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

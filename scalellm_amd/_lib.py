@@ -201,6 +201,12 @@ class MoeW4A4GemmArgs(C.Structure):
                                             ("c_scale", C.c_void_p), ("ldcs", C.c_int64)]
 
 
+class MoeW8A8GemmArgs(C.Structure):
+    """struct slm_moe_w8a8_gemm_args (include/slm_hip.h section 26): slm_moe_fp8_gemm_args, field for field (a: e4m3
+    bytes, lda in bytes), plus the activations' per-token scales."""
+    _fields_ = MoeFp8GemmArgs._fields_ + [("a_scale", C.c_void_p)]
+
+
 class MoeRouterArgs(C.Structure):
     """struct slm_moe_router_args (include/slm_hip.h section 17)."""
     _fields_ = [
@@ -486,6 +492,7 @@ def lib() -> C.CDLL:
         ("slm_w8a8_linear", C.c_int, [C.POINTER(W8A8LinearArgs), C.c_void_p]),
         ("slm_w8a8_linear_deferred_splits", C.c_int32, [C.POINTER(W8A8LinearArgs)]),
         ("slm_w8a8_linear_plan", C.c_int, [C.POINTER(W8A8LinearArgs), C.POINTER(LinearPlanInfo)]),
+        ("slm_moe_w8a8_gemm", C.c_int, [C.POINTER(MoeW8A8GemmArgs), C.c_void_p]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

@@ -11,6 +11,7 @@
 //   slm::moe_fp8_grouped_gemm  the same over fp8 (e4m3) experts with channel scales (section 16, csrc/moe_gemm.hip).
 //   slm::moe_mxfp4_grouped_gemm  the same over OCP MXFP4 experts with e8m0 block scales (section 21, csrc/moe_gemm.hip).
 //   slm::moe_w4a4_grouped_gemm   MXFP4 experts against MXFP4 activations, W4A4 (section 23, csrc/w4a4_moe.hip).
+//   slm::moe_w8a8_grouped_gemm   fp8 experts against e4m3 activations, W8A8 (section 26, csrc/w8a8_moe.hip).
 //   slm::moe_router            the fused router: gate GEMM + routing in one launch (section 17, csrc/moe_router.hip).
 // Everything runs on torch's current HIP stream and nothing synchronises with the host.
 // Python mirror: scalellm_amd/kernels.py (same kernels, same arguments: bit-identical results).
@@ -105,6 +106,15 @@ void moe_w4a4_grouped_gemm(const torch::Tensor& a, const torch::Tensor& a_scale,
                            const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
                            const torch::Tensor& row_scale, bool silu_mul, const torch::Tensor& c_scale,
                            torch::ScalarType quant_dtype);
+
+// moe_fp8_grouped_gemm against e4m3 activations on the fp8 MFMA (include/slm_hip.h section 26, csrc/w8a8_moe.hip):
+// aq float8_e4m3fn (or uint8) [rows, K] (row stride a multiple of 16) and a_scale fp32 [rows] or undefined (1.0), the
+// pair the fp8 activation quantiser writes; both scales multiply the fp32 sum, a_scale first.  c is T [n_flat, N]
+// ([n_flat, N/2] with silu_mul), row stride a multiple of 4.  The rest as moe_fp8_grouped_gemm.
+void moe_w8a8_grouped_gemm(const torch::Tensor& aq, const torch::Tensor& a_scale, const torch::Tensor& w8,
+                           const torch::Tensor& w_scale, torch::Tensor& c, const torch::Tensor& sorted_token_idxes,
+                           const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
+                           const torch::Tensor& row_scale, bool silu_mul);
 
 // logits = x [T, hidden] . gate_weight [E, hidden]^T in fp32 and their routing, in one launch: scoring "softmax"
 // (renormalize) or "grouped_sigmoid" (correction_bias, n_expert_groups, topk_group, scaling_factor); topk is

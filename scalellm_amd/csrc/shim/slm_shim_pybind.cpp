@@ -364,6 +364,18 @@ PYBIND11_MODULE(_slm_shim, m) {
         py::arg("sorted_token_idxes"), py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("a_div"),
         py::arg("row_scale") = py::none(), py::arg("silu_mul") = false, py::arg("c_scale") = py::none(),
         py::arg("quant_f16") = false);
+  m.def("moe_w8a8_grouped_gemm",
+        [](const torch::Tensor& aq, const c10::optional<torch::Tensor>& a_scale, const torch::Tensor& w8,
+           const c10::optional<torch::Tensor>& w_scale, torch::Tensor c, const torch::Tensor& sorted_token_idxes,
+           const torch::Tensor& expert_ids, const torch::Tensor& n_padded_tokens, int64_t a_div,
+           const c10::optional<torch::Tensor>& row_scale, bool silu_mul) {
+          slm::moe_w8a8_grouped_gemm(aq, a_scale.has_value() ? *a_scale : torch::Tensor(), w8,
+                                     w_scale.has_value() ? *w_scale : torch::Tensor(), c, sorted_token_idxes,
+                                     expert_ids, n_padded_tokens, a_div,
+                                     row_scale.has_value() ? *row_scale : torch::Tensor(), silu_mul);
+        }, py::arg("aq"), py::arg("a_scale"), py::arg("w8"), py::arg("w_scale"), py::arg("c"),
+        py::arg("sorted_token_idxes"), py::arg("expert_ids"), py::arg("n_padded_tokens"), py::arg("a_div"),
+        py::arg("row_scale") = py::none(), py::arg("silu_mul") = false);
   m.def("moe_router",
         [](const torch::Tensor& x, const torch::Tensor& gate_weight, torch::Tensor topk_weights,
            torch::Tensor topk_indices, const std::string& scoring, bool renormalize,

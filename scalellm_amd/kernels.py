@@ -2187,6 +2187,61 @@ def moe_fp8_grouped_gemm(a: torch.Tensor, w8: torch.Tensor, w_scale: Optional[to
                       fp8=True)
 
 
+def moe_w8a8_grouped_gemm(aq: torch.Tensor, a_scale: Optional[torch.Tensor], w8: torch.Tensor,
+                          w_scale: Optional[torch.Tensor], c: torch.Tensor, sorted_token_idxes: torch.Tensor,
+                          expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor, a_div: int,
+                          row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:
+    """moe_fp8_grouped_gemm with fp8 activations on the fp8 MFMA (slm_hip.h section 26): C[idx] = epilogue(((e4m3(
+    Aq[idx // a_div]) . e4m3(W8[e])^T) * a_scale[idx // a_div]) * w_scale[e]), the two scales applied to the fp32 sum in
+    that order.  `aq` / `a_scale` are quantize_fp8_act's pair (float8_e4m3fn or uint8 [rows, K], row stride a multiple
+    of 16; fp32 [rows] or None = 1.0), `w8` / `w_scale` the experts of moe_fp8_grouped_gemm; nothing is converted.  `c`
+    is f16 / bf16 [n_flat, N] ([n_flat, N/2] with silu_mul), row stride a multiple of 4.  An expert's rows are
+    w8a8_linear's bits (SLM_W8A8_SPLITK=1).  row_scale, the aligned list and the grid: as moe_grouped_gemm."""
+    _require_gpu(aq, a_scale, w8, w_scale, c, sorted_token_idxes, expert_ids, n_padded_tokens, row_scale)
+    fp8 = (torch.float8_e4m3fn, torch.uint8)
+    if aq.dtype not in fp8 or w8.dtype not in fp8:
+        raise SlmError(f"moe_w8a8_grouped_gemm takes float8_e4m3fn activations and weights (or their bytes), not "
+                       f"{aq.dtype} / {w8.dtype}")
+    if aq.dim() != 2 or c.dim() != 2 or aq.stride(1) != 1 or c.stride(1) != 1:
+        raise SlmError("Aq and C must be 2-D with contiguous rows")
+    if w8.dim() != 3 or w8.stride(2) != 1:
+        raise SlmError("expert weights must be [n_experts, N, K] with k contiguous")
+    E, N, K = w8.shape
+    n_flat = c.size(0)
+    if aq.size(1) != K or c.size(1) != (N // 2 if silu_mul else N) or a_div < 1 or aq.size(0) * a_div < n_flat:
+        raise SlmError("grouped GEMM shape mismatch")
+    if c.dtype not in (torch.float16, torch.bfloat16):
+        raise SlmError("C must be fp16 or bf16")
+    if a_scale is not None and (a_scale.dtype != torch.float32 or tuple(a_scale.shape) != (aq.size(0),) or
+                                not a_scale.is_contiguous()):
+        raise SlmError("a_scale must be contiguous fp32 with one entry per row of Aq")
+    if w_scale is not None and (w_scale.dtype != torch.float32 or tuple(w_scale.shape) != (E, N) or
+                                w_scale.stride(1) != 1):
+        raise SlmError("w_scale must be fp32 [n_experts, N] with contiguous rows (expand a per-tensor scale)")
+    for t in (sorted_token_idxes, expert_ids, n_padded_tokens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("sorted_token_idxes / expert_ids / n_padded_tokens must be contiguous int32")
+    if sorted_token_idxes.numel() < expert_ids.numel() * MOE_GEMM_BLOCK:
+        raise SlmError("sorted_token_idxes is shorter than expert_ids.numel() blocks of 32")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or not row_scale.is_contiguous() or
+                                  row_scale.numel() != n_flat):
+        raise SlmError("row_scale must be contiguous fp32 with one entry per row of C")
+    g = _lib.MoeW8A8GemmArgs()
+    g.a, g.w, g.c = aq.data_ptr(), w8.data_ptr(), c.data_ptr()
+    g.a_scale, g.w_scale, g.row_scale = (t.data_ptr() if t is not None else None for t in (a_scale, w_scale, row_scale))
+    g.sorted_token_idxes, g.expert_ids = sorted_token_idxes.data_ptr(), expert_ids.data_ptr()
+    g.n_padded_tokens = n_padded_tokens.data_ptr()
+    # a single expert's stride(0) is not meaningful: what covers the expert will do
+    g.w_expert_stride = w8.stride(0) if E > 1 else max(w8.stride(0), N * w8.stride(1))
+    g.w_scale_expert_stride = 0 if w_scale is None else (w_scale.stride(0) if E > 1 else max(w_scale.stride(0), N))
+    g.n_flat, g.K, g.N = n_flat, K, N
+    g.lda, g.ldw, g.ldc = aq.stride(0), w8.stride(1), c.stride(0)
+    g.a_div, g.n_experts, g.max_blocks = a_div, E, expert_ids.numel()
+    g.dtype = _dtype_code(c)
+    g.flags = _lib.SLM_MOE_SILU_MUL if silu_mul else 0
+    check(_lib.lib().slm_moe_w8a8_gemm(C.byref(g), _stream()), "slm_moe_w8a8_gemm")
+
+
 def moe_mxfp4_grouped_gemm(a: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, c: torch.Tensor,
                            sorted_token_idxes: torch.Tensor, expert_ids: torch.Tensor, n_padded_tokens: torch.Tensor,
                            a_div: int, row_scale: Optional[torch.Tensor] = None, silu_mul: bool = False) -> None:

@@ -14,7 +14,8 @@ with the dense MLP replaced by a sparse mixture of experts (HuggingFace MixtralD
     residual + the next layer's input norm (or the final norm)                   kernels.rms_norm(residual=)
   untied lm_head, no cap -> argmax, or the fused sampling kernel
 
-quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16), "mxfp4" (OCP MXFP4:
+quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16; with act_quant="fp8"
+W8A8: linears and experts against e4m3 activations with one dynamic scale per token), "mxfp4" (OCP MXFP4:
 e2m1 nibbles + e8m0 block scales, W4A16, the "none" checkpoint of the same seed quantised, loaded under the Quark
 names weight / weight_scale) or "awq" (int4): the four attention linears are the classes LlamaDecodeStep uses for
 that method, the experts the matching experts class of moe.py, loaded through load_state_dict under the Mixtral names
@@ -85,8 +86,11 @@ class MixtralDecodeStep:
             raise ValueError(f"quant_method must be 'none', 'fp8', 'awq' or 'mxfp4', not {quant_method!r}")
         # act_quant "mxfp4" (with quant_method "mxfp4" only): MXFP4 activations too (W4A4) -- the linears quantise theirs
         # as they load them (layers.*Mxfp4Linear(act_quant=...)), the experts run FusedMoE(act_quant=...)
-        if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
-            raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
+        # act_quant "fp8" (with quant_method "fp8" only): e4m3 activations with one dynamic scale per token (W8A8) --
+        # the linears quantise their input with one launch (layers.*Fp8Linear(act_quant=...)), the experts theirs
+        if act_quant is not None and (act_quant not in ("mxfp4", "fp8") or quant_method != act_quant):
+            raise ValueError(f"act_quant={act_quant!r} must be None, 'mxfp4' (with quant_method='mxfp4') or 'fp8' "
+                             "(with quant_method='fp8')")
         self.act_quant = act_quant
         aq = {"act_quant": act_quant} if act_quant else {}
         # keep_checkpoint: retain the CHECKPOINT-format tensors (self.ckpt[layer]: "qkv", "o" as the linears take

@@ -1,6 +1,6 @@
 """Mixture-of-experts FFN over int4 (AWQ / GPTQ), fp8 (e4m3, weight-only), OCP MXFP4 (weight-only) or unquantised
 f16 / bf16 experts: routing, block alignment, two grouped GEMMs and the sum over a token's experts, every step a HIP
-kernel of libslm_hip (include/slm_hip.h sections 10, 16, 21 and 23).
+kernel of libslm_hip (include/slm_hip.h sections 10, 16, 21, 23 and 26).
 
     FusedMoE.forward(x):  router logits (fp32, torch: [T, hidden] x [hidden, E] is tiny)
                           -> moe_topk_softmax | moe_grouped_topk_sigmoid      (weights, expert ids)
@@ -12,7 +12,9 @@ kernel of libslm_hip (include/slm_hip.h sections 10, 16, 21 and 23).
 
 With MXFP4 experts and act_quant="mxfp4" the activations are MXFP4 too (W4A4, section 23): x is quantised once per
 token (kernels.quantize_mxfp4_act), the gate_up GEMM's SiLU * mul epilogue writes the down GEMM's input as MXFP4
-codes and scale bytes, and both GEMMs run on the block-scaled MFMA: seven launches instead of six.
+codes and scale bytes, and both GEMMs run on the block-scaled MFMA: seven launches instead of six.  With fp8 experts
+and act_quant="fp8" (W8A8, section 26) x and the SiLU * mul output are each quantised to e4m3 with one dynamic scale per
+row (kernels.quantize_fp8_act) and both GEMMs run on the fp8 MFMA without converts: eight launches.
 
 All buffers are sized at construction by the capacity rule (slm_moe_align_capacity) for max_tokens rows, nothing on
 the path reads a device value on the host, and a smaller batch runs in views of the same buffers: forward() can be
@@ -160,14 +162,18 @@ class MoEFp8Experts:
     per expert and output channel: `gate_up_scale` [E, 2 * intermediate], `down_scale` [E, hidden].  load_state_dict
     takes Mixtral-FP8 names experts.{e}.w1|w3|w2.weight (float8_e4m3fn; any other dtype is a TypeError -- nothing is
     quantised on load, as in the fp8 linears) and .weight_scale (0-d, [1], [rows] or [rows, 1], any float dtype; a
-    per-tensor scale is expanded over its own rows, so w1 and w3 keep their own).  input_scale is ignored (W8A16)."""
+    per-tensor scale is expanded over its own rows, so w1 and w3 keep their own).  input_scale is ignored (W8A16; the
+    W8A8 path quantises dynamically, one scale per token).  act_quant="fp8": the same tensors under the same names,
+    multiplied against e4m3 activations (ffn_w8a8: kernels.moe_w8a8_grouped_gemm); gemm() stays the W8A16 path."""
 
     def __init__(self, hidden: int, intermediate: int, n_experts: int, dtype: torch.dtype, device,
-                 expert_offset: int = 0):
+                 expert_offset: int = 0, act_quant: Optional[str] = None):
         if dtype not in (torch.float16, torch.bfloat16):
             raise SlmError(f"MoE experts: fp16 / bf16 activations only, got {dtype}")
+        if act_quant not in (None, "fp8"):
+            raise SlmError(f"unknown act_quant {act_quant!r}: None or 'fp8'")
         self.hidden, self.intermediate, self.n_experts = hidden, intermediate, n_experts
-        self.dtype, self.device = dtype, device
+        self.dtype, self.device, self.act_quant = dtype, device, act_quant
         self.expert_offset = expert_offset   # expert e of this holder is experts.{expert_offset + e}.* (an EP shard)
         self._ckpt: Dict[str, torch.Tensor] = {}
         self.gate_up: Optional[torch.Tensor] = None
@@ -236,6 +242,32 @@ class MoEFp8Experts:
         """the grouped GEMM over `which` = "gate_up" | "down"; the arguments after c are the kernel's"""
         kernels.moe_fp8_grouped_gemm(a, getattr(self, which), getattr(self, which + "_scale"), c, *aligned,
                                      **epilogue)
+
+    def gemm_w8a8(self, which: str, aq, a_scale, c, *aligned, **epilogue) -> None:
+        """gemm() over e4m3 activations (aq, a_scale: quantize_fp8_act's pair)"""
+        kernels.moe_w8a8_grouped_gemm(aq, a_scale, getattr(self, which), getattr(self, which + "_scale"), c, *aligned,
+                                      **epilogue)
+
+    def ffn_w8a8(self, x2, bufs, n, down, srt, eids, n_padded, a_div: int, row_scale=None) -> None:
+        """quantise x2 [rows, hidden] once per token -> gate_up (SiLU * mul) -> quantise the n intermediate rows ->
+        down [n, hidden], in `bufs`' xq / xs / act / actq / acts (w8a8_buffers).  The second quantise is a launch of
+        its own: a dynamic per-token scale needs the whole intermediate row before its first byte."""
+        rows = x2.size(0)
+        xq, xs, act, actq, acts = bufs["xq"][:rows], bufs["xs"][:rows], bufs["act"][:n], bufs["actq"][:n], bufs["acts"][:n]
+        kernels.quantize_fp8_act(x2, aq=xq, a_scale=xs)
+        self.gemm_w8a8("gate_up", xq, xs, act, srt, eids, n_padded, a_div=a_div, silu_mul=True)
+        kernels.quantize_fp8_act(act, aq=actq, a_scale=acts)
+        self.gemm_w8a8("down", actq, acts, down, srt, eids, n_padded, a_div=1, row_scale=row_scale)
+
+    def w8a8_buffers(self, rows: int, n_flat: int) -> Dict[str, torch.Tensor]:
+        """the e4m3 images (bytes and per-token scales) of `rows` rows of x and `n_flat` rows of the SiLU * mul
+        output, and that output itself in T"""
+        f8, f32, dev = torch.float8_e4m3fn, torch.float32, self.device
+        return dict(xq=torch.empty(rows, self.hidden, dtype=f8, device=dev),
+                    xs=torch.empty(rows, dtype=f32, device=dev),
+                    act=torch.empty(n_flat, self.intermediate, dtype=self.dtype, device=dev),
+                    actq=torch.empty(n_flat, self.intermediate, dtype=f8, device=dev),
+                    acts=torch.empty(n_flat, dtype=f32, device=dev))
 
 
 class MoEMxfp4Experts:
@@ -333,15 +365,17 @@ class MoEMxfp4Experts:
 def _make_experts(hidden: int, intermediate: int, n_experts: int, quant_args: Optional[QuantArgs], dtype, device,
                   expert_offset: int = 0, act_quant: Optional[str] = None):
     """The experts holder a QuantArgs selects: None -> unquantised, "fp8" -> MoEFp8Experts, "mxfp4" ->
-    MoEMxfp4Experts, else int4.  act_quant ("mxfp4": MXFP4 activations) needs QuantArgs("mxfp4", 4)."""
+    MoEMxfp4Experts, else int4.  act_quant ("mxfp4": MXFP4 activations; "fp8": e4m3 activations with one dynamic
+    scale per token) needs the experts of its own format: QuantArgs("mxfp4", 4) / QuantArgs("fp8", 8)."""
     if act_quant is not None:
-        if act_quant != "mxfp4":
-            raise SlmError(f"unknown act_quant {act_quant!r}: None or 'mxfp4'")
-        if quant_args is None or quant_args.quant_method != "mxfp4" or quant_args.bits != 4:
-            raise SlmError("act_quant='mxfp4' needs MXFP4 experts: QuantArgs('mxfp4', 4)")
+        if act_quant not in ("mxfp4", "fp8"):
+            raise SlmError(f"unknown act_quant {act_quant!r}: None, 'mxfp4' or 'fp8'")
+        bits, cls = (4, MoEMxfp4Experts) if act_quant == "mxfp4" else (8, MoEFp8Experts)
+        if quant_args is None or quant_args.quant_method != act_quant or quant_args.bits != bits:
+            raise SlmError(f"act_quant={act_quant!r} needs experts of that format: QuantArgs({act_quant!r}, {bits})")
         if hidden % 32 or intermediate % 32:
             raise SlmError("hidden and intermediate must be multiples of 32 (K and N of the two grouped GEMMs)")
-        return MoEMxfp4Experts(hidden, intermediate, n_experts, dtype, device, expert_offset, act_quant)
+        return cls(hidden, intermediate, n_experts, dtype, device, expert_offset, act_quant)
     if quant_args is None or quant_args.quant_method in ("fp8", "mxfp4"):
         if quant_args is not None and quant_args.quant_method == "fp8" and quant_args.bits != 8:
             raise SlmError(f"quant_method 'fp8' means 8-bit weights, got bits = {quant_args.bits}")
@@ -365,6 +399,9 @@ class FusedMoE:
     GEMM (experts.gemm); the forward pass is the same six launches for all four.  act_quant="mxfp4" (MXFP4 experts
     only) runs both GEMMs against MXFP4 activations: router, align, quantise x, gate_up with SiLU * mul and a
     quantised output, down with the routing weight, sum -- seven launches, every buffer sized once.
+    act_quant="fp8" (fp8 experts only) runs them against e4m3 activations with one dynamic scale per token (W8A8):
+    router, align, quantise x, gate_up with SiLU * mul, quantise the intermediate rows, down with the routing weight,
+    sum -- eight launches, every buffer sized once.
 
     scoring = "softmax": top-k of the softmax (renormalize = Mixtral's rule: the k weights divided by their sum);
     scoring = "grouped_sigmoid": sigmoid scores with a correction bias, group-limited top-k (n_expert_groups,
@@ -394,7 +431,7 @@ class FusedMoE:
 
     @property
     def act_quant(self) -> Optional[str]:
-        """"mxfp4" when the experts multiply against MXFP4 activations (the experts holder carries it)"""
+        """"mxfp4" / "fp8" when the experts multiply against MXFP4 / e4m3 activations (the experts holder carries it)"""
         return getattr(self.experts, "act_quant", None)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
@@ -419,9 +456,12 @@ class FusedMoE:
                 act=torch.empty(n_flat, self.intermediate, dtype=self.dtype, device=dev),
                 down=torch.empty(n_flat, self.hidden, dtype=self.dtype, device=dev),
             )
-            if self.act_quant:   # x and the SiLU * mul output as MXFP4 instead of `act`
+            if self.act_quant == "mxfp4":   # x and the SiLU * mul output as MXFP4 instead of `act`
                 del self._buf["act"]
                 self._buf.update(self.experts.w4a4_buffers(self.max_tokens, n_flat))
+            elif self.act_quant == "fp8":   # x and the SiLU * mul output as e4m3 beside `act`
+                del self._buf["act"]
+                self._buf.update(self.experts.w8a8_buffers(self.max_tokens, n_flat))
         return self._buf
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -475,7 +515,8 @@ class FusedMoE:
                                                  k, self.scaling_factor, weights, ids)
         kernels.moe_align_block(ids, self.n_experts, kernels.MOE_GEMM_BLOCK, srt, eids, b["n_padded"])
         if self.act_quant:
-            self.experts.ffn_w4a4(x2, b, n_flat, down, srt, eids, b["n_padded"], k, row_scale=weights.view(-1))
+            ffn = self.experts.ffn_w4a4 if self.act_quant == "mxfp4" else self.experts.ffn_w8a8
+            ffn(x2, b, n_flat, down, srt, eids, b["n_padded"], k, row_scale=weights.view(-1))
         else:
             act = b["act"][:n_flat]
             self.experts.gemm("gate_up", x2, act, srt, eids, b["n_padded"], a_div=k, silu_mul=True)
@@ -684,7 +725,7 @@ class ExpertParallelMoE:
 
     @property
     def act_quant(self) -> Optional[str]:
-        """"mxfp4" when the experts multiply against MXFP4 activations (the experts holder carries it)"""
+        """"mxfp4" / "fp8" when the experts multiply against MXFP4 / e4m3 activations (the experts holder carries it)"""
         return getattr(self.experts, "act_quant", None)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
@@ -708,8 +749,11 @@ class ExpertParallelMoE:
         eids = torch.empty(max_blocks, dtype=i32, device=dev)
         n_padded = torch.zeros(1, dtype=i32, device=dev)
         kernels.moe_align_block(row_expert, L, kernels.MOE_GEMM_BLOCK, srt, eids, n_padded)
-        if self.act_quant:
+        if self.act_quant == "mxfp4":
             self.experts.ffn_w4a4(rows, self.experts.w4a4_buffers(n, n), n, down, srt, eids, n_padded, 1)
+            return down
+        if self.act_quant == "fp8":
+            self.experts.ffn_w8a8(rows, self.experts.w8a8_buffers(n, n), n, down, srt, eids, n_padded, 1)
             return down
         act = torch.empty(n, self.intermediate, dtype=rows.dtype, device=dev)
         self.experts.gemm("gate_up", rows, act, srt, eids, n_padded, a_div=1, silu_mul=True)

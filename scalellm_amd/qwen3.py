@@ -15,7 +15,8 @@ heads, eps = rms_norm_eps), and with n_experts > 0 the MLP replaced by Qwen3-MoE
     residual + the next layer's input norm (or the final norm)                   kernels.rms_norm(residual=)
   lm_head (the embedding itself when tie_word_embeddings) -> argmax, or the fused sampling kernel
 
-quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16), "mxfp4" (OCP MXFP4,
+quant_method "none" (f16 / bf16 checkpoint), "fp8" (e4m3 weights with channel scales, W8A16; with act_quant="fp8"
+W8A8: linears and experts against e4m3 activations with one dynamic scale per token), "mxfp4" (OCP MXFP4,
 W4A16: the attention projections and the dense MLP on layers.{Column,Row}ParallelMxfp4Linear, the experts on
 moe.MoEMxfp4Experts) or "awq" (int4), as MixtralDecodeStep.  head_dim must be one the QK-norm kernel takes (64, 128, 256).
 
@@ -97,8 +98,11 @@ class Qwen3DecodeStep:
             raise ValueError(f"quant_method must be 'none', 'fp8', 'awq' or 'mxfp4', not {quant_method!r}")
         # act_quant "mxfp4" (with quant_method "mxfp4" only): MXFP4 activations too (W4A4) -- the linears quantise theirs
         # as they load them (layers.*Mxfp4Linear(act_quant=...)), the experts run FusedMoE(act_quant=...)
-        if act_quant is not None and (act_quant != "mxfp4" or quant_method != "mxfp4"):
-            raise ValueError(f"act_quant={act_quant!r} needs quant_method='mxfp4' and must be None or 'mxfp4'")
+        # act_quant "fp8" (with quant_method "fp8" only): e4m3 activations with one dynamic scale per token (W8A8) --
+        # the linears quantise their input with one launch (layers.*Fp8Linear(act_quant=...)), the experts theirs
+        if act_quant is not None and (act_quant not in ("mxfp4", "fp8") or quant_method != act_quant):
+            raise ValueError(f"act_quant={act_quant!r} must be None, 'mxfp4' (with quant_method='mxfp4') or 'fp8' "
+                             "(with quant_method='fp8')")
         self.act_quant = act_quant
         aq = {"act_quant": act_quant} if act_quant else {}
         if shape.head_dim not in (64, 128, 256):

@@ -6,6 +6,7 @@ loop over the experts: per-expert slm_w4a16_gemm calls for int4 experts, torch.m
     python tools/bench_moe.py --fp8 [--out profiles/r18_moe_fp8.jsonl]
     python tools/bench_moe.py --mxfp4 [--out profiles/r23_moe_mxfp4.jsonl]
     python tools/bench_moe.py --w4a4 [--out profiles/r25_moe_w4a4.jsonl]
+    python tools/bench_moe.py --w8a8 [--out profiles/r28_moe_w8a8.jsonl]
 
 hidden 4096, intermediate 14336, E = 8, k = 2, AWQ group 128, bf16 (random weights: 705 MB packed).  One JSON
 line per T:
@@ -49,6 +50,13 @@ slm_moe_w4a4_gemm: seven launches, x quantised once per token, the gate_up epilo
 MXFP4) beside the W4A16 layer over the SAME expert tensors and the fp8 layer of --fp8, one process, alternating
 windows: one JSON line per T with w4a4_us / mxfp4_us / fp8_us, their windows and spreads, w4a4_over_mxfp4, the byte
 fractions, and w4a4_vs_mxfp4_rel_err (what quantising the activations costs on random, uncalibrated data).
+
+--w8a8: the fp8 experts of --fp8 against e4m3 activations with one dynamic scale per token (FusedMoE(QuantArgs("fp8",
+8), act_quant="fp8"), slm_moe_w8a8_gemm: eight launches, x and the SiLU * mul rows each quantised by one launch) beside
+the W8A16 layer over the SAME expert tensors, one process, alternating windows: one JSON line per T with w8a8_us /
+w8a16_us, quant_us (the two quantise launches alone on the layer's buffers, 20 pairs per replay) and quant_share = quant_us /
+w8a8_us, windows and spreads, and w8a8_vs_w8a16_rel_err.  Then two lines for the 8-of-32-layer Mixtral step at kv 4096,
+batch 1 and 32: act_quant="fp8" beside None on the same weights, alternating windows.
 """
 import argparse
 import json
@@ -64,6 +72,7 @@ from scalellm_amd.layers import QuantArgs  # noqa: E402
 
 HID, INTER, NE, TOPK, GS = 4096, 14336, 8, 2, 128
 READ_CEILING = 7.0e12
+QREP = 20   # --w8a8: pairs of quantise launches per replay of the graph that times them alone
 
 
 def _layer(max_tokens, dev):
@@ -297,6 +306,96 @@ def _main_w4a4(args, dev, tokens):
     return lines
 
 
+def _main_w8a8(args, dev, tokens):
+    """layer rows (W8A8 beside W8A16 over the SAME expert tensors, and the two quantise launches alone), then the step
+    rows (MixtralDecodeStep, 8 of 32 layers, kv 4096: act_quant "fp8" beside None, same seed = same weights)"""
+    import dataclasses
+    from scalellm_amd.decode import make_decode_inputs
+    from scalellm_amd.mixtral import MixtralDecodeStep, MixtralShape
+    w8a16 = _mxfp4_fp8_and_dense_layers(max(tokens), dev, sides=("fp8",))[0]
+    w8a8 = moe.FusedMoE(HID, INTER, NE, TOPK, quant_args=QuantArgs("fp8", 8), scoring="softmax", renormalize=True,
+                        max_tokens=max(tokens), dtype=torch.bfloat16, device=dev, act_quant="fp8")
+    w8a8.gate_weight = w8a16.gate_weight
+    for name in ("gate_up", "down", "gate_up_scale", "down_scale"):   # the same tensors: nothing is copied
+        setattr(w8a8.experts, name, getattr(w8a16.experts, name))
+    nbytes = w8a16.experts.nbytes() // NE
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    spread = lambda t: round((max(t) - min(t)) / med(t), 4)  # noqa: E731
+    lines = []
+    for T in tokens:
+        g = torch.Generator(device=dev).manual_seed(T)
+        pool = [torch.randn(T, HID, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(args.pool)]
+        runs = {"w8a8": _captured(w8a8, pool, T, dev), "w8a16": _captured(w8a16, pool, T, dev)}
+        y88, y816 = runs["w8a8"][1].float(), runs["w8a16"][1].float()
+        rel = float((y88 - y816).abs().mean() / y816.abs().mean())
+        # the layer's two quantise launches alone, on its own buffers (x [T, hidden], SiLU * mul rows [T * k, inter]):
+        # QREP pairs per replay, so that the replay's own launch cost does not count as theirs
+        b = w8a8._buffers()
+        qg = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(qg):
+            for _ in range(QREP):
+                kernels.quantize_fp8_act(pool[0], aq=b["xq"][:T], a_scale=b["xs"][:T])
+                kernels.quantize_fp8_act(b["act"][:T * TOPK], aq=b["actq"][:T * TOPK], a_scale=b["acts"][:T * TOPK])
+        fns = {"w8a8": runs["w8a8"][0], "w8a16": runs["w8a16"][0], "quant": lambda i: qg.replay()}
+        times = {k: [] for k in fns}
+        for _ in range(args.rounds):                    # alternating windows: drift hits all columns alike
+            for k, fn in fns.items():
+                times[k].append(_time(fn, args.iters))
+        times["quant"] = [t / QREP for t in times["quant"]]
+        us = {k: med(t) for k, t in times.items()}
+        routed = [_routing(w8a16, x)[1] for x in pool]
+        used = [int(ids.unique().numel()) for ids in routed]
+        n_used = sum(used) / len(used)
+        line = dict(bench="moe_mixtral_8x7b_w8a8_bf16", T=T, topk=TOPK, n_experts=NE)
+        for k in fns:
+            line[k + "_us"] = round(us[k], 2)
+            line[k + "_us_windows"] = [round(t, 2) for t in times[k]]
+            line[k + "_spread"] = spread(times[k])
+        line.update(w8a8_over_w8a16=round(us["w8a8"] / us["w8a16"], 4), quant_share=round(us["quant"] / us["w8a8"], 4),
+                    experts_in_use=round(n_used, 2), touched_bytes=int(nbytes * n_used),
+                    frac_7tbs=round(nbytes * n_used / (us["w8a8"] * 1e-6) / READ_CEILING, 4),
+                    w8a16_frac_7tbs=round(nbytes * n_used / (us["w8a16"] * 1e-6) / READ_CEILING, 4),
+                    w8a8_vs_w8a16_rel_err=round(rel, 5), iters=args.iters, pool=args.pool, rounds=args.rounds)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    del w8a8, w8a16, runs, fns, qg
+    torch.cuda.empty_cache()
+
+    shape = dataclasses.replace(MixtralShape.mixtral_8x7b(), n_layers=8)
+    kv_len, block = 4096, 16
+    nb = make_decode_inputs(32, kv_len, block, dev, vocab=shape.vocab)[3]
+    steps = {}
+    for k, aq in (("w8a8", {"act_quant": "fp8"}), ("w8a16", {})):
+        steps[k] = MixtralDecodeStep(shape, 32, nb, block, quant_method="fp8", device=dev, **aq)
+        for L in steps[k].layers:
+            for t in L["kv"].get_kv_cache():
+                t.normal_()
+        steps[k].reserve_workspaces(32, kv_len)
+    for bs in (1, 32):
+        tk, pos, params, _ = make_decode_inputs(bs, kv_len, block, dev, seed=bs, vocab=shape.vocab)
+        graphs = {}
+        for k, step in steps.items():
+            step.forward(tk, pos, params)               # warm-up: workspaces, lazy repacks
+            torch.cuda.synchronize()
+            graphs[k] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[k]):
+                step.forward(tk, pos, params)
+        times = {k: [] for k in graphs}
+        for _ in range(args.rounds):
+            for k in graphs:
+                times[k].append(_time(lambda i: graphs[k].replay(), args.iters))
+        us = {k: med(t) for k, t in times.items()}
+        line = dict(bench="mixtral_8x7b_step_8_of_32_layers_w8a8", batch=bs, kv_len=kv_len)
+        for k in graphs:
+            line[k + "_step_us"] = round(us[k], 2)
+            line[k + "_step_us_windows"] = [round(t, 2) for t in times[k]]
+            line[k + "_step_spread"] = spread(times[k])
+        line.update(w8a8_over_w8a16=round(us["w8a8"] / us["w8a16"], 4), iters=args.iters, rounds=args.rounds)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def _routing(layer, x):
     logits = x.float() @ layer.gate_weight.float().t()
     w, ids = kernels.moe_topk_softmax(logits, TOPK, True)
@@ -364,12 +463,15 @@ def main():
     ap.add_argument("--w4a4", action="store_true",
                     help="MXFP4 experts against MXFP4 activations (slm_moe_w4a4_gemm) beside the W4A16 layer over the "
                          "same tensors and the fp8 layer")
+    ap.add_argument("--w8a8", action="store_true",
+                    help="fp8 experts against fp8 activations (slm_moe_w8a8_gemm) beside the W8A16 layer over the same "
+                         "tensors, then the 8-layer Mixtral step with act_quant='fp8' beside None")
     ap.add_argument("--rounds", type=int, default=3,
-                    help="--fp8 / --mxfp4 / --w4a4: alternating timing windows per layer")
+                    help="--fp8 / --mxfp4 / --w4a4 / --w8a8: alternating timing windows per layer")
     args = ap.parse_args()
-    if args.dense + args.fp8 + args.mxfp4 + args.w4a4 > 1:
-        raise SystemExit("--dense, --fp8, --mxfp4 and --w4a4 are four modes: pick one (--fp8 and --mxfp4 measure the "
-                         "dense layer too)")
+    if args.dense + args.fp8 + args.mxfp4 + args.w4a4 + args.w8a8 > 1:
+        raise SystemExit("--dense, --fp8, --mxfp4, --w4a4 and --w8a8 are five modes: pick one (--fp8 and --mxfp4 "
+                         "measure the dense layer too)")
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda")
@@ -382,6 +484,9 @@ def main():
         return
     if args.w4a4:
         _write(args.out, _main_w4a4(args, dev, tokens))
+        return
+    if args.w8a8:
+        _write(args.out, _main_w8a8(args, dev, tokens))
         return
     if args.dense:
         layer = _dense_layer(max(tokens), dev)
