@@ -39,7 +39,8 @@ typedef enum slm_status {
   SLM_ERR_UNSUPPORTED = -2,   /* dtype / head_dim / bits / group not supported */
   SLM_ERR_WORKSPACE = -3,     /* workspace missing or too small */
   SLM_ERR_LAUNCH = -4,        /* hipLaunchKernel reported an error */
-  SLM_ERR_ALIGNMENT = -5      /* pointer or stride not 16-byte aligned */
+  SLM_ERR_ALIGNMENT = -5,     /* pointer or stride not 16-byte aligned */
+  SLM_ERR_SHAPE = -6          /* a size outside the entry point's set (section 27: head_dim) */
 } slm_status;
 
 typedef enum slm_dtype {
@@ -2033,6 +2034,108 @@ typedef struct slm_moe_w8a8_gemm_args {
 /* (the parameter list on its own line, as section 16's; tests/test_moe_w8a8_cpu.py covers this entry) */
 SLM_API int slm_moe_w8a8_gemm
     (const slm_moe_w8a8_gemm_args* a, void* stream);
+
+/* ========================================================================== */
+/* 27. fp8 (e4m3) paged KV cache: quantising append, stream attention         */
+/*    key_cache / value_cache are [n_slots, n_kv_heads, head_dim] BYTES, one  */
+/*    float8_e4m3fn code per element, paged exactly as in section 1 (same     */
+/*    slot formula, same block table).  k_scale / v_scale are [n_kv_heads]    */
+/*    fp32, static, > 0; element value = code * scale of its head (a          */
+/*    per-tensor checkpoint scale is that value repeated).                    */
+/*                                                                            */
+/*    slm_kv_fp8_append: cache[slot_ids[t], h, :] = e4m3(x[t, h, :] / s[h]),  */
+/*    the rule of slm_w8a8_quantize_act's static form (section 25): IEEE fp32 */
+/*    division, clamp at +-448, round to nearest even, a NaN keeps its sign   */
+/*    over 0x7F -- the bytes of (x.float() / s).clamp(-448, 448)              */
+/*    .to(float8_e4m3fn).  keys / values are [n_tokens, n_kv_heads, head_dim] */
+/*    T with a token stride (column slices of a qkv row), heads contiguous.   */
+/*    One launch, 16 elements per lane, 16-byte stores: head_dim % 16 == 0,   */
+/*    token strides % 8 == 0, 16-byte aligned bases (SLM_ERR_ALIGNMENT).      */
+/*    Like section 2, every slot id is written: none is skipped.  n_tokens == */
+/*    0 is a no-op.                                                           */
+/*                                                                            */
+/*    slm_paged_kv_fp8_attention: section 1's result over such caches, query  */
+/*    and out in T (f16 / bf16).  Token-major stream kernel for every row     */
+/*    (decode, verify, prefill chunks: per-token visible range; only q_len =  */
+/*    1 is fast -- a chunk streams its history once per query token).  Codes  */
+/*    are converted to T exactly; no element is multiplied by a scale:        */
+/*    k_scale[h] is folded into the score scale (with a soft cap: into the    */
+/*    pre-scale), v_scale[h] into the final 1 / l (split: into what the       */
+/*    combine pass writes).  Split-KV: the classic partition only, partials   */
+/*    in section 1's layout: workspace = o_part [n_tokens, n_heads, n_splits, */
+/*    head_dim] fp32, then ml_part [n_tokens, n_heads, n_splits, 2] fp32;     */
+/*    needed when n_splits > 1.  head_dim 64 / 128 / 256 (else                */
+/*    SLM_ERR_SHAPE); f16 / bf16 (else SLM_ERR_UNSUPPORTED); alibi_slopes     */
+/*    must be NULL (else SLM_ERR_UNSUPPORTED); n_heads % n_kv_heads == 0,     */
+/*    power-of-two block_size, slot strides in (0, 2^32) bytes (else          */
+/*    SLM_ERR_INVALID_ARG); 16-byte aligned bases, q / o strides % 8, cache   */
+/*    strides % 16 (SLM_ERR_ALIGNMENT); a missing or short workspace          */
+/*    (SLM_ERR_WORKSPACE).  Every check precedes the first HIP call.  Rows    */
+/*    behind q_cu_lens[batch] (graph padding) are left untouched; lengths and */
+/*    tables are read on the device; repeats are bit-identical.               */
+/* ========================================================================== */
+typedef struct slm_attn_fp8_args {
+  void* out;                /* [n_tokens, n_heads, head_dim] T                */
+  const void* query;        /* [n_tokens, n_heads, head_dim] T                */
+  const void* key_cache;    /* [n_slots, n_kv_heads, head_dim] e4m3fn bytes   */
+  const void* value_cache;
+  int64_t o_stride[2];      /* {token stride, head stride} in elements        */
+  int64_t q_stride[2];
+  int64_t k_stride[2];      /* {slot stride, head stride} in elements = bytes */
+  int64_t v_stride[2];
+  const int32_t* q_cu_lens;      /* as section 1                              */
+  const int32_t* kv_cu_lens;
+  const int32_t* block_table;
+  const int32_t* block_cu_lens;
+  const float* alibi_slopes;     /* must be NULL                              */
+  int32_t dtype;            /* slm_dtype of out / query                       */
+  int32_t batch_size;
+  int32_t n_tokens;         /* rows of query; rows behind q_cu_lens[batch] are never written */
+  int32_t n_heads;
+  int32_t n_kv_heads;
+  int32_t head_dim;         /* 64, 128 or 256                                 */
+  int32_t block_size;
+  int32_t max_q_len;        /* scheduling hint                                */
+  int32_t max_kv_len;       /* scheduling hint: sizes the KV splits; results are correct for any value */
+  float sm_scale;
+  float logits_soft_cap;    /* 0 = off                                        */
+  int32_t sliding_window;   /* -1 = off; keys behind the query, as section 1  */
+  void* workspace;          /* split-KV partials, may be NULL when the plan needs none */
+  size_t workspace_bytes;
+  int32_t num_splits;       /* 0 = heuristic, > 0 forces the split count      */
+  int32_t reserved;
+  const float* k_scale;     /* [n_kv_heads] fp32                              */
+  const float* v_scale;     /* [n_kv_heads] fp32                              */
+} slm_attn_fp8_args;
+
+typedef struct slm_attn_fp8_plan_info {
+  int32_t n_splits;           /* KV ranges per sequence                                         */
+  int32_t waves;              /* per workgroup                                                  */
+  int32_t lanes_per_row;      /* head_dim / 16                                                  */
+  int32_t heads_per_lane;     /* query heads of a KV head one lane accumulates (1 / 2 / 4)      */
+  int32_t n_chunks;           /* group / heads_per_lane: workgroups that share a KV head        */
+  int32_t kv_heads_per_wave;  /* KV heads one wave load covers                                  */
+  int32_t rows_per_iter;      /* KV rows a workgroup covers with one load per lane              */
+  int32_t ring_depth;         /* K and V loads in flight per lane                               */
+  int64_t grid;               /* workgroups of the stream launch                                */
+  uint64_t lds_bytes;
+  uint64_t workspace_bytes;   /* 0 when n_splits == 1                                           */
+} slm_attn_fp8_plan_info;
+
+/* host-side only: what slm_paged_kv_fp8_attention would launch for `a` (pointers are not looked at) */
+SLM_API int slm_paged_kv_fp8_attention_plan(const slm_attn_fp8_args* a, slm_attn_fp8_plan_info* out);
+SLM_API int slm_paged_kv_fp8_attention(const slm_attn_fp8_args* a, void* stream);
+SLM_API int slm_kv_fp8_append(const int32_t* slot_ids,  /* [n_tokens]                        */
+                              const void* keys,         /* [n_tokens, n_kv_heads, head_dim] T */
+                              const void* values,
+                              int64_t k_token_stride,   /* elements                          */
+                              int64_t v_token_stride,
+                              const float* k_scale,     /* [n_kv_heads] fp32                 */
+                              const float* v_scale,
+                              void* key_cache,          /* [n_slots, n_kv_heads, head_dim] bytes, contiguous */
+                              void* value_cache,
+                              int64_t n_tokens, int32_t n_kv_heads, int32_t head_dim,
+                              int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,21 @@ class AttnArgs(C.Structure):
     ]
 
 
+class AttnFp8Args(C.Structure):
+    """struct slm_attn_fp8_args (include/slm_hip.h section 27): the fields of slm_attn_args that apply, then the scales."""
+    _fields_ = [f for f in AttnArgs._fields_ if f[0] not in ("total_kv_len", "phase", "n_slots")] + \
+        [("reserved", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+
+
+class AttnFp8PlanInfo(C.Structure):
+    """struct slm_attn_fp8_plan_info (include/slm_hip.h section 27)."""
+    _fields_ = [
+        ("n_splits", C.c_int32), ("waves", C.c_int32), ("lanes_per_row", C.c_int32), ("heads_per_lane", C.c_int32),
+        ("n_chunks", C.c_int32), ("kv_heads_per_wave", C.c_int32), ("rows_per_iter", C.c_int32),
+        ("ring_depth", C.c_int32), ("grid", C.c_int64), ("lds_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64),
+    ]
+
+
 class W4GemmArgs(C.Structure):
     """struct slm_w4_gemm_args (include/slm_hip.h)."""
     _fields_ = [
@@ -493,6 +508,13 @@ def lib() -> C.CDLL:
         ("slm_w8a8_linear_deferred_splits", C.c_int32, [C.POINTER(W8A8LinearArgs)]),
         ("slm_w8a8_linear_plan", C.c_int, [C.POINTER(W8A8LinearArgs), C.POINTER(LinearPlanInfo)]),
         ("slm_moe_w8a8_gemm", C.c_int, [C.POINTER(MoeW8A8GemmArgs), C.c_void_p]),
+        ("slm_paged_kv_fp8_attention", C.c_int, [C.POINTER(AttnFp8Args), C.c_void_p]),
+        ("slm_paged_kv_fp8_attention_plan", C.c_int, [C.POINTER(AttnFp8Args), C.POINTER(AttnFp8PlanInfo)]),
+        # section 27: (slot_ids, keys, values, k_token_stride, v_token_stride, k_scale, v_scale, key_cache, value_cache,
+        # n_tokens, n_kv_heads, head_dim, dtype, stream)
+        ("slm_kv_fp8_append", C.c_int,
+         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+          C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
         ("slm_moe_router", C.c_int, [C.POINTER(MoeRouterArgs), C.c_void_p]),
         ("slm_moe_router_splits", C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
         ("slm_moe_router_workspace_bytes", C.c_int,

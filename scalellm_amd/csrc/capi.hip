@@ -25,6 +25,7 @@ const char* const kTuneNames[TUNE_COUNT] = {
     "SLM_LINEAR_SPLITK",    "SLM_LINEAR_RT",        "SLM_LINEAR_NW",
     "SLM_W4A4_SPLITK",      "SLM_W4A4_RT",          "SLM_W4A4_NW",
     "SLM_W8A8_SPLITK",      "SLM_W8A8_RT",          "SLM_W8A8_NW",
+    "SLM_ATTN8_SPLITS",     "SLM_ATTN8_NW",
 };
 std::atomic<int32_t> g_tune[TUNE_COUNT];
 std::once_flag g_tune_once;
@@ -66,6 +67,7 @@ SLM_API const char* slm_status_string(int status) {
     case SLM_ERR_WORKSPACE: return "workspace missing or too small";
     case SLM_ERR_LAUNCH: return "kernel launch failed";
     case SLM_ERR_ALIGNMENT: return "pointer or stride not 16-byte aligned";
+    case SLM_ERR_SHAPE: return "size outside the entry point's set";
     default: return "unknown status";
   }
 }

@@ -52,4 +52,21 @@ __device__ __forceinline__ float scaled(float acc, float s) {
   return y;
 }
 
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+
+// THE T -> e4m3fn rule of the quantisers (slm_w8a8_quantize_act, slm_kv_fp8_append; callers divide by the scale first).
+// (v0, v1) -> two e4m3fn codes in the low (HI = false) or high half of `old`: clamp at +-448, round to nearest even; a
+// NaN (only a static scale lets one through) keeps its sign over the code 0x7F
+template <bool HI>
+__device__ __forceinline__ uint32_t f32x2_to_e4m3(uint32_t old, float v0, float v1) {
+  const float c0 = __builtin_fminf(__builtin_fmaxf(v0, -448.f), 448.f);
+  const float c1 = __builtin_fminf(__builtin_fmaxf(v1, -448.f), 448.f);
+  uint32_t r = __builtin_bit_cast(
+      uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(i16x2, old), c0, c1, 1.0f, HI));
+  constexpr int SH = HI ? 16 : 0;
+  if (v0 != v0) r = (r & ~(0xFFu << SH)) | ((0x7Fu | ((__builtin_bit_cast(uint32_t, v0) >> 24) & 0x80u)) << SH);
+  if (v1 != v1) r = (r & ~(0xFF00u << SH)) | ((0x7Fu | ((__builtin_bit_cast(uint32_t, v1) >> 24) & 0x80u)) << (SH + 8));
+  return r;
+}
+
 }  // namespace slm

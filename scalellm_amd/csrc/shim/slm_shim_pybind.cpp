@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <thread>
 
+#include "slm_attn_fp8_hip.h"
 #include "slm_attn_handler_hip.h"
 #include "slm_llama_hip.h"
 #include "slm_mla_hip.h"
@@ -40,6 +41,27 @@ PYBIND11_MODULE(_slm_shim, m) {
                            torch::Tensor value_cache) {
     llm::kernel::set_kv_cache(slot_ids, keys, values, key_cache, value_cache);
   });
+  // fp8 (e4m3) KV cache (slm_attn_fp8_hip.h)
+  m.def("set_kv_cache_fp8", [](const torch::Tensor& slot_ids, const torch::Tensor& keys, const torch::Tensor& values,
+                               torch::Tensor key_cache, torch::Tensor value_cache, const torch::Tensor& k_scale,
+                               const torch::Tensor& v_scale) {
+    slm::set_kv_cache_fp8(slot_ids, keys, values, key_cache, value_cache, k_scale, v_scale);
+  });
+  m.def("paged_kv_fp8_attention",
+        [](torch::Tensor out, const torch::Tensor& query, const torch::Tensor& key_cache,
+           const torch::Tensor& value_cache, const torch::Tensor& q_cu_lens, const torch::Tensor& kv_cu_lens,
+           const torch::Tensor& block_table, const torch::Tensor& block_cu_lens,
+           const std::optional<torch::Tensor>& alibi_slopes, int block_size, int max_q_len, int max_kv_len,
+           float sm_scale, const torch::Tensor& k_scale, const torch::Tensor& v_scale, float logits_soft_cap,
+           int sliding_window, int num_splits) {
+          slm::paged_kv_fp8_attention(out, query, key_cache, value_cache, q_cu_lens, kv_cu_lens, block_table,
+                                      block_cu_lens, alibi_slopes, block_size, max_q_len, max_kv_len, sm_scale, k_scale,
+                                      v_scale, logits_soft_cap, sliding_window, num_splits);
+        },
+        py::arg("out"), py::arg("query"), py::arg("key_cache"), py::arg("value_cache"), py::arg("q_cu_lens"),
+        py::arg("kv_cu_lens"), py::arg("block_table"), py::arg("block_cu_lens"), py::arg("alibi_slopes"),
+        py::arg("block_size"), py::arg("max_q_len"), py::arg("max_kv_len"), py::arg("sm_scale"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("logits_soft_cap") = 0.f, py::arg("sliding_window") = -1, py::arg("num_splits") = 0);
   m.def("apply_rotary_pos_emb",
         [](torch::Tensor query, torch::Tensor key, const torch::Tensor& positions,
            const torch::Tensor& cos_sin, int rotary_dim, bool interleaved) {

@@ -56,6 +56,8 @@ enum TuneKey : int {
   TUNE_W8A8_SPLITK,       // SLM_W8A8_SPLITK       forced K slices of the fp8 x fp8 linear (1..16; every slice keeps >= 1 chunk)
   TUNE_W8A8_RT,           // SLM_W8A8_RT           forced 32-row accumulator tiles per wave of the fp8 x fp8 linear (1/2/4)
   TUNE_W8A8_NW,           // SLM_W8A8_NW           forced waves per workgroup of the fp8 x fp8 linear (1/2/4; raised to the row tiles)
+  TUNE_ATTN8_SPLITS,      // SLM_ATTN8_SPLITS      forced split-KV count of the fp8 KV attention (attn_fp8.hip)
+  TUNE_ATTN8_NW,          // SLM_ATTN8_NW          waves per workgroup of the fp8 KV attention (4 / 8; default: 8 when a split holds >= 1024 rows)
   TUNE_COUNT
 };
 

@@ -57,7 +57,6 @@
 namespace slm {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int W8A8_RING = 3;  // weight / A register rings (chunks)
 
@@ -357,20 +356,7 @@ struct T16Bits<bf16_tag> { static constexpr uint32_t INF = 0x7F80u; };
 template <>
 struct T16Bits<f16_tag> { static constexpr uint32_t INF = 0x7C00u; };
 
-// (v0, v1) -> two e4m3fn codes in the low (HI = false) or high half of `old`: clamp at +-448, round to nearest even; a
-// NaN (only a static scale lets one through) keeps its sign over the code 0x7F
-template <bool HI>
-__device__ __forceinline__ uint32_t f32x2_to_e4m3(uint32_t old, float v0, float v1) {
-  const float c0 = __builtin_fminf(__builtin_fmaxf(v0, -448.f), 448.f);
-  const float c1 = __builtin_fminf(__builtin_fmaxf(v1, -448.f), 448.f);
-  uint32_t r = __builtin_bit_cast(
-      uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(i16x2, old), c0, c1, 1.0f, HI));
-  constexpr int SH = HI ? 16 : 0;
-  if (v0 != v0) r = (r & ~(0xFFu << SH)) | ((0x7Fu | ((__builtin_bit_cast(uint32_t, v0) >> 24) & 0x80u)) << SH);
-  if (v1 != v1) r = (r & ~(0xFF00u << SH)) | ((0x7Fu | ((__builtin_bit_cast(uint32_t, v1) >> 24) & 0x80u)) << (SH + 8));
-  return r;
-}
-
+// (the pair convert f32x2_to_e4m3 lives in fp8_cvt.h: the fp8 KV append shares it)
 template <typename T, int NV>
 __global__ void __launch_bounds__(W8A8_QT) w8a8_quantize_kernel(const char* __restrict__ a, int64_t lda_bytes,
                                                                 char* __restrict__ aq, int64_t ldaq,

@@ -176,8 +176,20 @@ class LlamaDecodeStep:
                  group_size: int = 128, dtype=torch.bfloat16, device="cuda", seed: int = 0,
                  kv_fill: str = "none", custom_allreduce=None, keep_checkpoint: bool = False,
                  gptq_sym: bool = False, fuse_silu: bool = True, desc_act: bool = False, bits: int = 4,
-                 act_quant: Optional[str] = None, fuse_act_quant: bool = False):
+                 act_quant: Optional[str] = None, fuse_act_quant: bool = False, kv_cache_dtype: str = "auto",
+                 kv_scales=None):
         pa = parallel_args or ParallelArgs()
+        # kv_cache_dtype "fp8": every layer's KV cache holds e4m3 codes under static per-head scales (layers.KVCache,
+        # slm_hip.h section 27) -- the append quantises, the attention streams bytes.  kv_scales: per layer
+        # (k_scale, v_scale), each a scalar or [n_kv_heads]; None = ones.  Independent of the linears: any quant_method.
+        # One lane, one rank.  "auto" (default): the cache holds `dtype`, the path as it always was.
+        if kv_cache_dtype not in ("auto", "fp8"):
+            raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} must be 'auto' or 'fp8'")
+        self.kv_fp8 = kv_cache_dtype == "fp8"
+        if self.kv_fp8 and pa.world_size != 1:
+            raise ValueError("kv_cache_dtype='fp8' runs on one rank (no tensor-parallel form)")
+        if kv_scales is not None and (not self.kv_fp8 or len(kv_scales) != shape.n_layers):
+            raise ValueError("kv_scales: one (k_scale, v_scale) per layer, with kv_cache_dtype='fp8'")
         # act_quant "mxfp4" (with quant_method "mxfp4" only): the four linears quantise their activations to MXFP4 as
         # they load them and run the block-scaled MFMA (kernels.w4a4_linear): W4A4, no launch more than W4A16
         # act_quant "fp8" (with quant_method "fp8" only): every linear quantises its input to e4m3 with one dynamic scale
@@ -233,6 +245,10 @@ class LlamaDecodeStep:
         _lm = os.environ.get("SLM_DECODE_LANES", "auto")
         # (auto on a dense step: one lane -- the two-lane constants were measured for int4 weights only)
         self.lanes_min = (0 if dense else -1) if _lm == "auto" else int(_lm)
+        if self.kv_fp8:   # the fp8 attention has no hand-over between two streams: one lane
+            if self.lanes_min > 0:
+                raise ValueError("kv_cache_dtype='fp8' runs one lane: it cannot be combined with two decode lanes")
+            self.lanes_min = 0
         self.lanes_chain = os.environ.get("SLM_DECODE_LANES_CHAIN", "1") != "0"
         self._side_stream = None
         self._lane_bufs = {}
@@ -268,7 +284,7 @@ class LlamaDecodeStep:
                 self._build_dense_linears(L, gen, keep_checkpoint, fuse_silu)
                 L["in_norm"] = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
                 L["post_norm"] = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
-                L["kv"] = KVCache(n_blocks, block_size, self.n_kv_heads, D, dtype, self.device)
+                L["kv"] = self._new_kv_cache(len(self.layers), n_blocks, block_size, kv_scales)
                 self.layers.append(L)
                 continue
             L["qkv"] = ColumnParallelQLinear(H, qkv_n * tp, False, qa, False, pa, dtype, self.device)
@@ -303,7 +319,7 @@ class LlamaDecodeStep:
                 L[name]._repack()
             L["in_norm"] = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
             L["post_norm"] = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
-            L["kv"] = KVCache(n_blocks, block_size, self.n_kv_heads, D, dtype, self.device)
+            L["kv"] = self._new_kv_cache(len(self.layers), n_blocks, block_size, kv_scales)
             self.layers.append(L)
         self.final_norm = (1 + 0.05 * torch.randn(H, device=self.device, generator=gen)).to(dtype)
         # hidden-sharded embedding + all-gather (embedding.h:74-81); vocab-sharded lm_head, gathered
@@ -326,6 +342,24 @@ class LlamaDecodeStep:
                             act_s=u8(T, inter // 32))
         if kv_fill != "none":
             self.fill_kv(kv_fill, gen)
+
+    def _new_kv_cache(self, li: int, n_blocks: int, block_size: int, kv_scales) -> KVCache:
+        if not self.kv_fp8:
+            return KVCache(n_blocks, block_size, self.n_kv_heads, self.shape.head_dim, self.dtype, self.device)
+        ks, vs = kv_scales[li] if kv_scales is not None else (None, None)
+        return KVCache(n_blocks, block_size, self.n_kv_heads, self.shape.head_dim, torch.float8_e4m3fn, self.device,
+                       k_scale=ks, v_scale=vs)
+
+    def load_kv_scales(self, state_dict: dict) -> None:
+        """The static KV scales of an fp8 export: model.layers.{i}.self_attn.k_scale / v_scale (a scalar per tensor, or
+        one value per KV head), as compressed-tensors, Quark and vLLM exports name them.  A layer without them keeps
+        what it has."""
+        if not self.kv_fp8:
+            raise ValueError("load_kv_scales needs kv_cache_dtype='fp8'")
+        for i, L in enumerate(self.layers):
+            pre = f"model.layers.{i}.self_attn."
+            L["kv"].set_scales(state_dict.get(pre + "k_scale", L["kv"].k_scale),
+                               state_dict.get(pre + "v_scale", L["kv"].v_scale))
 
     def _build_dense_linears(self, L: dict, gen, keep_checkpoint: bool, fuse_silu: bool) -> None:
         """The four unquantised linears of one layer: every rank draws the SAME full weights [N, K] and keeps its
@@ -408,6 +442,15 @@ class LlamaDecodeStep:
         timing -- no two layers alias, nothing fits a cache)."""
         blk = None
         for li, L in enumerate(self.layers):
+            if self.kv_fp8:   # byte caches: the codes of a normal draw under the layer's scales
+                for t, sc in zip(L["kv"].get_kv_cache(), (L["kv"].k_scale, L["kv"].v_scale)):
+                    if blk is None:
+                        blk = torch.randn(min(t.size(0), 1 << 16), t.size(1), t.size(2), device=self.device,
+                                          dtype=self.dtype, generator=gen)
+                    for r0 in range(0, t.size(0), blk.size(0)):
+                        seg = t[r0:r0 + blk.size(0)]
+                        seg.copy_(kernels.quantize_fp8_kv(blk[:seg.size(0)], sc).view(torch.uint8))
+                continue
             for ti, t in enumerate(L["kv"].get_kv_cache()):
                 if mode == "consistent":
                     # same full-head history on every rank (tests): draw all heads, keep this shard
@@ -433,7 +476,8 @@ class LlamaDecodeStep:
         s = self.shape
 
         def need_for(rows: int) -> int:
-            need = rows * self.n_heads * 256 * (s.head_dim + 2) * 4  # worst-case split-KV partials
+            # worst-case split-KV partials (256 splits: the bound of the fp8 KV attention's plan as well)
+            need = rows * self.n_heads * 256 * (s.head_dim + 2) * 4
             need = max(need, 64 * rows * max(2 * s.intermediate // self.pa.world_size, s.hidden) * 4)
             return min(need, 4 << 30)
         # deferred split-K slabs (o / down / qkv leave up to 16 fp32 slabs for their consumer): both slots
@@ -592,6 +636,8 @@ class LlamaDecodeStep:
     @contextlib.contextmanager
     def graph_variant(self, variant):
         """Pin the step to `variant`'s lane count (while its graph is captured)."""
+        if self.kv_fp8 and int(variant[0]) != 1:
+            raise ValueError("kv_cache_dtype='fp8' runs one lane")
         prev, self._pinned_lanes = self._pinned_lanes, int(variant[0])
         try:
             yield
@@ -977,6 +1023,10 @@ def hf_state_dict(step: "LlamaDecodeStep") -> dict:
     nq, nkv, inter = s.n_heads * D, s.n_kv_heads * D, s.intermediate
     sd = {"model.embed_tokens.weight": step.embed, "model.norm.weight": step.final_norm,
           "lm_head.weight": step.lm_head.t()}   # [vocab, hidden] in a checkpoint
+    if getattr(step, "kv_fp8", False):   # the static KV scales under the names of the fp8 exports (load_kv_scales)
+        for i, L in enumerate(step.layers):
+            sd[f"model.layers.{i}.self_attn.k_scale"] = L["kv"].k_scale
+            sd[f"model.layers.{i}.self_attn.v_scale"] = L["kv"].v_scale
 
     if step.dense:   # plain *.weight tensors [out, in]: q | k | v and gate | up are row ranges of the fused shards
         # (an fp8 step: float8_e4m3fn *.weight plus the fp32 per-channel *.weight_scale, cut by the same rows)

@@ -406,6 +406,152 @@ def set_kv_cache(slot_ids: torch.Tensor, keys: torch.Tensor, values: torch.Tenso
                              _dtype_code(keys), _stream()), "slm_set_kv_cache")
 
 
+# ---------------------------------------------------------------------------------------
+# fp8 (e4m3) KV cache (include/slm_hip.h section 27): byte caches [n_slots, n_kv_heads, head_dim], one static fp32
+# scale per KV head, element = code * scale
+# ---------------------------------------------------------------------------------------
+FP8_KV_DTYPE = torch.float8_e4m3fn
+
+
+def quantize_fp8_kv(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """[..., n_kv_heads, head_dim] values -> e4m3 codes under the per-head scales [n_kv_heads]: THE rule of
+    set_kv_cache_fp8 in plain torch (fp32 division, clamp at +-448, round to nearest even)."""
+    return (x.float() / scale.float().view(-1, 1)).clamp(-448.0, 448.0).to(FP8_KV_DTYPE)
+
+
+def dequantize_fp8_kv(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """e4m3 codes (float8_e4m3fn or their bytes) [..., n_kv_heads, head_dim] -> code * scale of its head."""
+    if codes.dtype != FP8_KV_DTYPE:
+        codes = codes.view(FP8_KV_DTYPE)
+    return (codes.float() * scale.float().view(-1, 1)).to(dtype)
+
+
+def _fp8_kv_bytes(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype == FP8_KV_DTYPE:
+        return t.view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise SlmError(f"{what} must hold e4m3 codes (float8_e4m3fn or uint8), not {t.dtype}")
+    return t
+
+
+def _fp8_kv_scale(s: torch.Tensor, n_kv_heads: int, what: str) -> torch.Tensor:
+    if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != n_kv_heads:
+        raise SlmError(f"{what} must be contiguous float32 [n_kv_heads]")
+    return s
+
+
+def set_kv_cache_fp8(slot_ids: torch.Tensor, keys: torch.Tensor, values: torch.Tensor, key_cache: torch.Tensor,
+                     value_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+    """set_kv_cache into e4m3 caches: cache[slot_ids[t], h] = quantize_fp8_kv(x[t, h], scale[h]), bit for bit, one
+    launch.  keys / values [n_tokens, n_kv_heads, head_dim] f16 / bf16 (column slices of a qkv row are fine)."""
+    L = _lib.lib()
+    _require_gpu(slot_ids, keys, values, key_cache, value_cache, k_scale, v_scale)
+    if slot_ids.dtype != torch.int32 or not slot_ids.is_contiguous():
+        raise SlmError("slot_ids must be contiguous int32")
+    if keys.dim() != 3 or keys.shape != values.shape or keys.dtype != values.dtype:
+        raise SlmError("keys / values must be [n_tokens, n_kv_heads, head_dim] of one dtype")
+    for t in (keys, values):
+        if t.stride(-1) != 1 or t.stride(-2) != t.size(-1):
+            raise SlmError("keys/values must be contiguous in their last two dims")
+    kc, vc = _fp8_kv_bytes(key_cache, "key_cache"), _fp8_kv_bytes(value_cache, "value_cache")
+    if not (kc.is_contiguous() and vc.is_contiguous()) or kc.shape[1:] != keys.shape[1:] or vc.shape != kc.shape:
+        raise SlmError("caches must be contiguous [n_slots, n_kv_heads, head_dim] bytes")
+    if slot_ids.numel() != keys.size(0):
+        raise SlmError("slot_ids / keys / values token counts differ")
+    check(L.slm_kv_fp8_append(slot_ids.data_ptr(), keys.data_ptr(), values.data_ptr(), keys.stride(0),
+                              values.stride(0), _fp8_kv_scale(k_scale, keys.size(1), "k_scale").data_ptr(),
+                              _fp8_kv_scale(v_scale, keys.size(1), "v_scale").data_ptr(), kc.data_ptr(),
+                              vc.data_ptr(), keys.size(0), keys.size(1), keys.size(2), _dtype_code(keys), _stream()),
+          "slm_kv_fp8_append")
+
+
+def _attn_fp8_args(out, query, key_cache, value_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens,
+                   alibi_slopes, block_size, max_q_len, max_kv_len, sm_scale, k_scale, v_scale, logits_soft_cap,
+                   sliding_window, num_splits) -> "_lib.AttnFp8Args":
+    kc, vc = _fp8_kv_bytes(key_cache, "key_cache"), _fp8_kv_bytes(value_cache, "value_cache")
+    _require_gpu(out, query, kc, vc, q_cu_lens, kv_cu_lens, block_table, block_cu_lens, alibi_slopes, k_scale, v_scale)
+    if query.dim() != 3 or kc.dim() != 3 or vc.dim() != 3 or out.dim() != 3:
+        raise SlmError("query/out must be [n_tokens, n_heads, head_dim]; caches [n_slots, n_kv_heads, head_dim]")
+    for t in (out, query, kc, vc):
+        if t.stride(-1) != 1:
+            raise SlmError("last dimension must be contiguous")
+    for t in (q_cu_lens, kv_cu_lens, block_table, block_cu_lens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SlmError("index tensors must be contiguous int32")
+    if out.dtype != query.dtype:
+        raise SlmError("out/query dtypes must match")
+    a = _lib.AttnFp8Args()
+    a.out, a.query, a.key_cache, a.value_cache = out.data_ptr(), query.data_ptr(), kc.data_ptr(), vc.data_ptr()
+    a.o_stride[0], a.o_stride[1] = out.stride(0), out.stride(1)
+    a.q_stride[0], a.q_stride[1] = query.stride(0), query.stride(1)
+    a.k_stride[0], a.k_stride[1] = kc.stride(0), kc.stride(1)
+    a.v_stride[0], a.v_stride[1] = vc.stride(0), vc.stride(1)
+    a.q_cu_lens, a.kv_cu_lens = q_cu_lens.data_ptr(), kv_cu_lens.data_ptr()
+    a.block_table, a.block_cu_lens = block_table.data_ptr(), block_cu_lens.data_ptr()
+    a.alibi_slopes = alibi_slopes.data_ptr() if alibi_slopes is not None else None   # (refused by the library)
+    a.dtype = _dtype_code(query)
+    a.batch_size, a.n_tokens = q_cu_lens.numel() - 1, query.size(0)
+    a.n_heads, a.n_kv_heads, a.head_dim = query.size(1), kc.size(1), query.size(2)
+    a.block_size, a.max_q_len, a.max_kv_len = int(block_size), int(max_q_len), int(max_kv_len)
+    a.sm_scale, a.logits_soft_cap, a.sliding_window = float(sm_scale), float(logits_soft_cap), int(sliding_window)
+    a.num_splits = int(num_splits)
+    a.workspace, a.workspace_bytes = None, 0
+    a.k_scale = _fp8_kv_scale(k_scale, kc.size(1), "k_scale").data_ptr()
+    a.v_scale = _fp8_kv_scale(v_scale, kc.size(1), "v_scale").data_ptr()
+    return a
+
+
+def _attn_fp8_plan(a) -> "_lib.AttnFp8PlanInfo":
+    info = _lib.AttnFp8PlanInfo()
+    check(_lib.lib().slm_paged_kv_fp8_attention_plan(C.byref(a), C.byref(info)), "slm_paged_kv_fp8_attention_plan")
+    return info
+
+
+def paged_kv_fp8_attention_plan(out, query, key_cache, value_cache, q_cu_lens, kv_cu_lens, block_table,
+                                block_cu_lens, alibi_slopes, block_size, max_q_len, max_kv_len, sm_scale, k_scale,
+                                v_scale, logits_soft_cap=0.0, sliding_window=-1, num_splits=0):
+    """What paged_kv_fp8_attention would launch for these arguments (host-side only): split count, launch shape,
+    workspace_bytes."""
+    return _attn_fp8_plan(_attn_fp8_args(out, query, key_cache, value_cache, q_cu_lens, kv_cu_lens, block_table,
+                                         block_cu_lens, alibi_slopes, block_size, max_q_len, max_kv_len, sm_scale,
+                                         k_scale, v_scale, logits_soft_cap, sliding_window, num_splits))
+
+
+def paged_kv_fp8_attention(
+    out: torch.Tensor,            # [n_tokens, n_heads, head_dim] f16 / bf16
+    query: torch.Tensor,          # [n_tokens, n_heads, head_dim]
+    key_cache: torch.Tensor,      # [n_slots, n_kv_heads, head_dim] e4m3 codes (float8_e4m3fn or uint8)
+    value_cache: torch.Tensor,
+    q_cu_lens: torch.Tensor,
+    kv_cu_lens: torch.Tensor,
+    block_table: torch.Tensor,
+    block_cu_lens: torch.Tensor,
+    alibi_slopes: Optional[torch.Tensor],  # must be None: the fp8 stream kernel has no alibi form
+    block_size: int,
+    max_q_len: int,
+    max_kv_len: int,
+    sm_scale: float,
+    k_scale: torch.Tensor,        # [n_kv_heads] fp32
+    v_scale: torch.Tensor,        # [n_kv_heads] fp32
+    logits_soft_cap: float = 0.0,
+    sliding_window: int = -1,
+    num_splits: int = 0,
+) -> None:
+    """paged_kv_varlen_mha over an e4m3 KV cache: the same arguments plus the per-head scales; writes `out` in place,
+    async on the current stream.  Every row runs on the token-major stream kernel: fast for q_len = 1, correct but
+    slow for prefill chunks (the history is streamed once per query token)."""
+    a = _attn_fp8_args(out, query, key_cache, value_cache, q_cu_lens, kv_cu_lens, block_table, block_cu_lens,
+                       alibi_slopes, block_size, max_q_len, max_kv_len, sm_scale, k_scale, v_scale, logits_soft_cap,
+                       sliding_window, num_splits)
+    need = _attn_fp8_plan(a).workspace_bytes
+    if a.n_tokens == 0 or a.batch_size == 0:
+        return
+    if need:
+        ws = reserve_workspace(need, query.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(_lib.lib().slm_paged_kv_fp8_attention(C.byref(a), _stream()), "slm_paged_kv_fp8_attention")
+
+
 def decode_advance(positions: torch.Tensor, kv_cu_lens: torch.Tensor, new_cache_slots: torch.Tensor,
                    block_table: torch.Tensor, block_cu_lens: torch.Tensor, block_size: int,
                    overflow_flag: torch.Tensor | None = None) -> None:

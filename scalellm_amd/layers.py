@@ -71,14 +71,33 @@ def uniform_kv_hint(kv_total_len: int, n_seqs: int, q_max_seq_len: int, kv_max_s
 
 
 class KVCache:
-    """[n_blocks * block_size, n_kv_heads, head_dim] K and V tensors (memory/kv_cache.cpp:15-27)."""
+    """[n_blocks * block_size, n_kv_heads, head_dim] K and V tensors (memory/kv_cache.cpp:15-27).
+
+    dtype torch.float8_e4m3fn: byte caches of e4m3 codes (uint8 tensors) with one static fp32 scale per KV head,
+    element = code * scale (slm_hip.h section 27).  k_scale / v_scale: a scalar (a per-tensor checkpoint scale, repeated)
+    or [n_kv_heads]; missing = ones.  Any other dtype: the scales are not looked at."""
 
     def __init__(self, n_blocks: int, block_size: int, n_kv_heads: int, head_dim: int,
-                 dtype: torch.dtype, device):
+                 dtype: torch.dtype, device, k_scale=None, v_scale=None):
         self._block_size = block_size
-        self.key_cache = torch.empty(n_blocks * block_size, n_kv_heads, head_dim, dtype=dtype,
-                                     device=device)
+        self.is_fp8 = dtype == torch.float8_e4m3fn
+        self.key_cache = torch.empty(n_blocks * block_size, n_kv_heads, head_dim,
+                                     dtype=torch.uint8 if self.is_fp8 else dtype, device=device)
         self.value_cache = torch.empty_like(self.key_cache)
+        self.k_scale = self.v_scale = None
+        if self.is_fp8:
+            self.set_scales(k_scale, v_scale)
+
+    def set_scales(self, k_scale=None, v_scale=None) -> None:
+        def vec(s):
+            s = torch.ones(()) if s is None else torch.as_tensor(s)
+            return s.detach().to(device=self.key_cache.device, dtype=torch.float32).reshape(-1).expand(
+                self.key_cache.size(1)).contiguous()
+        if self.k_scale is None:
+            self.k_scale, self.v_scale = vec(k_scale), vec(v_scale)
+        else:   # in place: a graph captured earlier keeps reading these tensors
+            self.k_scale.copy_(vec(k_scale))
+            self.v_scale.copy_(vec(v_scale))
 
     def block_size(self) -> int:
         return self._block_size
@@ -87,6 +106,10 @@ class KVCache:
         return self.key_cache, self.value_cache
 
     def set_kv_cache(self, slot_ids: torch.Tensor, keys: torch.Tensor, values: torch.Tensor) -> None:
+        if self.is_fp8:
+            kernels.set_kv_cache_fp8(slot_ids, keys, values, self.key_cache, self.value_cache, self.k_scale,
+                                     self.v_scale)
+            return
         kernels.set_kv_cache(slot_ids, keys, values, self.key_cache, self.value_cache)
 
 
@@ -134,6 +157,19 @@ class HipAttnHandler:
     def append_kv_cache(self, kv_cache: KVCache, query, key, value, input_params: InputParameters):
         kc, vc = kv_cache.get_kv_cache()
         partials, self.qkv_partials = self.qkv_partials, None
+        if getattr(kv_cache, "is_fp8", False):
+            # e4m3 cache: the RoPE entry runs without slot_ids (it still consumes deferred qkv slabs and leaves the
+            # rotated k in place), then the quantising append -- one launch more than the fused RoPE + append
+            if self.q_norm is not None:
+                raise kernels.SlmError("the QK-norm prologue has no fp8 KV cache form")
+            if self._pending is not None:
+                kernels.apply_rotary_pos_emb(query, key, self._pending, self.cos_sin, self.rotary_dim,
+                                             self.interleaved, value=value, partials=partials)
+                self._pending = None
+            elif partials:
+                raise kernels.SlmError("deferred qkv partials need the rotary path (no RoPE configured)")
+            kv_cache.set_kv_cache(input_params.new_cache_slots, key, value)
+            return
         if self.q_norm is not None:
             if self._pending is None:
                 raise kernels.SlmError("the QK-norm prologue needs positions")
@@ -168,6 +204,18 @@ class HipAttnHandler:
     def batch_decode(self, query, kv_cache: KVCache, input_params: InputParameters,
                      sliding_window: int, output: torch.Tensor, phase: int = 0) -> None:
         kc, vc = kv_cache.get_kv_cache()
+        if getattr(kv_cache, "is_fp8", False):
+            if phase != 0:
+                raise kernels.SlmError("the fp8 KV attention has no phase split (one lane only)")
+            kernels.paged_kv_fp8_attention(output, query, kc, vc, input_params.q_cu_seq_lens,
+                                           input_params.kv_cu_seq_lens, input_params.block_tables,
+                                           input_params.cu_block_lens, self.alibi_slopes, kv_cache.block_size(),
+                                           input_params.q_max_seq_len,
+                                           kernels.visible_kv_hint(input_params.kv_max_seq_len,
+                                                                   input_params.q_max_seq_len, sliding_window),
+                                           self.sm_scale, kv_cache.k_scale, kv_cache.v_scale, self.logits_soft_cap,
+                                           sliding_window)
+            return
         total = getattr(input_params, "kv_total_len", 0)
         if total == 0 and not torch.cuda.is_current_stream_capturing():
             # (an unchanged engine fills no hint: the sizes it hands over settle the uniform case.  Not under
